@@ -9,25 +9,38 @@ exchange over xGMI (mrg_job_shuffle; torch.distributed only hands out the commun
 Weak scaling: per-GPU work is fixed.  --workload unique: configs[4] (C5), near-unique 12-char keys;
 --workload zipf_u: the C3 text with Gutenberg-like Unicode (the reference corpus's kind of text).
 
-The default N = 1 run adds, beside the C3 line: a `cold` object (the first job on a fresh Context over
+A plain run sets up, warms up, times the K steps, writes its outputs if --dump-outputs is given and
+prints the C3 line; everything below is measured only with --full.
+
+The --full N = 1 run adds, beside the C3 line: a `cold` object (the first job on a fresh Context over
 the same resident input -- what mrg_run_job and every one-shot worker call run -- with the pool's device
 allocations reported apart from the kernels), the end-to-end leg (files on disk -> mrg_run_job), a
 zipf_u sub-object (k_map GB/s on Unicode text against the ASCII rate), a c5 sub-object (configs[4] at
 50 x 256 MiB, 3 timed steps, with its own `cold` object), a c2 sub-object (the indexer's latency on the
-bundled corpus, configs[1]) and the CPU baseline; --quick leaves all of them out.
+bundled corpus, configs[1]), the CPU baseline and the D2H time of the output; --quick (kept for older
+command lines) leaves all of them out again.
+
+--dump-outputs DIR: after the timed steps, what the last timed step left for its caller (the bytes of
+every mr-{r}.txt, mrg_job_output) is written to DIR as .npy arrays: `output_bytes` (float32: every
+byte in partition order, or a fixed seeded sample of 15e6 positions of a larger output),
+`partition_offsets` (float64, nReduce + 1), `partition_byte_sums` (float64, the sum of every
+partition's bytes) and `counters` (float64: tokens, distinct keys, output bytes; not the map records,
+whose number depends on the order in which workgroups combine).  The input is a function of the
+arguments alone (--seed), so two builds can be compared array by array.
+At N > 1 every rank writes its own partitions as `<name>_rank<i>.npy`.
 
 A step = one whole job over the resident input: map (tokenize + combine) -> aggregate + SipHash
 partition -> [shuffle] -> sort -> format; the output bytes of every mr-{r}.txt are in HBM at the end
 of the step.  Input is resident in HBM before the timed region (host I/O and H2D are excluded; the
-D2H of the output is measured after the timed loop and reported beside `value`).
+D2H of the output is measured after the timed loop, with --full, and reported beside `value`).
 
 `value` = input bytes of all ranks per step / the MEDIAN step time (each step's time is the max over
 ranks); `ms_per_step` is that median; the mean over the bracketed K steps is reported as well.
 
-Launch: python bench.py [--gpus N --steps K --warmup W].  N > 1: under torch.distributed.run (one rank
-per GPU), or without a launcher, when bench.py starts the N ranks itself before touching the GPU; it
-exits non-zero if fewer than N GPUs are visible, and the line carries `rccl_nranks` (ncclCommCount of
-the library's communicator) beside `n_gpus`.
+Launch: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR].
+N > 1: under torch.distributed.run (one rank per GPU), or without a launcher, when bench.py starts the
+N ranks itself before touching the GPU; it exits non-zero if fewer than N GPUs are visible, and the
+line carries `rccl_nranks` (ncclCommCount of the library's communicator) beside `n_gpus`.
 """
 import argparse
 import gzip
@@ -72,7 +85,12 @@ def parse():
     ap.add_argument("--no-zipf-u", action="store_true", help="skip the Gutenberg-like Unicode leg (N = 1)")
     ap.add_argument("--no-c5", action="store_true", help="skip the C5 leg (N = 1)")
     ap.add_argument("--no-c2", action="store_true", help="skip the C2 indexer latency leg (N = 1)")
-    ap.add_argument("--quick", action="store_true", help="the headline C3 line only (no extra legs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the extra legs: cold job, end to end, zipf_u, C5, C2, CPU baseline, output D2H")
+    ap.add_argument("--quick", action="store_true",
+                    help="the headline C3 line only (no extra legs): what a run without --full does")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's output to DIR/<name>.npy (float32 / float64, at most 64 MB)")
     ap.add_argument("--c5-files", type=int, default=50, help="C5 leg: 256 MiB files (50 = configs[4]'s 1e9 keys)")
     ap.add_argument("--lds-cap", type=int, default=0)
     ap.add_argument("--shuffle-1", action="store_true",
@@ -248,6 +266,36 @@ def time_steps(ctx, step, steps, warmup, dev, world, rank, label):
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     return t[0].item(), t[1:].tolist(), stats
+
+
+DUMP_MAX_BYTES = 15 * 10**6  # output bytes dumped whole (60 MB as float32; C3 has 13.1e6); a larger output is sampled
+
+
+def dump_outputs(ctx, st, out_dir, rank, world):
+    """--dump-outputs: the output of the job the context holds (the last timed step's), copied to the
+    host through mrg_job_copy_output as a caller would, written as .npy arrays (see the module text)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    _, off = ctx.output()
+    n = off[-1]
+    host = np.zeros(max(n, 1), dtype=np.uint8)
+    ctx.copy_output_to(host.ctypes.data, n)
+    host = host[:n]
+    if n > DUMP_MAX_BYTES:
+        idx = np.sort(np.random.default_rng(0x5EED2026).integers(0, n, DUMP_MAX_BYTES))
+        sample = host[idx].astype(np.float32)
+    else:
+        sample = host.astype(np.float32)
+    sums = [float(host[off[r]:off[r + 1]].sum(dtype=np.uint64)) for r in range(len(off) - 1)]
+    arrays = {"output_bytes": sample,
+              "partition_offsets": np.asarray(off, dtype=np.float64),
+              "partition_byte_sums": np.asarray(sums, dtype=np.float64),
+              "counters": np.asarray([st["tokens"], st["distinct_keys"], st["output_bytes"]], dtype=np.float64)}
+    sfx = f"_rank{rank}" if world > 1 else ""
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{sfx}.npy"), arr)
+    log(f"--dump-outputs: {n} output bytes of {len(off) - 1} partitions -> {out_dir} "
+        f"({sum(x.nbytes for x in arrays.values())} bytes in {len(arrays)} arrays)")
 
 
 def med(stats, k):
@@ -478,7 +526,8 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
-    if a.quick:
+    extras = a.full and not a.quick
+    if not extras:
         a.no_e2e = a.no_cpu_baseline = a.no_zipf_u = a.no_c5 = a.no_c2 = True
     gpu = local % max(1, torch.cuda.device_count())  # = local on a node with one GPU per rank
     torch.cuda.set_device(gpu)
@@ -520,17 +569,22 @@ def main():
     m = statistics.median(step_max)
     st = ctx.stats()
 
+    if a.dump_outputs:
+        dump_outputs(ctx, st, a.dump_outputs, rank, world)
+
     # D2H of the mr-{r}.txt bytes into a pinned host buffer (what a worker writing the files pays
     # over PCIe; not in `value`: reported beside it).  The buffer is allocated outside the timing.
-    _, out_off = ctx.output()
-    out_n = out_off[-1]
-    host_out = torch.empty(max(out_n, 1), dtype=torch.uint8, pin_memory=True)
-    host_out.zero_()  # first touch of the pages outside the timing (a 15 GB C5 output otherwise faults them in)
-    torch.cuda.synchronize(dev)
-    td = time.perf_counter()
-    ctx.copy_output_to(host_out.data_ptr(), out_n)
-    d2h_ms = (time.perf_counter() - td) * 1e3
-    del host_out
+    d2h_ms = None
+    if extras:
+        _, out_off = ctx.output()
+        out_n = out_off[-1]
+        host_out = torch.empty(max(out_n, 1), dtype=torch.uint8, pin_memory=True)
+        host_out.zero_()  # first touch of the pages outside the timing (a 15 GB C5 output otherwise faults them in)
+        torch.cuda.synchronize(dev)
+        td = time.perf_counter()
+        ctx.copy_output_to(host_out.data_ptr(), out_n)
+        d2h_ms = (time.perf_counter() - td) * 1e3
+        del host_out
 
     value = shard * world / m / 1e9
     med_map_ms = med(stats, "ms_map")
@@ -605,8 +659,8 @@ def main():
         "xgmi": xgmi,
         "timing": {"value_basis": "median step (max over ranks)", "ms_per_step_mean": round(dt / a.steps * 1e3, 3),
                    "value_mean": round(shard * world * a.steps / dt / 1e9, 3),
-                   "output_d2h_ms": round(d2h_ms, 3),
-                   "value_with_output_d2h": round(shard * world / (m + d2h_ms / 1e3) / 1e9, 3)},
+                   "output_d2h_ms": round(d2h_ms, 3) if extras else None,
+                   "value_with_output_d2h": round(shard * world / (m + d2h_ms / 1e3) / 1e9, 3) if extras else None},
         "stages_ms": {k: round(med(stats, k), 3) for k in ("ms_map", "ms_aggregate", "ms_sort", "ms_format")},
         "job": {"tokens": st["tokens"], "map_records": st["map_records"], "distinct_keys": st["distinct_keys"],
                 "output_bytes": out_bytes, "map_launches": [s["map_launches"] for s in stats],
@@ -614,7 +668,7 @@ def main():
                 "agg_path": st["agg_path"]},
     }
     single = world == 1 and a.workload == "zipf" and not a.shuffle_1
-    if world == 1 and not a.shuffle_1 and not a.quick:
+    if world == 1 and not a.shuffle_1 and extras:
         line["cold"] = cold_job(dev, buf, doc_off, a.reduce, stats)
     if single and not a.no_e2e:
         line["end_to_end"] = end_to_end(buf, files, fbytes, a.reduce)

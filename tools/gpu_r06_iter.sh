@@ -7,5 +7,6 @@ NO_TESTS=1 VARIANTS="lib lib_variants/w12 lib_variants/w8 lib lib_variants/w12 l
 rc=$?; cat gpurun_out/waves.log; [ $rc -ne 0 ] && exit $rc
 bash tools/gpu_r06_c5w.sh > gpurun_out/c5w.log 2>&1
 rc=$?; cat gpurun_out/c5w.log; [ $rc -ne 0 ] && exit $rc
-timeout -k 10 300 python -u bench.py --no-cpu-baseline --no-zipf-u --no-c5 --no-c2 > gpurun_out/c3_e2e.log 2>&1
-rc=$?; grep -E "cold job|end-to-end" gpurun_out/c3_e2e.log; exit $rc
+bench_log=${BENCH_LOG:-$(mktemp -t mrg_bench.XXXXXX)}  # the bench.py --full log (stderr progress + the result line)
+timeout -k 10 300 python -u bench.py --full --no-cpu-baseline --no-zipf-u --no-c5 --no-c2 > "$bench_log" 2>&1
+rc=$?; grep -E "cold job|end-to-end" "$bench_log"; exit $rc
