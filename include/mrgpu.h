@@ -55,6 +55,9 @@ extern "C" {
 /* bits 8..15: truncate every internal (non-partition) hash to this many bits; 0 = full 64 bits.
    A test knob that forces hash collisions so the full-string tie-break paths are exercised. */
 #define MRG_FLAG_DEBUG_HASH_BITS(n) (((uint32_t)(n) & 0xFFu) << 8)
+/* bits 16..31, mrg_run_job only (word count; every other entry point ignores them): also write
+   out_dir/top.txt, the k (1..65535) most frequent lines of final.txt, see mrg_job_topk. */
+#define MRG_FLAG_TOP(k) (((uint32_t)(k) & 0xFFFFu) << 16)   /* mrg_run_job only: also write out_dir/top.txt */
 
 /* Exchange record (mrg_job_export / mrg_job_import / mrg_parts): 24 bytes, little-endian.
  *   short key (len <= 16):
@@ -105,7 +108,8 @@ typedef struct {
 /* ABI history: 1 = round-1 layout; 2 = mrg_run_job's last argument is n_gpus (was a device index);
  * 3 = 24-byte exchange records (were 40), mrg_run_get_stats; 4 = mrg_stats gains nonascii_tiles,
  * tail_records_16, spec_agg, agg_path; 5 = mrg_stats gains map_kind, mrg_comm_count, mrg_pool_stats;
- * 6 = mrg_pool_alloc_stats.  mrg_version() names the ABI it implements. */
+ * 6 = mrg_pool_alloc_stats.  mrg_version() names the ABI it implements.
+ * (6, additive): mrg_job_topk, mrg_job_copy_topk, MRG_FLAG_TOP */
 #define MRG_ABI_VERSION 6
 
 const char *mrg_last_error(void);
@@ -156,6 +160,15 @@ int mrg_job_copy_output(mrg_ctx *ctx, uint8_t *h_dst, uint64_t cap);
  * bytewise (= by key: key bytes are all > ' ').  *d_out stays valid until the next job call. */
 int mrg_job_final(mrg_ctx *ctx, const uint8_t **d_out, uint64_t *h_bytes);
 int mrg_job_copy_final(mrg_ctx *ctx, uint8_t *h_dst, uint64_t cap);
+/* The k most frequent words (word count only): the first min(k, lines) lines of what mrg_job_final
+ * would produce now (so with the last group of every partition dropped unless
+ * MRG_FLAG_NO_COMPAT_DROP_LAST), ordered by count descending, then key bytes ascending; each line
+ * byte-identical to its final.txt line.  Selected on the device (a radix select over the counts: the
+ * keys are not sorted).  Callable whenever mrg_job_final is, any number of times, with any k; it
+ * leaves the job as it was.  *d_out stays valid until the next job call; *h_lines = lines written.
+ * Any out pointer may be NULL.  k = 0 or no lines: zero bytes, MRG_OK. */
+int mrg_job_topk(mrg_ctx *ctx, uint64_t k, const uint8_t **d_out, uint64_t *h_bytes, uint64_t *h_lines);
+int mrg_job_copy_topk(mrg_ctx *ctx, uint8_t *h_dst, uint64_t cap);
 
 /* ---- multi-GPU: one rank per GPU, the shuffle as an RCCL all-to-all over xGMI ----
  * The reference moves map output to the reduce workers through mr-{m}-{r}.txt files in a shared
@@ -224,6 +237,9 @@ int mrg_reduce_text(mrg_ctx *ctx, const uint8_t *const *h_files, const uint64_t 
  * coordinator.rs:137-176), the shuffle is mrg_job_shuffle, GPU g reduces and writes out_dir/mr-{r}.txt
  * for r % n_gpus == g (the reduce task ids, coordinator.rs:178-215).  With MRG_FLAG_FINAL_TXT also
  * out_dir/final.txt: each GPU sorts the lines it holds, the host merges the n_gpus sorted runs.
+ * With MRG_FLAG_TOP(k) (word count only: MRG_EINVAL for the indexer, before any work) also
+ * out_dir/top.txt: each GPU selects the k most frequent lines among the keys it owns
+ * (mrg_job_topk), the host merges the n_gpus runs by (count descending, key ascending) and keeps k.
  * Indexer document names are the file paths as given (the reference opens "data/gut-{m}.txt").
  * Files are read by several host threads per GPU through pinned staging, overlapped with the copies
  * to the device.  Every phase runs on all GPUs and is joined before the next, and the exchange agrees

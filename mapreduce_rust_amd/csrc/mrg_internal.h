@@ -459,6 +459,43 @@ void mrg_wide_launch_dense(const uint64_t *keys, const uint64_t *ocnt, const uin
                            const uint32_t *leaf_nd, const uint32_t *dense_off, uint32_t B1, uint32_t B1r, KeySet ks,
                            hipStream_t s);
 
+// ---- k_topk.hip: the K most frequent keys by a radix select, wc only
+// Keys are ranked by the 24-byte composite (~count, k0, k1), big-endian, smaller first: count
+// descending, then the 16-byte key prefix ascending.  The select finds, one byte ("digit") at a time,
+// the composite prefix below or at which the `want` best keys lie; its state lives on the device and
+// every pass reads it from there (no host round trip per pass).
+#define MRG_TOPK_DIGITS 24
+struct TopkState {
+    uint64_t pre[3];             // composite prefix found so far: its first `digit` bytes count
+    uint64_t want;               // rank still wanted among the keys tied on the prefix
+    uint64_t better;             // keys strictly below the prefix (all of them candidates)
+    uint64_t tied;               // keys equal to the prefix (candidates too: better + tied >= want)
+    unsigned long long maxcnt;   // largest count (the select starts at its first non-zero byte)
+    unsigned long long ncand;    // compaction cursor (mrg_topk_compact)
+    unsigned long long ndrop;    // candidates that are their partition's dropped key (mrg_topk_count_keys)
+    uint32_t digit;              // prefix bytes fixed so far = the next digit to select on
+    uint32_t done;               // the select has finished (the tied keys are exactly the wanted ones, or digit 24)
+    uint32_t passes, pad;        // histogram passes that streamed the keys
+    uint64_t parts[MRG_TOPK_DIGITS];  // keys still tied when digit d was histogrammed (0: pass not run)
+    unsigned long long hist[256];
+};
+// Enqueues the whole select for the `want` (< n) best of n keys; *st zeroed by the caller.
+void mrg_topk_select(KeySet ks, uint64_t n, uint64_t want, TopkState *st, hipStream_t s);
+// Candidates (keys whose composite, cut to st->digit bytes, is <= the prefix; all keys for a zeroed
+// state) as SortRecs {k0, k1, part 0, idx = key index}, at most cap of them, in no particular order.
+void mrg_topk_compact(KeySet ks, uint64_t n, TopkState *st, SortRec *out, uint64_t cap, hipStream_t s);
+// cand_last[p] (zeroed) = 1 + position of the byte-largest candidate of partition p in r (key order)
+void mrg_topk_cand_last(const SortRec *r, uint64_t m, KeySet ks, uint32_t R, uint32_t *cand_last, hipStream_t s);
+// exceeded[p] (zeroed) = 1 when some key of partition p is byte-greater than that candidate: one
+// streaming pass over all n keys (part, k0; k1 and heap bytes only on ties)
+void mrg_topk_exceed(KeySet ks, const uint8_t *heap, uint64_t n, const SortRec *r, uint32_t R,
+                     const uint32_t *cand_last, uint32_t *exceeded, hipStream_t s);
+// keys[j] = ~count of candidate j (all ones for a dropped one: it sorts last), vals[j] = j;
+// cand_last == null: nothing is dropped.  st->ndrop += dropped candidates.
+void mrg_topk_count_keys(const SortRec *r, uint64_t m, KeySet ks, uint32_t R, const uint32_t *cand_last,
+                         const uint32_t *exceeded, uint64_t *keys, uint32_t *vals, TopkState *st, hipStream_t s);
+void mrg_topk_gather(const SortRec *r, const uint32_t *vals, uint64_t m, SortRec *out, hipStream_t s);
+
 // ---- k_gen.hip
 int mrg_gen_zipf_impl(uint8_t *dst, uint64_t n, uint64_t seed, uint64_t file_index, uint32_t vocab, double s, uint32_t style,
                       hipStream_t st);

@@ -364,6 +364,11 @@ struct mrg_ctx {
     uint8_t *d_final = nullptr;     // final.txt (mrg_job_final)
     uint64_t final_cap = 0, final_bytes = 0;
     bool finalized = false;
+    uint8_t *d_top = nullptr;       // the K most frequent lines (mrg_job_topk)
+    uint64_t top_cap = 0, top_bytes = 0, top_lines = 0;
+    bool topped = false;
+    uint64_t top_info[8] = {};      // last mrg_job_topk: keys, candidates, select passes, dropped candidates
+    uint64_t top_pass_bytes[MRG_TOPK_DIGITS] = {};  // bytes each of its select passes read (0: pass not run)
     uint64_t extra_first = 0;       // text reduce: values of empty-key lines, folded into the first group
     mrg_stats st{};
 };
@@ -1192,6 +1197,7 @@ void job_begin(mrg_ctx *c, int app, uint32_t R, uint32_t flags) {
     c->part_off.assign(R + 1, 0);
     c->final_bytes = 0;
     c->finalized = false;
+    c->topped = false;
     c->st = mrg_stats{};
 }
 
@@ -2050,6 +2056,89 @@ void job_final(mrg_ctx *c) {
     c->finalized = true;
 }
 
+// The first k lines of final.txt re-ordered by (count descending, key bytes ascending), without
+// sorting the keys (k_topk.hip): at most R keys are dropped, so these lines lie
+// within the k + R best keys; a radix select finds those, and only they are sorted and formatted.
+// Reads the key set only: reduce, final and export afterwards give what they give without it.
+void job_topk(mrg_ctx *c, uint64_t k) {
+    need_job(c);
+    if (is_idx(c)) raise(MRG_EINVAL, "mrg_job_topk: word count only (the indexer has no counts to rank)");
+    if (!c->mapped) raise(MRG_EINVAL, "no keys: call mrg_job_map or mrg_job_import first");
+    wide_densify(c, 0);
+    Pool &p = c->pool;
+    hipStream_t s = c->stream;
+    const uint64_t n = c->keys.n;
+    const KeySet ks = c->keys.ks;
+    memset(c->top_info, 0, sizeof c->top_info);
+    memset(c->top_pass_bytes, 0, sizeof c->top_pass_bytes);
+    c->top_info[0] = n;
+    c->top_bytes = c->top_lines = 0;
+    c->topped = true;  // (an empty answer is an answer; a failure below clears it again)
+    if (k == 0 || n == 0) return;
+    c->topped = false;
+    check_sort_n(n, "top-k");
+    const uint64_t want = std::min<uint64_t>(n, k > n ? n : k + c->R);  // (k > n: no overflow of k + R)
+    TopkState *st = pget<TopkState>(p, 1);
+    HIPCHK(hipMemsetAsync(st, 0, sizeof(TopkState), s));
+    TopkState h{};
+    uint64_t m = n;  // candidates
+    if (want < n) {
+        mrg_topk_select(ks, n, want, st, s);
+        HIPCHK(hipMemcpyAsync(&h, st, offsetof(TopkState, hist), hipMemcpyDeviceToHost, s));
+        sync(c);  // the one host wait of the select: the candidate count sizes what follows
+        m = h.better + h.tied;
+        if (m < want || m > n) raise(MRG_EHIP, "top-k select: %llu candidates for %llu wanted of %llu keys",
+                                     (unsigned long long)m, (unsigned long long)want, (unsigned long long)n);
+        for (uint32_t d = 0; d < MRG_TOPK_DIGITS; ++d)
+            if (h.parts[d]) c->top_pass_bytes[d] = 8 * n + (d >= 8 ? 8 * h.parts[8] : 0) + (d >= 16 ? 8 * h.parts[16] : 0);
+    }
+    SortRec *a = pget<SortRec>(p, m), *b = pget<SortRec>(p, m);
+    void *stmp = p.get(mrg_sort_tmp_bytes(m));
+    mrg_topk_compact(ks, n, st, a, m, s);
+    // key order of the candidates (part unused), full-string order where long keys share a prefix
+    uint32_t n_big = 0;
+    SortRec *sorted = mrg_msd_sort(a, b, m, 0, sort_plan(c, 1), stmp, s, &n_big, (uint32_t *)&c->h_cnt[CNT_N]);
+    if (c->keys.any_long) mrg_launch_fix_runs(sorted, m, ks, c->keys.heap, s);
+    // drop-last: the byte-largest candidate of a partition is dropped iff no key of the partition exceeds it
+    uint32_t *cand_last = nullptr, *exceeded = nullptr;
+    if (compat_drop_last(c)) {
+        cand_last = pget<uint32_t>(p, 2ull * c->R);
+        exceeded = cand_last + c->R;
+        HIPCHK(hipMemsetAsync(cand_last, 0, 8ull * c->R, s));
+        mrg_topk_cand_last(sorted, m, ks, c->R, cand_last, s);
+        if (m < n) mrg_topk_exceed(ks, c->keys.heap, n, sorted, c->R, cand_last, exceeded, s);  // (m == n: none can)
+    }
+    // then a stable sort by ~count: count descending, key order kept among equal counts
+    uint64_t *ckeys = pget<uint64_t>(p, m), *kvtmp = pget<uint64_t>(p, 4 * m);
+    uint32_t *vals = pget<uint32_t>(p, m);
+    mrg_topk_count_keys(sorted, m, ks, c->R, cand_last, exceeded, ckeys, vals, st, s);
+    mrg_radix_sort_u64(ckeys, vals, kvtmp, m, stmp, s);
+    SortRec *top = sorted == a ? b : a;
+    mrg_topk_gather(sorted, vals, m, top, s);
+    HIPCHK(hipMemcpyAsync(&h, st, offsetof(TopkState, hist), hipMemcpyDeviceToHost, s));
+    sync(c);
+    const uint64_t lines = std::min<uint64_t>(k, m - std::min<uint64_t>(m, h.ndrop));
+    // the wc line writer over the first `lines` records, as one partition; not any_long: the records
+    // are no longer in key order, and their long-key runs are already in full-string order
+    FormatArgs f{};
+    f.recs = top;
+    f.n = lines;
+    f.ks = ks;
+    f.heap = c->keys.heap;
+    f.heap_bytes = c->keys.heap_bytes;
+    f.n_reduce = 1;
+    uint64_t po[2] = {0, 0};
+    mrg_format(f, p, &c->d_top, &c->top_cap, po, s);
+    HIPCHK(hipGetLastError());
+    p.put(st); p.put(a); p.put(b); p.put(stmp); p.put(cand_last); p.put(ckeys); p.put(kvtmp); p.put(vals);
+    c->top_bytes = po[1];
+    c->top_lines = lines;
+    c->topped = true;
+    c->top_info[1] = m;
+    c->top_info[2] = h.passes;
+    c->top_info[3] = h.ndrop;
+}
+
 void export_sizes(mrg_ctx *c, uint32_t n_owners, uint64_t *h_rec, uint64_t *h_heap) {
     need_job(c);
     if (!c->mapped) raise(MRG_EINVAL, "export before map");
@@ -2728,6 +2817,29 @@ int mrg_job_copy_final(mrg_ctx *c, uint8_t *h_dst, uint64_t cap) {
     });
 }
 
+int mrg_job_topk(mrg_ctx *c, uint64_t k, const uint8_t **d_out, uint64_t *h_bytes, uint64_t *h_lines) {
+    return guard([&] {
+        job_topk(c, k);
+        if (d_out) *d_out = c->d_top;
+        if (h_bytes) *h_bytes = c->top_bytes;
+        if (h_lines) *h_lines = c->top_lines;
+    });
+}
+
+int mrg_job_copy_topk(mrg_ctx *c, uint8_t *h_dst, uint64_t cap) {
+    return guard([&] {
+        need_job(c);
+        if (!c->topped) raise(MRG_EINVAL, "no top-k lines: call mrg_job_topk first");
+        if (cap < c->top_bytes) raise(MRG_EINVAL, "destination too small (%llu < %llu)", (unsigned long long)cap,
+                                      (unsigned long long)c->top_bytes);
+        if (c->top_bytes) {
+            if (!h_dst) raise(MRG_EINVAL, "null argument");
+            HIPCHK(hipMemcpyAsync(h_dst, c->d_top, c->top_bytes, hipMemcpyDeviceToHost, c->stream));
+        }
+        sync(c);
+    });
+}
+
 // ---- text intermediates
 int mrg_map_text(mrg_ctx *c, const uint8_t *h_bytes, size_t n, uint32_t n_reduce, uint8_t **h_out,
                  uint64_t *h_part_off) {
@@ -2992,6 +3104,55 @@ std::vector<uint8_t> merge_sorted_lines(const std::vector<std::pair<const uint8_
     return out;
 }
 
+// k-way merge of G runs of "key count" lines, each ordered by (count descending, key bytes ascending)
+// -- each GPU's mrg_job_topk lines -- keeping the first k lines.  The count is the digits after the
+// line's last space, compared as a decimal string (no leading zeros: longer is larger), so any number
+// of digits works.  A run may be empty or lack its final newline.
+std::vector<uint8_t> merge_top_lines(const std::vector<std::pair<const uint8_t *, uint64_t>> &runs, uint64_t k) {
+    struct Cur { const uint8_t *p, *e, *le, *sp; };  // le = end of the current line, sp = its last space (or le)
+    auto line_end = [](const uint8_t *p, const uint8_t *e) {
+        const uint8_t *q = (const uint8_t *)memchr(p, '\n', (size_t)(e - p));
+        return q ? q : e;
+    };
+    auto last_space = [](const uint8_t *p, const uint8_t *le) {
+        const uint8_t *q = (const uint8_t *)memrchr(p, ' ', (size_t)(le - p));
+        return q ? q : le;
+    };
+    // a before b
+    auto before = [](const Cur &a, const Cur &b) {
+        const size_t da = a.sp < a.le ? (size_t)(a.le - a.sp - 1) : 0, db = b.sp < b.le ? (size_t)(b.le - b.sp - 1) : 0;
+        if (da != db) return da > db;
+        const int cc = da ? memcmp(a.sp + 1, b.sp + 1, da) : 0;
+        if (cc) return cc > 0;
+        const size_t ka = (size_t)(a.sp - a.p), kb = (size_t)(b.sp - b.p);
+        const int cm = memcmp(a.p, b.p, std::min(ka, kb));
+        return cm < 0 || (cm == 0 && ka < kb);
+    };
+    std::vector<Cur> cur;
+    for (auto &r : runs) {
+        if (!r.second) continue;
+        const uint8_t *e = r.first + r.second, *le = line_end(r.first, e);
+        cur.push_back({r.first, e, le, last_space(r.first, le)});
+    }
+    std::vector<uint8_t> out;
+    for (uint64_t taken = 0; taken < k && !cur.empty(); ++taken) {
+        size_t best = 0;
+        for (size_t i = 1; i < cur.size(); ++i)
+            if (before(cur[i], cur[best])) best = i;
+        Cur &c = cur[best];
+        out.insert(out.end(), c.p, c.le);
+        out.push_back('\n');
+        c.p = c.le < c.e ? c.le + 1 : c.e;
+        if (c.p >= c.e) {
+            cur.erase(cur.begin() + (ptrdiff_t)best);
+        } else {
+            c.le = line_end(c.p, c.e);
+            c.sp = last_space(c.p, c.le);
+        }
+    }
+    return out;
+}
+
 // ---- input files -> device: worker.rs:65-77 reads each file whole (read_to_string).  Here the
 // files of a GPU are read in chunks by several host threads into pinned staging buffers (two per
 // thread), each chunk copied to the device buffer while the thread reads the next one, so disk /
@@ -3085,7 +3246,7 @@ struct RankState {
     mrg_comm *m = nullptr;
     uint8_t *d = nullptr;
     uint64_t in_bytes = 0;
-    std::vector<uint8_t> out, fin;
+    std::vector<uint8_t> out, fin, top;
 };
 
 // Runs fn on every rank, one host thread each, and returns when all have returned; the per-rank
@@ -3173,6 +3334,7 @@ void run_job(const char *const *files, size_t n_files, uint32_t R, int app, cons
     g_run = mrg_run_stats{};
     const int G = (int)devices.size();
     g_run.n_gpus = G;
+    const uint64_t top_k = flags >> 16;  // MRG_FLAG_TOP(k): also out_dir/top.txt
     std::vector<const char *> names(files, files + n_files);
     check_names(names.data(), (uint32_t)n_files);
     std::vector<RankState> rs(G);
@@ -3272,6 +3434,11 @@ void run_job(const char *const *files, size_t n_files, uint32_t R, int app, cons
             if (c->final_bytes)
                 HIPCHK(hipMemcpyAsync(r.fin.data(), c->d_final, c->final_bytes, hipMemcpyDeviceToHost, c->stream));
         }
+        if (top_k) {  // this GPU's most frequent lines among the keys it owns
+            job_topk(c, top_k);
+            r.top.resize(c->top_bytes);
+            if (c->top_bytes) HIPCHK(hipMemcpyAsync(r.top.data(), c->d_top, c->top_bytes, hipMemcpyDeviceToHost, c->stream));
+        }
         sync(c);
     }, rc, msg);
     raise_first(rc, msg, rs);
@@ -3296,6 +3463,15 @@ void run_job(const char *const *files, size_t n_files, uint32_t R, int app, cons
             write_file(std::string(out_dir) + "/final.txt", all.data(), all.size());
         }
     }
+    if (top_k) {  // exact: after the shuffle every key, and every partition's dropped key, is on one GPU
+        if (G == 1) write_file(std::string(out_dir) + "/top.txt", rs[0].top.data(), rs[0].top.size());
+        else {
+            std::vector<std::pair<const uint8_t *, uint64_t>> runs;
+            for (auto &r : rs) runs.push_back({r.top.data(), r.top.size()});
+            const std::vector<uint8_t> all = merge_top_lines(runs, top_k);
+            write_file(std::string(out_dir) + "/top.txt", all.data(), all.size());
+        }
+    }
     g_run.ms_write = ms_since(t0);
     g_run.ms_total = ms_since(t_all);
 }
@@ -3309,6 +3485,7 @@ int mrg_run_job(const char *const *files, size_t n_files, uint32_t n_reduce, int
     return guard([&] {
         if ((n_files && !files) || !out_dir) raise(MRG_EINVAL, "null argument");
         if (n_reduce == 0) raise(MRG_EINVAL, "n_reduce must be > 0");
+        if ((flags >> 16) && app == MRG_APP_INDEXER) raise(MRG_EINVAL, "MRG_FLAG_TOP: word count only");
         int ndev = 0;
         HIPCHK(hipGetDeviceCount(&ndev));
         if (n_gpus < 1 || n_gpus > ndev) raise(MRG_EINVAL, "n_gpus %d: %d devices visible", n_gpus, ndev);
@@ -3339,6 +3516,35 @@ int mrg_test_merge_sorted_lines(const uint8_t *const *runs, const uint64_t *size
         if (!m.empty()) memcpy(o, m.data(), m.size());
         *out = o;
         *out_len = m.size();
+    });
+}
+
+// Test entry (not in include/mrgpu.h): the merge of per-GPU top-k line runs (count descending, key
+// ascending) that builds a multi-GPU top.txt, callable without a GPU.  *out: free with mrg_free.
+int mrg_test_merge_top_lines(const uint8_t *const *runs, const uint64_t *sizes, size_t n_runs, uint64_t k, uint8_t **out,
+                             uint64_t *out_len) {
+    return guard([&] {
+        if (!out || !out_len || (n_runs && (!runs || !sizes))) raise(MRG_EINVAL, "null argument");
+        std::vector<std::pair<const uint8_t *, uint64_t>> v;
+        for (size_t i = 0; i < n_runs; ++i) v.push_back({runs[i], sizes[i]});
+        const std::vector<uint8_t> m = merge_top_lines(v, k);
+        uint8_t *o = (uint8_t *)malloc(m.size() + 1);
+        if (!o) raise(MRG_ENOMEM, "host allocation failed");
+        if (!m.empty()) memcpy(o, m.data(), m.size());
+        *out = o;
+        *out_len = m.size();
+    });
+}
+
+// Diagnostics of the last mrg_job_topk (not in include/mrgpu.h; tools/time_topk.py): h_info[0..4) =
+// distinct keys, candidates, select passes run, candidates dropped as their partition's last key;
+// h_pass_bytes[24] = bytes each select pass read (0: pass not run).  Either may be NULL.
+int mrg_test_topk_info(mrg_ctx *c, uint64_t *h_info, uint64_t *h_pass_bytes) {
+    return guard([&] {
+        need_job(c);
+        if (!c->topped) raise(MRG_EINVAL, "no top-k lines: call mrg_job_topk first");
+        if (h_info) memcpy(h_info, c->top_info, 4 * sizeof(uint64_t));
+        if (h_pass_bytes) memcpy(h_pass_bytes, c->top_pass_bytes, sizeof c->top_pass_bytes);
     });
 }
 

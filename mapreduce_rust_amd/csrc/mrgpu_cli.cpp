@@ -5,8 +5,9 @@
 // (one host thread each): GPU g maps files m % N == g and reduces partitions r % N == g, and the
 // map -> reduce hand-off is an RCCL all-to-all over xGMI (mrg_job_shuffle).
 // --final also writes final.txt, the output of src/run.sh:16-20 (cat mr-* | sort, LC_ALL=C), built on the GPUs.
+// --top K also writes top.txt, the K (1..65535) most frequent lines of final.txt (count descending, then key).
 // --times prints the wall-clock phases of the job (mrg_run_get_stats) as one JSON line on stderr.
-//   usage: mrgpu <map_n> <reduce_n> [--gpus N] [--app wc|indexer] [--no-compat-drop-last] [--final] [--times]
+//   usage: mrgpu <map_n> <reduce_n> [--gpus N] [--app wc|indexer] [--no-compat-drop-last] [--final] [--top K] [--times]
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -19,7 +20,7 @@
 int main(int argc, char **argv) {
     if (argc < 3) {
         fprintf(stderr, "Usage: mrgpu <input files number> <reduce task number> [--gpus N] [--app wc|indexer] "
-                        "[--no-compat-drop-last] [--final] [--times]\n");
+                        "[--no-compat-drop-last] [--final] [--top K] [--times]\n");
         return 2;
     }
     const int map_n = atoi(argv[1]);
@@ -37,6 +38,13 @@ int main(int argc, char **argv) {
             flags |= MRG_FLAG_NO_COMPAT_DROP_LAST;
         } else if (!strcmp(argv[i], "--final")) {
             flags |= MRG_FLAG_FINAL_TXT;
+        } else if (!strcmp(argv[i], "--top") && i + 1 < argc) {
+            const long k = atol(argv[++i]);
+            if (k < 1 || k > 65535) {
+                fprintf(stderr, "mrgpu: --top takes 1..65535\n");
+                return 2;
+            }
+            flags |= MRG_FLAG_TOP(k);
         } else if (!strcmp(argv[i], "--times")) {
             times = true;
         } else {

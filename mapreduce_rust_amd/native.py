@@ -26,6 +26,11 @@ def debug_hash_bits(n):
     return (n & 0xFF) << 8
 
 
+def flag_top(k):
+    """MRG_FLAG_TOP(k): run_job also writes out_dir/top.txt, the k (1..65535) most frequent lines."""
+    return (k & 0xFFFF) << 16
+
+
 def kernel_source_sha():
     """sha256 over the sources libmrgpu.so is built from (kernels, headers, host layer): keys the
     committed PMC traffic figure (profiles/map_traffic.json) to the code it was measured on."""
@@ -100,6 +105,8 @@ _SIGS = {
     "mrg_job_copy_output": (C.c_int, [_vp, _vp, C.c_uint64]),
     "mrg_job_final": (C.c_int, [_vp, C.POINTER(_vp), _u64p]),
     "mrg_job_copy_final": (C.c_int, [_vp, _vp, C.c_uint64]),
+    "mrg_job_topk": (C.c_int, [_vp, C.c_uint64, C.POINTER(_vp), _u64p, _u64p]),
+    "mrg_job_copy_topk": (C.c_int, [_vp, _vp, C.c_uint64]),
     "mrg_map": (C.c_int, [_vp, C.c_int, C.c_char_p, C.c_size_t, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32,
                           C.POINTER(_vp)]),
     "mrg_parts_get": (C.c_int, [_vp, C.c_uint32, C.POINTER(_vp), _u64p, C.POINTER(_vp), _u64p]),
@@ -309,6 +316,27 @@ class Context:
         _check(load().mrg_job_copy_final(self.h, buf, n.value))
         return buf.raw[:n.value]
 
+    def topk(self, k):
+        """The k most frequent lines of final.txt (count descending, then key bytes), selected on the
+        device without sorting the keys (mrg_job_topk); wc only."""
+        d = _vp()
+        n, lines = C.c_uint64(), C.c_uint64()
+        _check(load().mrg_job_topk(self.h, k, C.byref(d), C.byref(n), C.byref(lines)))
+        buf = C.create_string_buffer(max(n.value, 1))
+        _check(load().mrg_job_copy_topk(self.h, buf, n.value))
+        return buf.raw[:n.value]
+
+    def topk_info(self):
+        """Diagnostics of the last topk(): distinct keys, candidates the select kept, select passes
+        run, candidates dropped as their partition's last key, and the bytes each pass read."""
+        f = load().mrg_test_topk_info
+        f.restype = C.c_int
+        f.argtypes = [_vp, _u64p, _u64p]
+        info, pb = (C.c_uint64 * 4)(), (C.c_uint64 * 24)()
+        _check(f(self.h, info, pb))
+        return {"n": info[0], "candidates": info[1], "passes": info[2], "dropped": info[3],
+                "pass_bytes": [b for b in pb if b]}
+
     # ---- plugin surface (host buffers)
     def map_task(self, app, data, doc, doc_id, n_reduce, flags=0):
         h = _vp()
@@ -377,6 +405,21 @@ def merge_sorted_lines(runs):
     arr = (C.c_char_p * max(len(runs), 1))(*runs)
     out, n = _vp(), C.c_uint64()
     _check(f(arr, _u64arr([len(r) for r in runs]), len(runs), C.byref(out), C.byref(n)))
+    data = C.string_at(out, n.value) if n.value else b""
+    L.mrg_free(out)
+    return data
+
+
+def merge_top_lines(runs, k):
+    """The host merge of per-GPU top-k runs (count descending, key ascending), first k lines (test
+    entry, no GPU needed)."""
+    L = load()
+    f = L.mrg_test_merge_top_lines
+    f.restype = C.c_int
+    f.argtypes = [C.POINTER(C.c_char_p), _u64p, C.c_size_t, C.c_uint64, C.POINTER(_vp), _u64p]
+    arr = (C.c_char_p * max(len(runs), 1))(*runs)
+    out, n = _vp(), C.c_uint64()
+    _check(f(arr, _u64arr([len(r) for r in runs]), len(runs), k, C.byref(out), C.byref(n)))
     data = C.string_at(out, n.value) if n.value else b""
     L.mrg_free(out)
     return data

@@ -25,6 +25,10 @@ pub const MRG_FLAG_FINAL_TXT: u32 = 0x2;
 pub const fn mrg_flag_debug_hash_bits(n: u32) -> u32 {
     (n & 0xFF) << 8
 }
+/// mrg_run_job only: also write out_dir/top.txt, the k (1..65535) most frequent lines of final.txt.
+pub const fn mrg_flag_top(k: u32) -> u32 {
+    (k & 0xFFFF) << 16
+}
 pub const MRG_XREC_BYTES: usize = 24;
 pub const MRG_ABI_VERSION: u32 = 6;
 pub const MRG_COMM_ID_BYTES: usize = 128;
@@ -112,6 +116,8 @@ extern "C" {
     pub fn mrg_job_copy_output(ctx: *mut mrg_ctx, h_dst: *mut u8, cap: u64) -> c_int;
     pub fn mrg_job_final(ctx: *mut mrg_ctx, d_out: *mut *const u8, h_bytes: *mut u64) -> c_int;
     pub fn mrg_job_copy_final(ctx: *mut mrg_ctx, h_dst: *mut u8, cap: u64) -> c_int;
+    pub fn mrg_job_topk(ctx: *mut mrg_ctx, k: u64, d_out: *mut *const u8, h_bytes: *mut u64, h_lines: *mut u64) -> c_int;
+    pub fn mrg_job_copy_topk(ctx: *mut mrg_ctx, h_dst: *mut u8, cap: u64) -> c_int;
 
     pub fn mrg_comm_get_id(id: *mut u8) -> c_int;
     pub fn mrg_comm_init(ctx: *mut mrg_ctx, id: *const u8, n_ranks: c_int, rank: c_int,
