@@ -52,6 +52,7 @@ extern "C" {
 #define MRG_FLAG_NO_COMPAT_DROP_LAST 0x1u  /* default (flag clear): reproduce worker.rs:169-184, which never
                                               writes the last group of a partition.  Set: write it. */
 #define MRG_FLAG_FINAL_TXT 0x2u  /* mrg_run_job: also write out_dir/final.txt (src/run.sh:16-20) */
+#define MRG_FLAG_STREAM 0x4u   /* mrg_run_job only: map each GPU's files in batches while the next batch is read */
 /* bits 8..15: truncate every internal (non-partition) hash to this many bits; 0 = full 64 bits.
    A test knob that forces hash collisions so the full-string tie-break paths are exercised. */
 #define MRG_FLAG_DEBUG_HASH_BITS(n) (((uint32_t)(n) & 0xFFu) << 8)
@@ -102,14 +103,19 @@ typedef struct {
     uint32_t agg_path;         /* aggregation taken: 0 none, 1 bucket tables, 2 wide (sort-based) */
     uint32_t map_kind;         /* map kernel: 0 LDS combine + hash-bucketed tail records, 1 the wide map
                                   (near-unique keys: every key straight to its sort bucket) */
-    uint32_t reserved;
+    uint32_t map_batches;      /* successful mrg_job_map_add calls of the job (0 after mrg_job_map / mrg_job_import);
+                                  was `reserved`.  After mrg_job_map_add, input_bytes, tokens and long_tokens are
+                                  totals over the job's batches, distinct_keys is the job's exact count so far,
+                                  and the ms_*, launch and path fields describe the last batch */
 } mrg_stats;
 
 /* ABI history: 1 = round-1 layout; 2 = mrg_run_job's last argument is n_gpus (was a device index);
  * 3 = 24-byte exchange records (were 40), mrg_run_get_stats; 4 = mrg_stats gains nonascii_tiles,
  * tail_records_16, spec_agg, agg_path; 5 = mrg_stats gains map_kind, mrg_comm_count, mrg_pool_stats;
  * 6 = mrg_pool_alloc_stats.  mrg_version() names the ABI it implements.
- * (6, additive): mrg_job_topk, mrg_job_copy_topk, MRG_FLAG_TOP */
+ * (6, additive): mrg_job_topk, mrg_job_copy_topk, MRG_FLAG_TOP
+ * (6, additive): mrg_job_map_add, MRG_FLAG_STREAM, mrg_run_get_stream_stats; mrg_stats.reserved is now
+ * map_batches (same size and offset) */
 #define MRG_ABI_VERSION 6
 
 const char *mrg_last_error(void);
@@ -139,6 +145,18 @@ int mrg_job_set_input(mrg_ctx *ctx, const uint8_t *d_bytes, const uint64_t *h_do
                       const uint32_t *h_doc_ids);
 /* Map: tokenize (wc.rs:6-13) + combine + SipHash partition (worker.rs:111-115).  Validates UTF-8. */
 int mrg_job_map(mrg_ctx *ctx);
+/* Map the input set by mrg_job_set_input and ADD its tokens to the job's keys.
+ * mrg_job_map replaces the job's keys; this call adds to them.
+ * After mrg_job_begin the caller may repeat { mrg_job_set_input, mrg_job_map_add } any number of times;
+ * every consumer (export, shuffle, reduce, final, topk) then behaves as if one mrg_job_map had run over
+ * all the batches' documents together, byte for byte.  Consumers may be called between batches and more
+ * batches may follow.  A batch holds whole documents (a token across a cut would become two); indexer
+ * batches pass global ids in h_doc_ids, and mrg_job_set_doc_names is given once with the full table.
+ * Keys the job already holds (mrg_job_map, mrg_job_import) are added to; mrg_job_map and mrg_job_import
+ * still replace everything.  All-or-nothing: when the map fails (MRG_EUTF8, MRG_ENOMEM) the job keeps
+ * exactly the keys it had and stays usable.  The device no longer reads the batch's buffer once this
+ * call returns: the caller may overwrite or free it then (mrg_job_map's contract is unchanged). */
+int mrg_job_map_add(mrg_ctx *ctx);
 /* Shuffle boundary.  Owner of partition r is r % n_owners.  Sizes first (host arrays of n_owners),
  * then pack into caller device buffers ordered by owner (records, then heap bytes). */
 int mrg_job_export_sizes(mrg_ctx *ctx, uint32_t n_owners, uint64_t *h_rec_counts, uint64_t *h_heap_bytes);
@@ -244,6 +262,11 @@ int mrg_reduce_text(mrg_ctx *ctx, const uint8_t *const *h_files, const uint64_t 
  * Files are read by several host threads per GPU through pinned staging, overlapped with the copies
  * to the device.  Every phase runs on all GPUs and is joined before the next, and the exchange agrees
  * on every rank's status before each transfer: a failure on any GPU fails the call, never hangs it.
+ * With MRG_FLAG_STREAM each GPU's files (in order) are cut into batches -- maximal runs of consecutive
+ * files of at most MRG_STREAM_BATCH_BYTES (env; default 4 GiB) together, a larger file alone -- and
+ * batch i is mapped (mrg_job_map_add) while a helper thread reads batch i + 1 into the other of two
+ * device buffers: the input footprint is two batches instead of the whole input.  The output files are
+ * byte-identical with and without the flag.
  * (ABI 2 changed the last argument from a device index to n_gpus.) */
 int mrg_run_job(const char *const *files, size_t n_files, uint32_t n_reduce, int app, const char *out_dir,
                 uint32_t flags, int n_gpus);
@@ -252,8 +275,10 @@ int mrg_run_job(const char *const *files, size_t n_files, uint32_t n_reduce, int
 typedef struct {
     double ms_total;        /* the whole call */
     double ms_open;         /* contexts + communicators */
-    double ms_read;         /* input files -> device (read + H2D, overlapped; slowest GPU) */
-    double ms_map;          /* map + aggregation after the read (slowest GPU) */
+    double ms_read;         /* input files -> device (read + H2D, overlapped; slowest GPU); MRG_FLAG_STREAM:
+                               the time the GPU's thread waited for reads */
+    double ms_map;          /* map + aggregation after the read (slowest GPU); MRG_FLAG_STREAM: the phase's
+                               wall time minus ms_read */
     double ms_shuffle;      /* the exchange (0 without a communicator) */
     double ms_reduce;       /* sort + format + D2H of the output (+ final.txt) */
     double ms_write;        /* mr-{r}.txt (+ final.txt) files */
@@ -266,6 +291,10 @@ typedef struct {
     double ms_aggregate_kernel; /* of ms_map: the aggregation after it (HIP events, slowest GPU; ABI 6) */
 } mrg_run_stats;
 int mrg_run_get_stats(mrg_run_stats *out);
+/* The last mrg_run_job of this thread: batches mapped on the GPU that mapped the most (0 without
+ * MRG_FLAG_STREAM) and the largest GPU's bytes of device input buffers (unstreamed: its whole input).
+ * Either may be NULL. */
+int mrg_run_get_stream_stats(uint32_t *batches, uint64_t *peak_input_bytes);
 
 /* Free host memory returned by the library (mrg_reduce / mrg_map_text / mrg_reduce_text output). */
 void mrg_free(void *p);

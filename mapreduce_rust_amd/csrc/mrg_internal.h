@@ -496,6 +496,29 @@ void mrg_topk_count_keys(const SortRec *r, uint64_t m, KeySet ks, uint32_t R, co
                          const uint32_t *exceeded, uint64_t *keys, uint32_t *vals, TopkState *st, hipStream_t s);
 void mrg_topk_gather(const SortRec *r, const uint32_t *vals, uint64_t m, SortRec *out, hipStream_t s);
 
+// ---- k_acc.hip: the accumulator of mrg_job_map_add
+// Persistent open-addressing table of the job's short keys (<= 16 bytes), SoA; empty slot: k0 =
+// MRG_EMPTY_K0, k1 = MRG_EMPTY_K1, doc = MRG_EMPTY_DOC, cnt = 0.  The host keeps keys <= cap / 2.
+struct AccTable {
+    uint64_t *k0, *k1, *cnt;
+    uint32_t *doc, *part;
+    uint64_t cap;                // power of two
+    uint32_t hash_bits;          // 0 = full; else the slot comes from the truncated hash (collision test knob)
+};
+void mrg_acc_launch_clear(const AccTable &t, hipStream_t s);
+// insert-or-add the short keys of ks[0, n) (distinct among themselves, partition attached); *created +=
+// keys that were new to the table
+void mrg_acc_launch_fold(const AccTable &t, KeySet ks, uint64_t n, bool indexer, unsigned long long *created,
+                         hipStream_t s);
+void mrg_acc_launch_rehash(const AccTable &from, const AccTable &to, bool indexer, hipStream_t s);
+// the full slots as a dense KeySet out[*counter ...), at most out_cap keys
+void mrg_acc_launch_emit(const AccTable &t, bool indexer, KeySet out, uint64_t out_cap, unsigned long long *counter,
+                         hipStream_t s);
+// the long keys of ks[0, n) as long items [first + j), j counted in *counter (zeroed), over a heap in
+// which ks's heap starts at heap_base; items at or beyond cap are not written
+void mrg_acc_launch_long(KeySet ks, uint64_t n, uint64_t heap_base, uint64_t first, uint64_t cap, uint64_t *start,
+                         uint32_t *rawlen, uint32_t *doc, uint64_t *cnt, unsigned long long *counter, hipStream_t s);
+
 // ---- k_gen.hip
 int mrg_gen_zipf_impl(uint8_t *dst, uint64_t n, uint64_t seed, uint64_t file_index, uint32_t vocab, double s, uint32_t style,
                       hipStream_t st);

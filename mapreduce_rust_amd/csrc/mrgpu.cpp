@@ -311,6 +311,21 @@ struct WideRes {
     }
 };
 
+// The accumulator of mrg_job_map_add (k_acc.hip): the job's keys over all its
+// batches.  Short keys live in a persistent open-addressing table, long keys (rare) beside it as rows
+// of a KeysBuf with their heap; c->keys is then only a view, emitted on demand for the consumers.
+struct Acc {
+    bool on = false;      // the job's keys live here
+    bool dirty = false;   // c->keys does not show them (a fold, or a failed batch, since the last emit)
+    bool seeded = false;  // started from keys the job already held (mrg_job_map / mrg_job_import)
+    AccTable T{};
+    uint64_t n = 0;       // short keys in the table (exact: the fold counts the slots it claims)
+    KeysBuf lng;          // long keys: dense rows (k0, k1 = prefix, cnt, hoff, doc, len, part) + heap
+    uint64_t in_bytes = 0, tokens = 0, long_tokens = 0;  // totals over the batches (mrg_stats)
+    uint32_t batches = 0, rehashes = 0;
+    double ms_fold = 0.0;  // last batch, HIP events (mrg_set_timing): end of the aggregation .. end of the fold
+};
+
 }  // namespace
 
 struct mrg_ctx {
@@ -353,6 +368,8 @@ struct mrg_ctx {
     std::vector<std::string> names;
     KeysBuf keys;
     WideRes wide;
+    Acc acc;
+    bool keyed = false;   // keys / wide hold the complete result of a map or an import
     bool mapped = false;
     uint32_t n_owners = 0;
     std::vector<uint64_t> exp_rec, exp_heap;
@@ -488,6 +505,25 @@ void keys_release(mrg_ctx *c) {
     p.put(k.ks.doc); p.put(k.ks.len); p.put(k.ks.part);
     p.put(k.heap);
     k = KeysBuf{};
+}
+
+void keysbuf_release(Pool &p, KeysBuf &k) {
+    p.put(k.ks.k0); p.put(k.ks.k1); p.put(k.ks.cnt); p.put(k.ks.hoff);
+    p.put(k.ks.doc); p.put(k.ks.len); p.put(k.ks.part);
+    p.put(k.heap);
+    k = KeysBuf{};
+}
+
+void acc_table_put(Pool &p, AccTable &T) {
+    p.put(T.k0); p.put(T.k1); p.put(T.cnt); p.put(T.doc); p.put(T.part);
+    T = AccTable{};
+}
+
+// mrg_job_begin, mrg_job_map, mrg_job_import, mrg_close: the accumulator's blocks back to the pool
+void acc_release(mrg_ctx *c) {
+    acc_table_put(c->pool, c->acc.T);
+    keysbuf_release(c->pool, c->acc.lng);
+    c->acc = Acc{};
 }
 
 void keys_reserve(mrg_ctx *c, uint64_t cap) {
@@ -1183,6 +1219,8 @@ void job_begin(mrg_ctx *c, int app, uint32_t R, uint32_t flags) {
     c->pend_lo = 0;
     keys_release(c);
     c->wide.release(c->pool);
+    acc_release(c);
+    c->keyed = false;
     c->job = true;
     c->app = app;
     c->R = R;
@@ -1460,8 +1498,9 @@ void job_map_wide(mrg_ctx *c, WideMapPlan &wp, uint64_t *d_doc_off, uint64_t *d_
         p.put(wp.spl1); p.put(wp.ix1);
         uint32_t d = 0;
         while (d + 1 < nd && c->doc_off[d + 1] <= errpos) ++d;
-        raise(MRG_EUTF8, "stream did not contain valid UTF-8: document %u (id %u), byte offset %llu", d, ids[d],
-              (unsigned long long)(errpos - c->doc_off[d]));
+        const char *nm = ids[d] < c->names.size() ? c->names[ids[d]].c_str() : "";
+        raise(MRG_EUTF8, "stream did not contain valid UTF-8: document %u (id %u%s%s), byte offset %llu", d, ids[d],
+              *nm ? ", " : "", nm, (unsigned long long)(errpos - c->doc_off[d]));
     }
     ev_rec(c, 2);
     LongItems li{};
@@ -1508,14 +1547,14 @@ void job_map_wide(mrg_ctx *c, WideMapPlan &wp, uint64_t *d_doc_off, uint64_t *d_
     // the hint holds while the input stays near-unique
     c->wide_hint = 2 * c->st.distinct_keys > c->st.tokens;
     c->wc_sized = true;
-    c->mapped = true;
+    c->mapped = c->keyed = true;
 }
 
 void job_map(mrg_ctx *c) {
     need_job(c);
     if (c->doc_off.empty()) raise(MRG_EINVAL, "no input: call mrg_job_set_input first");
     c->wide.release(c->pool);  // a second map of the same job replaces the first one's keys
-    c->mapped = c->reduced = false;
+    c->mapped = c->reduced = c->keyed = false;
     c->st.spec_agg = c->st.agg_path = c->st.map_kind = 0;
     Pool &p = c->pool;
     hipStream_t s = c->stream;
@@ -1802,8 +1841,9 @@ void job_map(mrg_ctx *c) {
         release_map();
         uint32_t d = 0;
         while (d + 1 < nd && c->doc_off[d + 1] <= errpos) ++d;
-        raise(MRG_EUTF8, "stream did not contain valid UTF-8: document %u (id %u), byte offset %llu", d, ids[d],
-              (unsigned long long)(errpos - c->doc_off[d]));
+        const char *nm = ids[d] < c->names.size() ? c->names[ids[d]].c_str() : "";
+        raise(MRG_EUTF8, "stream did not contain valid UTF-8: document %u (id %u%s%s), byte offset %llu", d, ids[d],
+              *nm ? ", " : "", nm, (unsigned long long)(errpos - c->doc_off[d]));
     }
     if (!spec.live) ev_rec(c, 2);
     LongItems li{};
@@ -1836,7 +1876,246 @@ void job_map(mrg_ctx *c) {
     release_map();
     c->st.ms_aggregate = ev_ms(c, 2, 3);
     if (!idx && total >= (64ull << 20)) c->wc_sized = true;
+    c->mapped = c->keyed = true;
+}
+
+// ---- the accumulator of mrg_job_map_add (k_acc.hip)
+
+AccTable acc_table_get(mrg_ctx *c, uint64_t cap) {
+    Pool &p = c->pool;
+    AccTable T{};
+    try {
+        T.k0 = pget<uint64_t>(p, cap);
+        T.k1 = pget<uint64_t>(p, cap);
+        T.cnt = pget<uint64_t>(p, cap);
+        T.doc = pget<uint32_t>(p, cap);
+        T.part = pget<uint32_t>(p, cap);
+    } catch (...) {
+        acc_table_put(p, T);
+        throw;
+    }
+    T.cap = cap;
+    T.hash_bits = hash_bits(c);
+    mrg_acc_launch_clear(T, c->stream);
+    return T;
+}
+
+// Room for `more` further short keys at a load of at most 1/2, so a fold can never fill the table: the
+// host knows the table's key count and the batch's.  Growth re-inserts every key into a table of twice
+// the size or more (the only pass over the table beside the emit).  MRG_TEST_ACC_CAP: the first
+// table's slots (rounded up to a power of two >= 1024), so that growth runs on small inputs.
+void acc_reserve(mrg_ctx *c, uint64_t more) {
+    Acc &A = c->acc;
+    const uint64_t need = pow2_at_least(2 * (A.n + more));
+    if (!A.T.cap) {
+        const uint64_t t = env_u64("MRG_TEST_ACC_CAP", 0);
+        A.T = acc_table_get(c, t ? pow2_at_least(t) : need);
+    }
+    if (A.T.cap >= need) return;
+    AccTable N = acc_table_get(c, std::max<uint64_t>(need, 2 * A.T.cap));
+    mrg_acc_launch_rehash(A.T, N, is_idx(c), c->stream);
+    HIPCHK(hipGetLastError());
+    acc_table_put(c->pool, A.T);  // (the pool is stream-ordered: reused only behind the rehash)
+    A.T = N;
+    ++A.rehashes;
+    if (getenv("MRG_DEBUG"))
+        fprintf(stderr, "[mrgpu] accumulator: %llu keys rehashed into %llu slots\n", (unsigned long long)A.n,
+                (unsigned long long)N.cap);
+}
+
+// Fold a dense key set (distinct keys with their partitions; long keys on b.heap) into the accumulator
+// and give b's blocks back.  Short keys: one insert-or-add each (k_acc_fold).  Long keys: regrouped
+// with the accumulated ones by the existing long-key path, over one concatenated heap -- O(all long
+// keys) per batch; they are rare.  Everything that can fail runs before the table is touched, and the
+// new long rows replace the old ones only at the end: a failing fold leaves the accumulator as it was.
+void acc_fold(mrg_ctx *c, KeysBuf &b) {
+    Acc &A = c->acc;
+    Pool &p = c->pool;
+    hipStream_t s = c->stream;
+    const bool idx = is_idx(c);
+    struct Tmp {  // released on every path
+        Pool &p; KeysBuf &b;
+        unsigned long long *d_n = nullptr;
+        uint64_t *start = nullptr, *cnt = nullptr;
+        uint32_t *rawlen = nullptr, *doc = nullptr;
+        uint8_t *heap = nullptr;
+        ~Tmp() {
+            p.put(d_n); p.put(start); p.put(cnt); p.put(rawlen); p.put(doc); p.put(heap);
+            keysbuf_release(p, b);
+        }
+    } t{p, b};
+    A.dirty = true;  // (also when nothing is added: the view is rebuilt from the accumulator)
+    if (!b.n) return;
+    acc_reserve(c, b.n);
+    t.d_n = pget<unsigned long long>(p, 2);  // [0] keys new to the table, [1] the batch's long keys
+    HIPCHK(hipMemsetAsync(t.d_n, 0, 16, s));
+    bool relong = false;
+    if (b.any_long) {
+        const uint64_t cap = A.lng.n + b.n;
+        t.start = pget<uint64_t>(p, cap);
+        t.cnt = pget<uint64_t>(p, cap);
+        t.rawlen = pget<uint32_t>(p, cap);
+        t.doc = pget<uint32_t>(p, cap);
+        t.heap = pget<uint8_t>(p, A.lng.heap_bytes + b.heap_bytes + 16);
+        if (A.lng.n) {  // the accumulated rows first, their heap in front
+            HIPCHK(hipMemcpyAsync(t.start, A.lng.ks.hoff, 8 * A.lng.n, hipMemcpyDeviceToDevice, s));
+            HIPCHK(hipMemcpyAsync(t.cnt, A.lng.ks.cnt, 8 * A.lng.n, hipMemcpyDeviceToDevice, s));
+            HIPCHK(hipMemcpyAsync(t.rawlen, A.lng.ks.len, 4 * A.lng.n, hipMemcpyDeviceToDevice, s));
+            HIPCHK(hipMemcpyAsync(t.doc, A.lng.ks.doc, 4 * A.lng.n, hipMemcpyDeviceToDevice, s));
+            if (A.lng.heap_bytes)
+                HIPCHK(hipMemcpyAsync(t.heap, A.lng.heap, A.lng.heap_bytes, hipMemcpyDeviceToDevice, s));
+        }
+        if (b.heap_bytes)
+            HIPCHK(hipMemcpyAsync(t.heap + A.lng.heap_bytes, b.heap, b.heap_bytes, hipMemcpyDeviceToDevice, s));
+        mrg_acc_launch_long(b.ks, b.n, A.lng.heap_bytes, A.lng.n, cap, t.start, t.rawlen, t.doc, t.cnt, &t.d_n[1], s);
+        HIPCHK(hipGetLastError());
+        uint64_t nl = 0;
+        HIPCHK(hipMemcpyAsync(&nl, &t.d_n[1], 8, hipMemcpyDeviceToHost, s));
+        sync(c);
+        if (nl > b.n) raise(MRG_EHIP, "internal: accumulator long-key count");
+        if (nl) {
+            LongItems li{};
+            li.base = t.heap;
+            li.start = t.start; li.rawlen = t.rawlen; li.doc = t.doc; li.cnt = t.cnt;
+            li.n = A.lng.n + nl;
+            li.verbatim = 1;  // both heaps hold exact key bytes
+            keys_reserve(c, li.n + 1);  // (c->keys is free here: the caller moved the batch out of it)
+            HIPCHK(hipMemsetAsync(&c->d_cnt[CNT_KEYS], 0, sizeof(unsigned long long), s));
+            try {
+                long_aggregate(c, li);
+                read_counters(c);
+                c->keys.n = c->h_cnt[CNT_KEYS];
+                if (c->keys.n > li.n) raise(MRG_EHIP, "internal: accumulator long-key set overflow");
+                mrg_launch_partition(c->keys.ks, c->keys.heap, c->keys.n, c->R, s);
+                HIPCHK(hipGetLastError());
+            } catch (...) {
+                keys_release(c);
+                throw;
+            }
+            relong = true;
+        }
+    }
+    mrg_acc_launch_fold(A.T, b.ks, b.n, idx, &t.d_n[0], s);
+    HIPCHK(hipGetLastError());
+    uint64_t made = 0;
+    HIPCHK(hipMemcpyAsync(&made, &t.d_n[0], 8, hipMemcpyDeviceToHost, s));
+    sync(c);
+    A.n += made;
+    if (relong) {
+        keysbuf_release(p, A.lng);
+        A.lng = c->keys;
+        c->keys = KeysBuf{};
+    }
+    A.dirty = true;
+}
+
+// The accumulator as the job's dense KeySet (unsorted, as after an import), for the consumers: at the
+// first consumer call after a fold.  The table stays, so further batches can follow.
+void acc_emit(mrg_ctx *c) {
+    Acc &A = c->acc;
+    if (!A.on || !A.dirty) return;
+    Pool &p = c->pool;
+    hipStream_t s = c->stream;
+    const uint64_t n = A.n + A.lng.n;
+    c->wide.release(p);
+    keys_reserve(c, n + 1);
+    KeysBuf &k = c->keys;
+    HIPCHK(hipMemsetAsync(&c->d_cnt[CNT_KEYS], 0, sizeof(unsigned long long), s));
+    if (A.T.cap) mrg_acc_launch_emit(A.T, is_idx(c), k.ks, A.n, &c->d_cnt[CNT_KEYS], s);
+    HIPCHK(hipGetLastError());
+    if (A.lng.n) {  // the long rows behind the short keys; their heap offsets stay valid in a copy of the heap
+        const KeySet &l = A.lng.ks;
+        const uint64_t m = A.lng.n;
+        HIPCHK(hipMemcpyAsync(k.ks.k0 + A.n, l.k0, 8 * m, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(k.ks.k1 + A.n, l.k1, 8 * m, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(k.ks.cnt + A.n, l.cnt, 8 * m, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(k.ks.hoff + A.n, l.hoff, 8 * m, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(k.ks.doc + A.n, l.doc, 4 * m, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(k.ks.len + A.n, l.len, 4 * m, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(k.ks.part + A.n, l.part, 4 * m, hipMemcpyDeviceToDevice, s));
+        k.heap = pget<uint8_t>(p, A.lng.heap_bytes + 16);
+        if (A.lng.heap_bytes)
+            HIPCHK(hipMemcpyAsync(k.heap, A.lng.heap, A.lng.heap_bytes, hipMemcpyDeviceToDevice, s));
+        k.heap_bytes = A.lng.heap_bytes;
+        k.any_long = true;
+    }
+    read_counters(c);
+    if (c->h_cnt[CNT_KEYS] != A.n)
+        raise(MRG_EHIP, "internal: accumulator holds %llu keys, %llu expected", (unsigned long long)c->h_cnt[CNT_KEYS],
+              (unsigned long long)A.n);
+    k.n = n;
+    k.sorted = false;
+    c->st.distinct_keys = n;
+    A.dirty = false;
+}
+
+// mrg_job_map_add: map the input like mrg_job_map, then ADD the batch's keys to the job's.
+void job_map_add(mrg_ctx *c) {
+    need_job(c);
+    if (c->doc_off.empty()) raise(MRG_EINVAL, "no input: call mrg_job_set_input first");
+    Acc &A = c->acc;
+    flush_stage(c);  // (nothing is pending between calls: every map launch flushes first)
+    sync(c);
+    c->stage_used = c->pend_lo = 0;  // the previous batch's staged copies are done: the staging region is free
+    if (!A.on) {  // the keys the job holds already (mrg_job_map / mrg_job_import) come first
+        if (c->keyed) {
+            wide_densify(c, 0);
+            A.on = A.seeded = true;
+            A.in_bytes = c->st.input_bytes;
+            A.tokens = c->st.tokens;
+            A.long_tokens = c->st.long_tokens;
+            KeysBuf b = c->keys;
+            c->keys = KeysBuf{};
+            c->keyed = false;
+            try {
+                acc_fold(c, b);
+            } catch (...) {  // (out of memory with the keys already moved: the job is left without keys)
+                acc_release(c);
+                c->mapped = false;
+                throw;
+            }
+        }
+        A.on = true;
+    }
+    // the job's keys are in the accumulator; c->keys is a view of it, which the map below rebuilds for
+    // the batch alone -- so a batch that fails leaves the job with exactly the keys it had
+    const mrg_stats st0 = c->st;
+    const bool had = A.seeded || A.batches;
+    try {
+        job_map(c);
+        wide_densify(c, 0);
+        KeysBuf b = c->keys;
+        c->keys = KeysBuf{};
+        c->keyed = false;
+        acc_fold(c, b);
+        ev_rec(c, 7);
+        A.ms_fold = ev_ms(c, 3, 7);
+    } catch (...) {
+        keys_release(c);
+        c->wide.release(c->pool);
+        c->keyed = false;
+        c->st = st0;
+        c->mapped = had;
+        c->reduced = false;
+        A.dirty = true;
+        throw;
+    }
+    A.in_bytes += c->st.input_bytes;
+    A.tokens += c->st.tokens;
+    A.long_tokens += c->st.long_tokens;
+    ++A.batches;
+    c->st.input_bytes = A.in_bytes;
+    c->st.tokens = A.tokens;
+    c->st.long_tokens = A.long_tokens;
+    c->st.map_batches = A.batches;
+    c->st.distinct_keys = A.n + A.lng.n;
     c->mapped = true;
+    c->reduced = false;
+    // the device has read the last of the batch's buffer (acc_fold waited for the stream): the caller
+    // may overwrite or free it; the next batch needs its own mrg_job_set_input
+    c->d_in = nullptr;
+    c->doc_off.clear();
+    c->doc_ids.clear();
 }
 
 // Indexer document order = bytewise order of the names (the indexer reduce sorts its values):
@@ -1973,6 +2252,7 @@ void wide_reduce(mrg_ctx *c) {
 void job_reduce(mrg_ctx *c) {
     need_job(c);
     if (!c->mapped) raise(MRG_EINVAL, "nothing to reduce: call mrg_job_map or mrg_job_import first");
+    acc_emit(c);
     if (c->wide.ready) {
         wide_reduce(c);
         return;
@@ -2026,6 +2306,7 @@ void job_reduce(mrg_ctx *c) {
 void job_final(mrg_ctx *c) {
     need_job(c);
     if (!c->mapped) raise(MRG_EINVAL, "no keys: call mrg_job_map or mrg_job_import first");
+    acc_emit(c);
     wide_densify(c, 0);
     Pool &p = c->pool;
     hipStream_t s = c->stream;
@@ -2064,6 +2345,7 @@ void job_topk(mrg_ctx *c, uint64_t k) {
     need_job(c);
     if (is_idx(c)) raise(MRG_EINVAL, "mrg_job_topk: word count only (the indexer has no counts to rank)");
     if (!c->mapped) raise(MRG_EINVAL, "no keys: call mrg_job_map or mrg_job_import first");
+    acc_emit(c);
     wide_densify(c, 0);
     Pool &p = c->pool;
     hipStream_t s = c->stream;
@@ -2143,6 +2425,7 @@ void export_sizes(mrg_ctx *c, uint32_t n_owners, uint64_t *h_rec, uint64_t *h_he
     need_job(c);
     if (!c->mapped) raise(MRG_EINVAL, "export before map");
     if (n_owners == 0) raise(MRG_EINVAL, "n_owners must be > 0");
+    acc_emit(c);
     wide_densify(c, 0);
     Pool &p = c->pool;
     hipStream_t s = c->stream;
@@ -2191,6 +2474,9 @@ void import_recs(mrg_ctx *c, const XRec *xr, const LRec *lr, uint64_t n_rec, con
                  const uint64_t *seg_recs, const uint64_t *seg_heap, uint32_t n_segs) {
     need_job(c);
     c->wide.release(c->pool);  // the imported records replace the job's keys, whatever path the map took
+    acc_release(c);            // (and the accumulator of mrg_job_map_add)
+    c->keyed = false;
+    c->st.map_batches = 0;
     Pool &p = c->pool;
     hipStream_t s = c->stream;
     std::vector<uint64_t> rec_end, heap_base;
@@ -2233,7 +2519,7 @@ void import_recs(mrg_ctx *c, const XRec *xr, const LRec *lr, uint64_t n_rec, con
     sync(c);
     p.put(d_seg); p.put(li.start); p.put(li.rawlen); p.put(li.doc); p.put(li.cnt);
     c->st.ms_aggregate = ev_ms(c, 2, 3);
-    c->mapped = true;
+    c->mapped = c->keyed = true;
     c->reduced = false;
 }
 
@@ -2753,7 +3039,16 @@ int mrg_job_set_input(mrg_ctx *c, const uint8_t *d_bytes, const uint64_t *h_doc_
 }
 
 int mrg_job_map(mrg_ctx *c) {
-    return guard([&] { job_map(c); });
+    return guard([&] {
+        need_job(c);
+        acc_release(c);  // replaces the job's keys: what mrg_job_map_add accumulated goes too
+        c->st.map_batches = 0;
+        job_map(c);
+    });
+}
+
+int mrg_job_map_add(mrg_ctx *c) {
+    return guard([&] { job_map_add(c); });
 }
 
 int mrg_job_export_sizes(mrg_ctx *c, uint32_t n_owners, uint64_t *h_rec_counts, uint64_t *h_heap_bytes) {
@@ -3060,6 +3355,21 @@ double ms_since(Clock::time_point t0) {
 }
 
 thread_local mrg_run_stats g_run{};
+thread_local uint32_t g_stream_batches = 0;   // mrg_run_get_stream_stats
+thread_local uint64_t g_stream_peak = 0;
+
+// MRG_FLAG_STREAM: the batches of one GPU's files, first[i] = first file of batch i.  A batch is a
+// maximal run of consecutive files whose sizes sum to at most batch_bytes; a larger file is a batch of
+// its own; zero-length files join their neighbours (they never end a run that still has room).
+std::vector<uint32_t> stream_plan(const uint64_t *sizes, size_t n, uint64_t batch_bytes) {
+    std::vector<uint32_t> first;
+    for (size_t i = 0; i < n;) {
+        first.push_back((uint32_t)i);
+        uint64_t sum = sizes[i++];
+        while (i < n && sum <= batch_bytes && sizes[i] <= batch_bytes - sum) sum += sizes[i++];
+    }
+    return first;
+}
 
 void write_file(const std::string &path, const uint8_t *p, uint64_t n) {
     FILE *f = fopen(path.c_str(), "wb");  // worker.rs:167-168 File::create("mr-{r}.txt")
@@ -3164,14 +3474,47 @@ struct FileChunk {
 };
 
 constexpr uint64_t MRG_READ_CHUNK = 32ull << 20;
+// MRG_FLAG_STREAM reads with smaller chunks: the readers' pinned staging (two chunks per thread) is made
+// and freed once per job, at a cost that grows with its size and that no longer hides in a long read
+// (measured: DESIGN.md section 18)
+constexpr uint64_t MRG_STREAM_READ_CHUNK = 8ull << 20;
+
+// The reader threads' pinned staging buffers, copy streams and events.  One call makes and frees its
+// own; a caller that reads batch after batch (MRG_FLAG_STREAM) keeps one across its calls -- pinning
+// the buffers again for every batch cost more than reading it.
+struct ReadStage {
+    struct Slot {
+        hipStream_t st = nullptr;
+        uint8_t *pin[2] = {nullptr, nullptr};
+        hipEvent_t ev[2] = {nullptr, nullptr};
+        uint64_t bytes = 0;
+        void release() {
+            if (st) (void)hipStreamSynchronize(st);
+            for (int k = 0; k < 2; ++k) {
+                if (ev[k]) (void)hipEventDestroy(ev[k]);
+                if (pin[k]) (void)hipHostFree(pin[k]);
+            }
+            if (st) (void)hipStreamDestroy(st);
+            *this = Slot{};
+        }
+    };
+    int device = 0;
+    std::vector<Slot> slots;  // one per reader thread
+    ~ReadStage() {
+        (void)hipSetDevice(device);
+        for (auto &sl : slots) sl.release();
+    }
+};
 
 void read_files_to_device(int device, const std::vector<const char *> &paths, const std::vector<uint64_t> &doc_off,
-                          uint8_t *d, int n_threads) {
+                          uint8_t *d, int n_threads, ReadStage *stage = nullptr, uint64_t chunk_dflt = MRG_READ_CHUNK) {
     std::vector<FileChunk> chunks;
+    // (MRG_READ_CHUNK_MIB: a tuning knob for the staging size, tools/time_stream.py)
+    const uint64_t chunk = std::max<uint64_t>(1, env_u64("MRG_READ_CHUNK_MIB", chunk_dflt >> 20)) << 20;
     for (uint32_t i = 0; i < paths.size(); ++i) {
         const uint64_t sz = doc_off[i + 1] - doc_off[i];
-        for (uint64_t o = 0; o < sz; o += MRG_READ_CHUNK)
-            chunks.push_back({i, o, std::min<uint64_t>(MRG_READ_CHUNK, sz - o), doc_off[i] + o});
+        for (uint64_t o = 0; o < sz; o += chunk)
+            chunks.push_back({i, o, std::min<uint64_t>(chunk, sz - o), doc_off[i] + o});
     }
     if (chunks.empty()) return;
     n_threads = std::max(1, std::min<int>(n_threads, (int)chunks.size()));
@@ -3181,27 +3524,36 @@ void read_files_to_device(int device, const std::vector<const char *> &paths, co
     std::atomic<int> fail{0};
     std::vector<int> rc(n_threads, MRG_OK);
     std::vector<std::string> msg(n_threads);
+    if (stage) {
+        stage->device = device;
+        if (stage->slots.size() < (size_t)n_threads) stage->slots.resize((size_t)n_threads);
+    }
     auto reader = [&](int t) {
         rc[t] = guard([&] {
             HIPCHK(hipSetDevice(device));
-            hipStream_t st = nullptr;
-            uint8_t *pin[2] = {nullptr, nullptr};
-            hipEvent_t ev[2] = {nullptr, nullptr};
+            ReadStage::Slot local;
+            ReadStage::Slot &sl = stage ? stage->slots[(size_t)t] : local;
             std::vector<int> fds(paths.size(), -1);
-            struct Res {  // released on every exit path
-                hipStream_t &st; uint8_t **pin; hipEvent_t *ev; std::vector<int> &fds;
+            struct Res {  // on every exit path: the copies done, the files closed, a one-call stage freed
+                ReadStage::Slot &sl; bool own; std::vector<int> &fds;
                 ~Res() {
-                    if (st) (void)hipStreamSynchronize(st);
-                    for (int k = 0; k < 2; ++k) { if (ev[k]) (void)hipEventDestroy(ev[k]); if (pin[k]) (void)hipHostFree(pin[k]); }
-                    if (st) (void)hipStreamDestroy(st);
+                    if (sl.st) (void)hipStreamSynchronize(sl.st);
+                    if (own) sl.release();
                     for (int fd : fds) if (fd >= 0) close(fd);
                 }
-            } res{st, pin, ev, fds};
-            HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-            for (int k = 0; k < 2; ++k) {
-                HIPCHK(hipHostMalloc(&pin[k], pin_bytes, hipHostMallocDefault));
-                HIPCHK(hipEventCreateWithFlags(&ev[k], hipEventDisableTiming));
+            } res{sl, stage == nullptr, fds};
+            if (sl.bytes < pin_bytes) {  // (a kept stage grows to the largest chunk it meets)
+                sl.release();
+                HIPCHK(hipStreamCreateWithFlags(&sl.st, hipStreamNonBlocking));
+                for (int k = 0; k < 2; ++k) {
+                    HIPCHK(hipHostMalloc(&sl.pin[k], pin_bytes, hipHostMallocDefault));
+                    HIPCHK(hipEventCreateWithFlags(&sl.ev[k], hipEventDisableTiming));
+                }
+                sl.bytes = pin_bytes;
             }
+            hipStream_t st = sl.st;
+            uint8_t **pin = sl.pin;
+            hipEvent_t *ev = sl.ev;
             bool used[2] = {false, false};
             for (int k = 0;; k ^= 1) {
                 if (fail.load()) return;
@@ -3244,8 +3596,9 @@ struct RankState {
     int g = 0, device = 0;
     mrg_ctx *c = nullptr;
     mrg_comm *m = nullptr;
-    uint8_t *d = nullptr;
-    uint64_t in_bytes = 0;
+    uint8_t *d = nullptr, *d2 = nullptr;  // device input (MRG_FLAG_STREAM: the two batch buffers)
+    uint64_t in_bytes = 0, buf_bytes = 0;
+    uint32_t batches = 0;
     std::vector<uint8_t> out, fin, top;
 };
 
@@ -3315,6 +3668,7 @@ void release_ranks(std::vector<RankState> &rs) {
         if (r.d && r.c) {
             (void)hipSetDevice(r.device);
             r.c->pool.put(r.d);
+            r.c->pool.put(r.d2);
         }
         if (r.m) (void)mrg_comm_destroy(r.m);
         if (r.c) (void)mrg_close(r.c);
@@ -3332,6 +3686,8 @@ void run_job(const char *const *files, size_t n_files, uint32_t R, int app, cons
              const std::vector<int> &devices) {
     const Clock::time_point t_all = Clock::now();
     g_run = mrg_run_stats{};
+    g_stream_batches = 0;
+    g_stream_peak = 0;
     const int G = (int)devices.size();
     g_run.n_gpus = G;
     const uint64_t top_k = flags >> 16;  // MRG_FLAG_TOP(k): also out_dir/top.txt
@@ -3388,13 +3744,94 @@ void run_job(const char *const *files, size_t n_files, uint32_t R, int app, cons
             ids.push_back((uint32_t)m);
         }
         r.in_bytes = off.back();
+        double a0 = 0.0, a1 = 0.0;
+        if (flags & MRG_FLAG_STREAM) {
+            // batches of whole files, mapped one at a time (mrg_job_map_add) while a helper thread reads
+            // the next one into the other buffer.  Both buffers are taken here: the pool is not
+            // thread-safe, and the helper touches neither it nor the context.
+            std::vector<uint64_t> sizes;
+            for (size_t i = 0; i + 1 < off.size(); ++i) sizes.push_back(off[i + 1] - off[i]);
+            uint64_t bb = env_u64("MRG_STREAM_BATCH_BYTES", 0);
+            if (!bb) bb = 4ull << 30;  // the best of 256 MiB / 1 GiB / 4 GiB measured
+            std::vector<uint32_t> first = stream_plan(sizes.data(), sizes.size(), bb);
+            const size_t nb = first.size();
+            first.push_back((uint32_t)sizes.size());
+            uint64_t maxb = 0;
+            for (size_t i = 0; i < nb; ++i) maxb = std::max(maxb, off[first[i + 1]] - off[first[i]]);
+            uint8_t *buf[2] = {nullptr, nullptr};
+            if (nb) buf[0] = r.d = pget<uint8_t>(c->pool, maxb + 64);
+            if (nb > 1) buf[1] = r.d2 = pget<uint8_t>(c->pool, maxb + 64);
+            r.buf_bytes = (uint64_t)std::min<size_t>(nb, 2) * (maxb + 64);
+            r.batches = (uint32_t)nb;
+            c->pool.alloc_stats(nullptr, nullptr, &a0);
+            c->timing = true;
+            ReadStage stage;  // the readers' pinned buffers, kept over the batches (freed after the last join)
+            struct Read {  // one batch's read on the helper thread
+                std::thread th;
+                int rc = MRG_OK;
+                std::string msg;
+                std::vector<const char *> paths;
+                std::vector<uint64_t> boff;
+            } rd;
+            struct Join { Read &rd; ~Join() { if (rd.th.joinable()) rd.th.join(); } } join{rd};  // on every path
+            auto start_read = [&](size_t i) {
+                rd.rc = MRG_OK;
+                rd.paths.assign(mine.begin() + first[i], mine.begin() + first[i + 1]);
+                rd.boff.assign(1, 0);
+                for (uint32_t f = first[i]; f < first[i + 1]; ++f) rd.boff.push_back(off[f + 1] - off[first[i]]);
+                uint8_t *dst = buf[i & 1];
+                rd.th = std::thread([&rd, &stage, dst, dev = c->device, readers] {
+                    rd.rc = guard([&] {
+                        HIPCHK(hipSetDevice(dev));
+                        read_files_to_device(dev, rd.paths, rd.boff, dst, readers, &stage, MRG_STREAM_READ_CHUNK);
+                    });
+                    if (rd.rc) rd.msg = g_err;
+                });
+            };
+            double waited = ms_since(tr);  // (stat + plan + buffers: before the first read)
+            double t_add = 0.0, t_start = 0.0;
+            if (nb) start_read(0);
+            for (size_t i = 0; i < nb; ++i) {
+                const Clock::time_point tw = Clock::now();
+                rd.th.join();
+                waited += ms_since(tw);
+                if (rd.rc) raise(rd.rc, "%s", rd.msg.c_str());
+                const std::vector<uint64_t> boff = rd.boff;
+                // buffer (i + 1) & 1 is free: the map of batch i - 1 has returned (it waits for the stream)
+                const Clock::time_point ts = Clock::now();
+                if (i + 1 < nb) start_read(i + 1);
+                t_start += ms_since(ts);
+                c->d_in = buf[i & 1];
+                c->doc_off = boff;
+                c->doc_ids.assign(ids.begin() + first[i], ids.begin() + first[i + 1]);
+                const Clock::time_point ta = Clock::now();
+                job_map_add(c);
+                t_add += ms_since(ta);
+                t_mapk[r.g] += c->st.ms_map;
+                t_aggk[r.g] += c->st.ms_aggregate;
+            }
+            if (!nb) {  // no files: an empty job, as the unstreamed path maps an empty input
+                r.d = pget<uint8_t>(c->pool, 64);
+                c->d_in = r.d;
+                c->doc_off.assign(1, 0);
+                c->doc_ids.clear();
+                job_map_add(c);
+            }
+            t_read[r.g] = waited;
+            c->pool.alloc_stats(nullptr, nullptr, &a1);
+            t_alloc[r.g] = a1 - a0;
+            if (getenv("MRG_DEBUG"))
+                fprintf(stderr, "[mrgpu] stream GPU %d: %zu batches, waited for reads %.2f ms, map_add calls %.2f ms, "
+                        "read starts %.2f ms, phase so far %.2f ms\n", r.g, nb, waited, t_add, t_start, ms_since(tr));
+            return;
+        }
+        r.buf_bytes = off.back();
         r.d = pget<uint8_t>(c->pool, off.back() + 64);
         read_files_to_device(c->device, mine, off, r.d, readers);
         t_read[r.g] = ms_since(tr);
         c->d_in = r.d;
         c->doc_off = off;
         c->doc_ids = ids;
-        double a0 = 0.0, a1 = 0.0;
         c->pool.alloc_stats(nullptr, nullptr, &a0);
         c->timing = true;  // HIP events around the map and aggregation kernels (mrg_run_stats)
         job_map(c);
@@ -3411,6 +3848,8 @@ void run_job(const char *const *files, size_t n_files, uint32_t R, int app, cons
         g_run.ms_aggregate_kernel = std::max(g_run.ms_aggregate_kernel, t_aggk[g]);
         g_run.ms_read = std::max(g_run.ms_read, t_read[g]);
         g_run.input_bytes += rs[g].in_bytes;
+        g_stream_batches = std::max(g_stream_batches, rs[g].batches);
+        g_stream_peak = std::max(g_stream_peak, rs[g].buf_bytes);
     }
     g_run.ms_map -= g_run.ms_read;
     // ---- exchange (RCCL over xGMI)
@@ -3499,6 +3938,39 @@ int mrg_run_get_stats(mrg_run_stats *out) {
     return guard([&] {
         if (!out) raise(MRG_EINVAL, "null argument");
         *out = g_run;
+    });
+}
+
+int mrg_run_get_stream_stats(uint32_t *batches, uint64_t *peak_input_bytes) {
+    if (batches) *batches = g_stream_batches;
+    if (peak_input_bytes) *peak_input_bytes = g_stream_peak;
+    return MRG_OK;
+}
+
+// Diagnostics of the accumulator (not in include/mrgpu.h; tools/time_stream.py): h_info[0..6) = table
+// slots, short keys, long keys, long-key heap bytes, rehashes so far, batches; *ms_fold = the last
+// batch's fold (HIP events, with mrg_set_timing: aggregation end .. fold end).  Either may be NULL.
+int mrg_test_acc_info(mrg_ctx *c, uint64_t *h_info, double *ms_fold) {
+    return guard([&] {
+        need_job(c);
+        const Acc &A = c->acc;
+        if (h_info) {
+            const uint64_t v[6] = {A.T.cap, A.n, A.lng.n, A.lng.heap_bytes, A.rehashes, A.batches};
+            memcpy(h_info, v, sizeof v);
+        }
+        if (ms_fold) *ms_fold = A.ms_fold;
+    });
+}
+
+// Test entry (not in include/mrgpu.h): the batch plan of MRG_FLAG_STREAM over one GPU's file sizes,
+// callable without a GPU.  first[i] (room for n entries) = first file of batch i; *n_batches = batches.
+int mrg_test_stream_plan(const uint64_t *sizes, size_t n, uint64_t batch_bytes, uint32_t *first, size_t *n_batches) {
+    return guard([&] {
+        if (!n_batches || (n && (!sizes || !first))) raise(MRG_EINVAL, "null argument");
+        if (n > 0xFFFFFFFFull) raise(MRG_EINVAL, "too many files");
+        const std::vector<uint32_t> f = stream_plan(sizes, n, batch_bytes);
+        if (!f.empty()) memcpy(first, f.data(), sizeof(uint32_t) * f.size());
+        *n_batches = f.size();
     });
 }
 

@@ -6,8 +6,10 @@
 // map -> reduce hand-off is an RCCL all-to-all over xGMI (mrg_job_shuffle).
 // --final also writes final.txt, the output of src/run.sh:16-20 (cat mr-* | sort, LC_ALL=C), built on the GPUs.
 // --top K also writes top.txt, the K (1..65535) most frequent lines of final.txt (count descending, then key).
+// --stream maps each GPU's files in batches (MRG_STREAM_BATCH_BYTES, default 4 GiB) while the next batch is read
+//   (MRG_FLAG_STREAM): same output files, an input footprint of two batches.
 // --times prints the wall-clock phases of the job (mrg_run_get_stats) as one JSON line on stderr.
-//   usage: mrgpu <map_n> <reduce_n> [--gpus N] [--app wc|indexer] [--no-compat-drop-last] [--final] [--top K] [--times]
+//   usage: mrgpu <map_n> <reduce_n> [--gpus N] [--app wc|indexer] [--no-compat-drop-last] [--final] [--top K] [--stream] [--times]
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -20,7 +22,7 @@
 int main(int argc, char **argv) {
     if (argc < 3) {
         fprintf(stderr, "Usage: mrgpu <input files number> <reduce task number> [--gpus N] [--app wc|indexer] "
-                        "[--no-compat-drop-last] [--final] [--top K] [--times]\n");
+                        "[--no-compat-drop-last] [--final] [--top K] [--stream] [--times]\n");
         return 2;
     }
     const int map_n = atoi(argv[1]);
@@ -45,6 +47,8 @@ int main(int argc, char **argv) {
                 return 2;
             }
             flags |= MRG_FLAG_TOP(k);
+        } else if (!strcmp(argv[i], "--stream")) {
+            flags |= MRG_FLAG_STREAM;
         } else if (!strcmp(argv[i], "--times")) {
             times = true;
         } else {
@@ -68,12 +72,18 @@ int main(int argc, char **argv) {
     }
     if (times) {
         mrg_run_stats st;
+        uint32_t batches = 0;
+        uint64_t peak = 0;
+        (void)mrg_run_get_stream_stats(&batches, &peak);
         if (mrg_run_get_stats(&st) == MRG_OK)
             fprintf(stderr,
                     "{\"ms_total\": %.3f, \"ms_open\": %.3f, \"ms_read\": %.3f, \"ms_map\": %.3f, \"ms_shuffle\": %.3f, "
-                    "\"ms_reduce\": %.3f, \"ms_write\": %.3f, \"input_bytes\": %llu, \"output_bytes\": %llu, \"n_gpus\": %d}\n",
+                    "\"ms_reduce\": %.3f, \"ms_write\": %.3f, \"input_bytes\": %llu, \"output_bytes\": %llu, \"n_gpus\": %d, "
+                    "\"ms_map_kernel\": %.3f, \"ms_aggregate_kernel\": %.3f, \"stream\": %d, \"batches\": %u, "
+                    "\"peak_input_bytes\": %llu}\n",
                     st.ms_total, st.ms_open, st.ms_read, st.ms_map, st.ms_shuffle, st.ms_reduce, st.ms_write,
-                    (unsigned long long)st.input_bytes, (unsigned long long)st.output_bytes, st.n_gpus);
+                    (unsigned long long)st.input_bytes, (unsigned long long)st.output_bytes, st.n_gpus, st.ms_map_kernel, st.ms_aggregate_kernel,
+                    (flags & MRG_FLAG_STREAM) ? 1 : 0, batches, (unsigned long long)peak);
     }
     return 0;
 }

@@ -13,6 +13,7 @@ APP_WC = 0
 APP_INDEXER = 1
 FLAG_NO_COMPAT_DROP_LAST = 0x1
 FLAG_FINAL_TXT = 0x2
+FLAG_STREAM = 0x4  # run_job only: map each GPU's files in batches while the next batch is read
 XREC_BYTES = 24  # include/mrgpu.h MRG_XREC_BYTES (ABI 3)
 ABI_VERSION = 6  # include/mrgpu.h MRG_ABI_VERSION
 
@@ -62,7 +63,7 @@ class Stats(C.Structure):
                 ("overflow_keys", C.c_uint64), ("ms_exchange", C.c_double), ("exchange_sent", C.c_uint64),
                 ("exchange_recv", C.c_uint64), ("map_spill", C.c_uint64),
                 ("nonascii_tiles", C.c_uint64), ("tail_records_16", C.c_uint64), ("spec_agg", C.c_uint32),
-                ("agg_path", C.c_uint32), ("map_kind", C.c_uint32), ("reserved", C.c_uint32)]
+                ("agg_path", C.c_uint32), ("map_kind", C.c_uint32), ("map_batches", C.c_uint32)]
 
     def as_dict(self):
         return {f: getattr(self, f) for f, _ in self._fields_}
@@ -97,6 +98,7 @@ _SIGS = {
     "mrg_job_set_doc_names": (C.c_int, [_vp, C.POINTER(C.c_char_p), C.c_uint32]),
     "mrg_job_set_input": (C.c_int, [_vp, _vp, _u64p, C.c_uint32, _u32p]),
     "mrg_job_map": (C.c_int, [_vp]),
+    "mrg_job_map_add": (C.c_int, [_vp]),
     "mrg_job_export_sizes": (C.c_int, [_vp, C.c_uint32, _u64p, _u64p]),
     "mrg_job_export": (C.c_int, [_vp, _vp, _vp]),
     "mrg_job_import": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, _u64p, _u64p, C.c_uint32]),
@@ -119,6 +121,7 @@ _SIGS = {
     "mrg_run_job": (C.c_int, [C.POINTER(C.c_char_p), C.c_size_t, C.c_uint32, C.c_int, C.c_char_p, C.c_uint32,
                               C.c_int]),
     "mrg_run_get_stats": (C.c_int, [C.POINTER(RunStats)]),
+    "mrg_run_get_stream_stats": (C.c_int, [_u32p, _u64p]),
     "mrg_comm_get_id": (C.c_int, [_vp]),
     "mrg_comm_init": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.POINTER(_vp)]),
     "mrg_comm_destroy": (C.c_int, [_vp]),
@@ -261,6 +264,23 @@ class Context:
     def map(self):
         _check(load().mrg_job_map(self.h))
 
+    def map_add(self):
+        """mrg_job_map_add: map the input set by set_input() and ADD its tokens to the job's keys.
+        Repeat set_input() + map_add() per batch of whole documents; the consumers then see one map
+        over all batches.  The batch's buffer may be overwritten once this returns."""
+        _check(load().mrg_job_map_add(self.h))
+
+    def acc_info(self):
+        """Diagnostics of the map_add accumulator: table slots, short and long keys, long-key heap
+        bytes, rehashes and batches so far, and the last batch's fold time (with set_timing)."""
+        f = load().mrg_test_acc_info
+        f.restype = C.c_int
+        f.argtypes = [_vp, _u64p, C.POINTER(C.c_double)]
+        info, ms = (C.c_uint64 * 6)(), C.c_double()
+        _check(f(self.h, info, C.byref(ms)))
+        return {"slots": info[0], "short_keys": info[1], "long_keys": info[2], "long_heap_bytes": info[3],
+                "rehashes": info[4], "batches": info[5], "ms_fold": ms.value}
+
     def export_sizes(self, n_owners):
         rec = (C.c_uint64 * n_owners)()
         heap = (C.c_uint64 * n_owners)()
@@ -394,6 +414,27 @@ def run_job(files, n_reduce, app=APP_WC, out_dir=".", flags=0, n_gpus=1):
     st = RunStats()
     _check(load().mrg_run_get_stats(C.byref(st)))
     return st.as_dict()
+
+
+def run_stream_stats():
+    """mrg_run_get_stream_stats: (batches mapped, peak bytes of device input buffers) of this thread's
+    last run_job; 0 batches without FLAG_STREAM (the peak is then the whole input)."""
+    b, p = C.c_uint32(), C.c_uint64()
+    _check(load().mrg_run_get_stream_stats(C.byref(b), C.byref(p)))
+    return b.value, p.value
+
+
+def stream_plan(sizes, batch_bytes):
+    """The batch plan of FLAG_STREAM over one GPU's file sizes (test entry, no GPU needed): the index
+    of each batch's first file."""
+    L = load()
+    f = L.mrg_test_stream_plan
+    f.restype = C.c_int
+    f.argtypes = [_u64p, C.c_size_t, C.c_uint64, _u32p, C.POINTER(C.c_size_t)]
+    first = (C.c_uint32 * max(len(sizes), 1))()
+    n = C.c_size_t()
+    _check(f(_u64arr(sizes), len(sizes), batch_bytes, first, C.byref(n)))
+    return list(first[:n.value])
 
 
 def merge_sorted_lines(runs):

@@ -22,6 +22,8 @@ pub const MRG_FLAG_NO_COMPAT_DROP_LAST: u32 = 0x1;
 pub const MRG_TEXT_ASCII: u32 = 0;
 pub const MRG_TEXT_GUTENBERG: u32 = 1;
 pub const MRG_FLAG_FINAL_TXT: u32 = 0x2;
+/// `mrg_run_job` only: map each GPU's files in batches while the next batch is read.
+pub const MRG_FLAG_STREAM: u32 = 0x4;
 pub const fn mrg_flag_debug_hash_bits(n: u32) -> u32 {
     (n & 0xFF) << 8
 }
@@ -71,7 +73,7 @@ pub struct mrg_stats {
     pub spec_agg: u32,
     pub agg_path: u32,
     pub map_kind: u32,
-    pub reserved: u32,
+    pub map_batches: u32,
 }
 
 #[repr(C)]
@@ -106,6 +108,7 @@ extern "C" {
     pub fn mrg_job_set_input(ctx: *mut mrg_ctx, d_bytes: *const u8, h_doc_off: *const u64, n_docs: u32,
                              h_doc_ids: *const u32) -> c_int;
     pub fn mrg_job_map(ctx: *mut mrg_ctx) -> c_int;
+    pub fn mrg_job_map_add(ctx: *mut mrg_ctx) -> c_int;
     pub fn mrg_job_export_sizes(ctx: *mut mrg_ctx, n_owners: u32, h_rec_counts: *mut u64,
                                 h_heap_bytes: *mut u64) -> c_int;
     pub fn mrg_job_export(ctx: *mut mrg_ctx, d_rec: *mut c_void, d_heap: *mut c_void) -> c_int;
@@ -146,6 +149,7 @@ extern "C" {
     pub fn mrg_run_job(files: *const *const c_char, n_files: usize, n_reduce: u32, app: c_int,
                        out_dir: *const c_char, flags: u32, n_gpus: c_int) -> c_int;
     pub fn mrg_run_get_stats(out: *mut mrg_run_stats) -> c_int;
+    pub fn mrg_run_get_stream_stats(batches: *mut u32, peak_input_bytes: *mut u64) -> c_int;
     pub fn mrg_free(p: *mut c_void);
 
     pub fn mrg_gen_zipf(ctx: *mut mrg_ctx, d_dst: *mut u8, n_bytes: u64, seed: u64, file_index: u64, vocab: u32,
@@ -236,6 +240,14 @@ impl Ctx {
         check(unsafe { mrg_job_map(self.0) })
     }
 
+    /// Map the input set by `job_set_input` and ADD its tokens to the job's keys (`mrg_job_map_add`):
+    /// repeat { `job_set_input`, `job_map_add` } per batch of whole documents; the consumers then
+    /// see one map over all of them.  The batch's buffer may be reused once this returns.  A failing
+    /// batch (e.g. `MRG_EUTF8`) leaves the job's keys as they were.
+    pub fn job_map_add(&self) -> Result<(), Error> {
+        check(unsafe { mrg_job_map_add(self.0) })
+    }
+
     /// The exchange with the other ranks of `comm` (`mrg_job_shuffle`, RCCL over xGMI).
     pub fn shuffle(&self, comm: &Comm) -> Result<(), Error> {
         check(unsafe { mrg_job_shuffle(self.0, comm.0) })
@@ -313,4 +325,12 @@ pub fn run_job(files: &[&str], n_reduce: u32, app: c_int, out_dir: &str, flags: 
     let mut st = mrg_run_stats::default();
     check(unsafe { mrg_run_get_stats(&mut st) })?;
     Ok(st)
+}
+
+/// Batches mapped and peak bytes of device input buffers of this thread's last `run_job`
+/// (`mrg_run_get_stream_stats`; 0 batches without `MRG_FLAG_STREAM`).
+pub fn run_stream_stats() -> Result<(u32, u64), Error> {
+    let (mut b, mut p) = (0u32, 0u64);
+    check(unsafe { mrg_run_get_stream_stats(&mut b, &mut p) })?;
+    Ok((b, p))
 }
