@@ -76,6 +76,8 @@ extern "C" {
 
 typedef struct mrg_ctx mrg_ctx;
 typedef struct mrg_parts mrg_parts;
+typedef struct mrg_vocab mrg_vocab;
+#define MRG_ID_UNK 0xFFFFFFFFu   /* mrg_vocab_encode: the id of a word that is not in the vocabulary */
 
 typedef struct {
     uint64_t input_bytes;      /* bytes mapped */
@@ -115,7 +117,9 @@ typedef struct {
  * 6 = mrg_pool_alloc_stats.  mrg_version() names the ABI it implements.
  * (6, additive): mrg_job_topk, mrg_job_copy_topk, MRG_FLAG_TOP
  * (6, additive): mrg_job_map_add, MRG_FLAG_STREAM, mrg_run_get_stream_stats; mrg_stats.reserved is now
- * map_batches (same size and offset) */
+ * map_batches (same size and offset)
+ * (6, additive): mrg_job_vocab, mrg_vocab_size, mrg_vocab_copy_text, mrg_vocab_free, mrg_vocab_encode,
+ * MRG_ID_UNK */
 #define MRG_ABI_VERSION 6
 
 const char *mrg_last_error(void);
@@ -187,6 +191,46 @@ int mrg_job_copy_final(mrg_ctx *ctx, uint8_t *h_dst, uint64_t cap);
  * Any out pointer may be NULL.  k = 0 or no lines: zero bytes, MRG_OK. */
 int mrg_job_topk(mrg_ctx *ctx, uint64_t k, const uint8_t **d_out, uint64_t *h_bytes, uint64_t *h_lines);
 int mrg_job_copy_topk(mrg_ctx *ctx, uint8_t *h_dst, uint64_t cap);
+
+/* ---- vocabulary: the most frequent words as ids 0..n-1, and text -> id sequences on the device ----
+ * mrg_job_vocab freezes the job's most frequent words into a vocabulary object (word count only: the
+ * indexer gets MRG_EINVAL).  Callable whenever mrg_job_topk is (between mrg_job_map_add batches and
+ * after mrg_job_import too).  The word with id i is line i of what mrg_job_topk(ctx, max_words, ...)
+ * would return now: count descending, then key bytes ascending, with the last group of every partition
+ * dropped unless the job has MRG_FLAG_NO_COMPAT_DROP_LAST -- set that flag for a complete vocabulary.
+ * The list is cut at the first word whose count is below min_count (0 and 1: no cut).  max_words = 0:
+ * all words; more than 0xFFFFFFFE resulting words: MRG_EINVAL.  An empty vocabulary is valid.  The
+ * job's keys stay as they were; like any job call it may invalidate d_out pointers of earlier topk /
+ * final calls (and it replaces the lines mrg_job_copy_topk returns).  On failure *out is NULL and
+ * nothing is leaked.
+ * The vocabulary owns its device memory (the words' bytes are copied: nothing is borrowed from the
+ * job, the input buffer or the context's pool), so it survives mrg_job_begin, later jobs and mrg_close
+ * of the context that made it.  It is read-only after creation: any context on the same device may use
+ * it, from several threads at once; a context on another device gets MRG_EINVAL.  It inherits
+ * MRG_FLAG_DEBUG_HASH_BITS from its job.  mrg_vocab_free(NULL) is a no-op. */
+int mrg_job_vocab(mrg_ctx *ctx, uint64_t max_words, uint64_t min_count, mrg_vocab **out);
+/* Words in the vocabulary and bytes of its text.  Either pointer may be NULL. */
+int mrg_vocab_size(const mrg_vocab *v, uint64_t *n_words, uint64_t *text_bytes);
+/* The "word count\n" lines in id order, each byte-identical to the mrg_job_topk line the word came
+ * from, to host memory.  cap below the text's bytes: MRG_EINVAL. */
+int mrg_vocab_copy_text(const mrg_vocab *v, uint8_t *h_dst, uint64_t cap);
+void mrg_vocab_free(mrg_vocab *v);
+/* Text -> ids.  Input as for mrg_job_set_input: documents back to back in d_bytes (16-byte aligned),
+ * document i = d_bytes[h_doc_off[i] .. h_doc_off[i+1]).  The tokens are exactly those of wc::map
+ * (src/app/wc.rs:6-13), per document, in input order: a token is a maximal run of non-White_Space
+ * codepoints, its key the token's \w codepoints; a token with an empty key produces nothing; a token
+ * never crosses a document boundary.  d_ids[h_tok_off[i] .. h_tok_off[i+1]) receives document i's ids
+ * (h_tok_off has n_docs + 1 entries); a word not in the vocabulary gets MRG_ID_UNK.  Identity is the
+ * full key bytes, always (keys longer than 16 bytes are compared byte for byte).
+ * d_ids = NULL: count only -- h_tok_off is filled, nothing is written to the device output.  Otherwise
+ * cap_ids (in ids) < h_tok_off[n_docs] returns MRG_EINVAL with d_ids untouched.  Invalid UTF-8 returns
+ * MRG_EUTF8 (mrg_last_error names the document and the byte offset, as for the map); d_ids is then
+ * unspecified; the context, its job and the vocabulary stay usable.  The call needs no job and touches
+ * no job state (it is legal between the batches of a streamed job).  It runs on the context's stream
+ * with scratch from the context's pool (about 1/7 of the input's bytes), all returned before the call
+ * ends; on return the ids are complete and the caller may free or overwrite the input. */
+int mrg_vocab_encode(mrg_ctx *ctx, const mrg_vocab *v, const uint8_t *d_bytes, const uint64_t *h_doc_off,
+                     uint32_t n_docs, uint32_t *d_ids, uint64_t cap_ids, uint64_t *h_tok_off);
 
 /* ---- multi-GPU: one rank per GPU, the shuffle as an RCCL all-to-all over xGMI ----
  * The reference moves map output to the reduce workers through mr-{m}-{r}.txt files in a shared

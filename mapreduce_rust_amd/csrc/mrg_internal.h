@@ -519,6 +519,46 @@ void mrg_acc_launch_emit(const AccTable &t, bool indexer, KeySet out, uint64_t o
 void mrg_acc_launch_long(KeySet ks, uint64_t n, uint64_t heap_base, uint64_t first, uint64_t cap, uint64_t *start,
                          uint32_t *rawlen, uint32_t *doc, uint64_t *cnt, unsigned long long *counter, hipStream_t s);
 
+// ---- k_encode.hip: the frozen word -> id table of a vocabulary and the encoder
+// Open-addressing table over the vocabulary's words, SoA; empty slot: k0 = MRG_EMPTY_K0, k1 =
+// MRG_EMPTY_K1, id = 0xFFFFFFFF.  A short word's slot holds its packed key; a long word's slot holds
+// (hash of its bytes | 1 << 63, 0xFF << 56 | length) and is confirmed against text + line_off[id].
+struct VocTable {
+    uint64_t *k0, *k1;
+    uint32_t *id;
+    uint64_t cap;                // power of two, >= 2 n
+    uint32_t hash_bits;          // 0 = full; else truncated hashes (collision test knob, from the job's flags)
+    const uint8_t *text;         // "word count\n" lines in id order
+    const uint64_t *line_off;    // [n + 1]
+    uint64_t n;
+};
+// lines [0, m) of the ranked records `top` (idx = key index in ks): len64[j] = bytes of line j
+// (len64[m] = 0), wlen[j] = the word's bytes, *nkeep (zeroed) = lines whose count is >= min_count
+void mrg_voc_launch_lines(const SortRec *top, uint64_t m, KeySet ks, uint64_t min_count, uint64_t *len64,
+                          uint32_t *wlen, unsigned long long *nkeep, hipStream_t s);
+// clear the table and insert words [0, t.n); *fail (zeroed) counts words that found no slot (never)
+void mrg_voc_launch_build(const VocTable &t, const uint32_t *wlen, unsigned long long *fail, hipStream_t s);
+// One encode call.  Positions are byte offsets from `in` (16-byte aligned); the documents cover [lo, hi)
+// with lo < 1024; ntiles = 1 KiB chunks over [0, hi).
+struct EncPlan {
+    const uint8_t *in;
+    uint64_t lo, hi, ntiles;
+    uint32_t *bnd;               // [mrg_enc_bitmap_words(ntiles)] zeroed: the document-boundary bitmap
+    const uint64_t *doc_off;     // [n_docs + 1] device copy of the offsets
+    uint32_t n_docs;
+    uint64_t *cnt;               // [ntiles + 1] zeroed: tokens per chunk, then (scanned in place) chunk bases
+    uint64_t *tok_off;           // [n_docs + 1]
+    uint32_t *out;               // the ids (emit only)
+    uint64_t out_n;              // their number (tok_off[n_docs])
+    unsigned long long *err;     // all ones: first invalid UTF-8 byte
+    unsigned long long *info;    // [8] zeroed: tokens, UNK, long tokens, non-ASCII chunks, table probes
+};
+uint64_t mrg_enc_bitmap_words(uint64_t ntiles);
+void mrg_enc_launch_bounds(const EncPlan &p, hipStream_t s);
+void mrg_enc_launch_count(const EncPlan &p, const VocTable &t, hipStream_t s);    // fills cnt, err, info[3]
+void mrg_enc_launch_offsets(const EncPlan &p, const VocTable &t, hipStream_t s);  // after the scan of cnt
+void mrg_enc_launch_emit(const EncPlan &p, const VocTable &t, hipStream_t s);
+
 // ---- k_gen.hip
 int mrg_gen_zipf_impl(uint8_t *dst, uint64_t n, uint64_t seed, uint64_t file_index, uint32_t vocab, double s, uint32_t style,
                       hipStream_t st);

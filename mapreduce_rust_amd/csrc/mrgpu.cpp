@@ -22,6 +22,7 @@
 #include <chrono>
 #include <condition_variable>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -388,6 +389,21 @@ struct mrg_ctx {
     uint64_t top_pass_bytes[MRG_TOPK_DIGITS] = {};  // bytes each of its select passes read (0: pass not run)
     uint64_t extra_first = 0;       // text reduce: values of empty-key lines, folded into the first group
     mrg_stats st{};
+    // last mrg_vocab_encode (mrg_encode_info): tokens, UNK, long tokens, non-ASCII chunks, table probes,
+    // input bytes, scratch bytes; ms of the count, offsets (scan + boundaries) and emit passes, and of
+    // the last mrg_job_vocab (with mrg_set_timing)
+    uint64_t enc_info[8] = {};
+    double enc_ms[4] = {};
+    hipEvent_t enc_ev[6] = {};      // created on first use
+};
+
+// A vocabulary (mrg_job_vocab): one device allocation of its own -- the ranked "word count\n" lines, the
+// byte offset of every line, and the word -> id table over them (k_encode.hip).  Read-only once built.
+struct mrg_vocab {
+    int device = 0;
+    uint64_t n = 0, text_bytes = 0;
+    void *block = nullptr;
+    VocTable T{};
 };
 
 struct mrg_comm {
@@ -2341,7 +2357,9 @@ void job_final(mrg_ctx *c) {
 // sorting the keys (k_topk.hip): at most R keys are dropped, so these lines lie
 // within the k + R best keys; a radix select finds those, and only they are sorted and formatted.
 // Reads the key set only: reduce, final and export afterwards give what they give without it.
-void job_topk(mrg_ctx *c, uint64_t k) {
+// keep: *keep receives the ranked records of the lines written (idx = key index in c->keys), a pool
+// block the caller returns; null when no line was written (mrg_job_vocab).
+void job_topk(mrg_ctx *c, uint64_t k, SortRec **keep = nullptr) {
     need_job(c);
     if (is_idx(c)) raise(MRG_EINVAL, "mrg_job_topk: word count only (the indexer has no counts to rank)");
     if (!c->mapped) raise(MRG_EINVAL, "no keys: call mrg_job_map or mrg_job_import first");
@@ -2412,13 +2430,229 @@ void job_topk(mrg_ctx *c, uint64_t k) {
     uint64_t po[2] = {0, 0};
     mrg_format(f, p, &c->d_top, &c->top_cap, po, s);
     HIPCHK(hipGetLastError());
-    p.put(st); p.put(a); p.put(b); p.put(stmp); p.put(cand_last); p.put(ckeys); p.put(kvtmp); p.put(vals);
+    p.put(st); p.put(sorted); p.put(stmp); p.put(cand_last); p.put(ckeys); p.put(kvtmp); p.put(vals);
+    if (keep) *keep = top;
+    else p.put(top);
     c->top_bytes = po[1];
     c->top_lines = lines;
     c->topped = true;
     c->top_info[1] = m;
     c->top_info[2] = h.passes;
     c->top_info[3] = h.ndrop;
+}
+
+// Pool blocks of one call, returned on every exit.
+struct Scratch {
+    Pool &p;
+    std::vector<void *> b;
+    explicit Scratch(Pool &pool) : p(pool) {}
+    Scratch(const Scratch &) = delete;
+    Scratch &operator=(const Scratch &) = delete;
+    template <class T>
+    T *get(uint64_t n) {
+        b.push_back(nullptr);
+        return (T *)(b.back() = pget<T>(p, n));
+    }
+    void adopt(void *q) { b.push_back(q); }
+    ~Scratch() {
+        for (void *q : b) p.put(q);
+    }
+};
+
+void enc_events(mrg_ctx *c) {
+    if (!c->timing) return;
+    for (auto &e : c->enc_ev)
+        if (!e) HIPCHK(hipEventCreate(&e));
+}
+void enc_rec(mrg_ctx *c, int i) {
+    if (c->timing) HIPCHK(hipEventRecord(c->enc_ev[i], c->stream));
+}
+double enc_ms(mrg_ctx *c, int a, int b) {
+    if (!c->timing) return 0.0;
+    float ms = 0;
+    HIPCHK(hipEventSynchronize(c->enc_ev[b]));
+    HIPCHK(hipEventElapsedTime(&ms, c->enc_ev[a], c->enc_ev[b]));
+    return ms;
+}
+
+void vocab_destroy(mrg_vocab *v) {
+    if (!v) return;
+    if (v->block) {
+        int cur = -1;
+        (void)hipGetDevice(&cur);
+        (void)hipSetDevice(v->device);
+        (void)hipFree(v->block);
+        if (cur >= 0 && cur != v->device) (void)hipSetDevice(cur);
+    }
+    delete v;
+}
+
+// The vocabulary of the job's keys: mrg_job_topk's ranked lines, cut at
+// min_count, copied with their line offsets into one allocation of the vocabulary's own, and the
+// word -> id table over that copy.
+mrg_vocab *job_vocab(mrg_ctx *c, uint64_t max_words, uint64_t min_count) {
+    need_job(c);
+    if (is_idx(c)) raise(MRG_EINVAL, "mrg_job_vocab: word count only (the indexer has no counts to rank)");
+    Pool &p = c->pool;
+    hipStream_t s = c->stream;
+    Scratch sc(p);
+    enc_events(c);
+    enc_rec(c, 4);
+    SortRec *top = nullptr;
+    job_topk(c, max_words ? max_words : ~0ull, &top);
+    if (top) sc.adopt(top);
+    const uint64_t m = top ? c->top_lines : 0;
+    uint64_t n = 0, text_bytes = 0;
+    uint64_t *loff = nullptr;
+    uint32_t *wlen = nullptr;
+    if (m) {
+        loff = sc.get<uint64_t>(m + 1);
+        wlen = sc.get<uint32_t>(m);
+        uint64_t *stmp = sc.get<uint64_t>(mrg_scan_tmp_elems(m + 1));
+        unsigned long long *nk = sc.get<unsigned long long>(1);
+        HIPCHK(hipMemsetAsync(nk, 0, 8, s));
+        mrg_voc_launch_lines(top, m, c->keys.ks, min_count, loff, wlen, nk, s);
+        mrg_scan_u64(loff, loff, m + 1, stmp, s);
+        HIPCHK(hipMemcpyAsync(&n, nk, 8, hipMemcpyDeviceToHost, s));
+        sync(c);
+        if (n > m) raise(MRG_EHIP, "vocabulary: %llu of %llu lines kept", (unsigned long long)n, (unsigned long long)m);
+        HIPCHK(hipMemcpyAsync(&text_bytes, loff + n, 8, hipMemcpyDeviceToHost, s));
+        sync(c);
+        if (text_bytes > c->top_bytes) raise(MRG_EHIP, "vocabulary: line offsets exceed the ranked text");
+    }
+    if (n > 0xFFFFFFFEull) raise(MRG_EINVAL, "vocabulary of %llu words: ids are 32 bits", (unsigned long long)n);
+    struct Del {
+        void operator()(mrg_vocab *v) const { vocab_destroy(v); }
+    };
+    std::unique_ptr<mrg_vocab, Del> v(new mrg_vocab());
+    v->device = c->device;
+    v->n = n;
+    v->text_bytes = text_bytes;
+    const uint64_t cap = pow2_at_least(2 * n);
+    auto up = [](uint64_t x) { return (x + 255) & ~255ull; };
+    const uint64_t o_text = 0, o_loff = o_text + up(text_bytes + 16), o_k0 = o_loff + up(8 * (n + 1)),
+                   o_k1 = o_k0 + 8 * cap, o_id = o_k1 + 8 * cap, total = o_id + 4 * cap;
+    if (hipMalloc(&v->block, total) != hipSuccess) {
+        (void)hipGetLastError();
+        v->block = nullptr;
+        raise(MRG_ENOMEM, "vocabulary: device allocation of %llu bytes failed", (unsigned long long)total);
+    }
+    uint8_t *blk = (uint8_t *)v->block;
+    VocTable &T = v->T;
+    T.k0 = (uint64_t *)(blk + o_k0);
+    T.k1 = (uint64_t *)(blk + o_k1);
+    T.id = (uint32_t *)(blk + o_id);
+    T.cap = cap;
+    T.hash_bits = hash_bits(c);
+    T.text = blk + o_text;
+    T.line_off = (const uint64_t *)(blk + o_loff);
+    T.n = n;
+    if (text_bytes) HIPCHK(hipMemcpyAsync(blk + o_text, c->d_top, text_bytes, hipMemcpyDeviceToDevice, s));
+    if (n) HIPCHK(hipMemcpyAsync(blk + o_loff, loff, 8 * (n + 1), hipMemcpyDeviceToDevice, s));
+    else HIPCHK(hipMemsetAsync(blk + o_loff, 0, 8, s));
+    unsigned long long *fail = sc.get<unsigned long long>(1);
+    HIPCHK(hipMemsetAsync(fail, 0, 8, s));
+    mrg_voc_launch_build(T, wlen, fail, s);
+    HIPCHK(hipGetLastError());
+    unsigned long long hfail = 0;
+    HIPCHK(hipMemcpyAsync(&hfail, fail, 8, hipMemcpyDeviceToHost, s));
+    enc_rec(c, 5);
+    sync(c);
+    if (hfail) raise(MRG_EHIP, "vocabulary: %llu words found no table slot", hfail);
+    c->enc_ms[3] = enc_ms(c, 4, 5);
+    return v.release();
+}
+
+// Text -> ids (k_encode.hip): boundary bitmap, count pass, scan, per-document offsets, emit pass.
+// Touches no job state; scratch comes from the pool and goes back on every exit.
+void vocab_encode(mrg_ctx *c, const mrg_vocab *v, const uint8_t *d_bytes, const uint64_t *h_doc_off, uint32_t n_docs,
+                  uint32_t *d_ids, uint64_t cap_ids, uint64_t *h_tok_off) {
+    if (!c) raise(MRG_EINVAL, "null context");
+    if (!v) raise(MRG_EINVAL, "null vocabulary");
+    if (!h_doc_off || !h_tok_off) raise(MRG_EINVAL, "null offsets (h_doc_off and h_tok_off need n_docs + 1 entries)");
+    if (v->device != c->device) raise(MRG_EINVAL, "the vocabulary lives on device %d, the context on device %d", v->device,
+                                      c->device);
+    if (n_docs == 0xFFFFFFFFu) raise(MRG_EINVAL, "n_docs out of range");
+    if ((uintptr_t)d_bytes & 15u) raise(MRG_EINVAL, "input buffer must be 16-byte aligned");
+    for (uint32_t i = 0; i < n_docs; ++i)
+        if (h_doc_off[i + 1] < h_doc_off[i]) raise(MRG_EINVAL, "document offsets must be non-decreasing");
+    HIPCHK(hipSetDevice(c->device));
+    memset(c->enc_info, 0, sizeof c->enc_info);
+    c->enc_ms[0] = c->enc_ms[1] = c->enc_ms[2] = 0.0;
+    const uint64_t lo0 = h_doc_off[0], hi0 = h_doc_off[n_docs];
+    if (hi0 == lo0) {  // no bytes: no tokens
+        for (uint32_t i = 0; i <= n_docs; ++i) h_tok_off[i] = 0;
+        return;
+    }
+    if (!d_bytes) raise(MRG_EINVAL, "null input");
+    Pool &p = c->pool;
+    hipStream_t s = c->stream;
+    Scratch sc(p);
+    enc_events(c);
+    // positions relative to the 1 KiB boundary at or below the first document
+    const uint64_t shift = lo0 & ~1023ull;
+    std::vector<uint64_t> rel(h_doc_off, h_doc_off + n_docs + 1);
+    for (auto &x : rel) x -= shift;
+    EncPlan P{};
+    P.in = d_bytes + shift;
+    P.lo = lo0 - shift;
+    P.hi = hi0 - shift;
+    P.ntiles = (P.hi + 1023) >> 10;
+    P.n_docs = n_docs;
+    const uint64_t bw = mrg_enc_bitmap_words(P.ntiles);
+    P.bnd = sc.get<uint32_t>(bw);
+    uint64_t *d_off = sc.get<uint64_t>((uint64_t)n_docs + 1);
+    P.doc_off = d_off;
+    P.cnt = sc.get<uint64_t>(P.ntiles + 1);
+    P.tok_off = sc.get<uint64_t>((uint64_t)n_docs + 1);
+    uint64_t *stmp = sc.get<uint64_t>(mrg_scan_tmp_elems(P.ntiles + 1));
+    unsigned long long *small = sc.get<unsigned long long>(9);  // err, info[8]
+    P.err = small;
+    P.info = small + 1;
+    c->enc_info[5] = hi0 - lo0;
+    c->enc_info[6] = 4 * bw + 8 * (P.ntiles + 1) + 16 * ((uint64_t)n_docs + 1) + 8 * mrg_scan_tmp_elems(P.ntiles + 1) + 72;
+    HIPCHK(hipMemcpyAsync(d_off, rel.data(), 8 * ((uint64_t)n_docs + 1), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(P.bnd, 0, 4 * bw, s));
+    HIPCHK(hipMemsetAsync(P.cnt, 0, 8 * (P.ntiles + 1), s));
+    HIPCHK(hipMemsetAsync(P.err, 0xFF, 8, s));
+    HIPCHK(hipMemsetAsync(P.info, 0, 64, s));
+    mrg_enc_launch_bounds(P, s);
+    enc_rec(c, 0);
+    mrg_enc_launch_count(P, v->T, s);
+    enc_rec(c, 1);
+    mrg_scan_u64(P.cnt, P.cnt, P.ntiles + 1, stmp, s);
+    mrg_enc_launch_offsets(P, v->T, s);
+    enc_rec(c, 2);
+    HIPCHK(hipGetLastError());
+    unsigned long long herr = 0;
+    HIPCHK(hipMemcpyAsync(h_tok_off, P.tok_off, 8 * ((uint64_t)n_docs + 1), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&herr, P.err, 8, hipMemcpyDeviceToHost, s));
+    sync(c);  // (also: the pageable `rel` has been read)
+    c->enc_ms[0] = enc_ms(c, 0, 1);
+    c->enc_ms[1] = enc_ms(c, 1, 2);
+    if (herr != ~0ull) {
+        uint32_t d = 0;
+        while (d + 1 < n_docs && rel[d + 1] <= herr) ++d;
+        raise(MRG_EUTF8, "stream did not contain valid UTF-8: document %u, byte offset %llu", d,
+              (unsigned long long)(herr - rel[d]));
+    }
+    const uint64_t total = h_tok_off[n_docs];
+    if (d_ids) {
+        if (cap_ids < total) raise(MRG_EINVAL, "destination too small (%llu ids < %llu tokens)", (unsigned long long)cap_ids,
+                                   (unsigned long long)total);
+        P.out = d_ids;
+        P.out_n = total;
+        enc_rec(c, 2);
+        if (total) mrg_enc_launch_emit(P, v->T, s);
+        enc_rec(c, 3);
+        HIPCHK(hipGetLastError());
+    }
+    unsigned long long hinfo[8] = {};
+    HIPCHK(hipMemcpyAsync(hinfo, P.info, 64, hipMemcpyDeviceToHost, s));
+    sync(c);
+    if (d_ids) c->enc_ms[2] = enc_ms(c, 2, 3);
+    for (int i = 0; i < 5; ++i) c->enc_info[i] = hinfo[i];
+    if (!d_ids) c->enc_info[0] = total;
 }
 
 void export_sizes(mrg_ctx *c, uint32_t n_owners, uint64_t *h_rec, uint64_t *h_heap) {
@@ -2973,6 +3207,8 @@ int mrg_close(mrg_ctx *c) {
         (void)hipSetDevice(c->device);
         (void)hipStreamSynchronize(c->stream);
         for (auto &e : c->ev) (void)hipEventDestroy(e);
+        for (auto &e : c->enc_ev)
+            if (e) (void)hipEventDestroy(e);
         (void)hipFree(c->d_cnt);
         (void)hipHostFree(c->h_cnt);
         if (c->h_stage) (void)hipHostFree(c->h_stage);
@@ -3132,6 +3368,53 @@ int mrg_job_copy_topk(mrg_ctx *c, uint8_t *h_dst, uint64_t cap) {
             HIPCHK(hipMemcpyAsync(h_dst, c->d_top, c->top_bytes, hipMemcpyDeviceToHost, c->stream));
         }
         sync(c);
+    });
+}
+
+int mrg_job_vocab(mrg_ctx *c, uint64_t max_words, uint64_t min_count, mrg_vocab **out) {
+    if (out) *out = nullptr;
+    return guard([&] {
+        if (!out) raise(MRG_EINVAL, "null out");
+        *out = job_vocab(c, max_words, min_count);
+    });
+}
+
+int mrg_vocab_size(const mrg_vocab *v, uint64_t *n_words, uint64_t *text_bytes) {
+    return guard([&] {
+        if (!v) raise(MRG_EINVAL, "null vocabulary");
+        if (n_words) *n_words = v->n;
+        if (text_bytes) *text_bytes = v->text_bytes;
+    });
+}
+
+int mrg_vocab_copy_text(const mrg_vocab *v, uint8_t *h_dst, uint64_t cap) {
+    return guard([&] {
+        if (!v) raise(MRG_EINVAL, "null vocabulary");
+        if (cap < v->text_bytes) raise(MRG_EINVAL, "destination too small (%llu < %llu)", (unsigned long long)cap,
+                                       (unsigned long long)v->text_bytes);
+        if (!v->text_bytes) return;
+        if (!h_dst) raise(MRG_EINVAL, "null argument");
+        HIPCHK(hipSetDevice(v->device));
+        HIPCHK(hipMemcpy(h_dst, v->T.text, v->text_bytes, hipMemcpyDeviceToHost));
+    });
+}
+
+void mrg_vocab_free(mrg_vocab *v) { vocab_destroy(v); }
+
+int mrg_vocab_encode(mrg_ctx *c, const mrg_vocab *v, const uint8_t *d_bytes, const uint64_t *h_doc_off, uint32_t n_docs,
+                     uint32_t *d_ids, uint64_t cap_ids, uint64_t *h_tok_off) {
+    return guard([&] { vocab_encode(c, v, d_bytes, h_doc_off, n_docs, d_ids, cap_ids, h_tok_off); });
+}
+
+// Diagnostics of the last mrg_vocab_encode (not in include/mrgpu.h; tools/time_encode.py): h_info[0..7) =
+// tokens, UNK tokens, long tokens, non-ASCII 1 KiB chunks, table probes, input bytes, scratch bytes;
+// h_ms[0..4) = count pass, scan + document offsets, emit pass, and the last mrg_job_vocab (HIP events,
+// with mrg_set_timing).
+int mrg_encode_info(mrg_ctx *c, uint64_t *h_info, double *h_ms) {
+    return guard([&] {
+        if (!c) raise(MRG_EINVAL, "null context");
+        if (h_info) memcpy(h_info, c->enc_info, sizeof c->enc_info);
+        if (h_ms) memcpy(h_ms, c->enc_ms, sizeof c->enc_ms);
     });
 }
 

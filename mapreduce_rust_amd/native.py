@@ -16,6 +16,7 @@ FLAG_FINAL_TXT = 0x2
 FLAG_STREAM = 0x4  # run_job only: map each GPU's files in batches while the next batch is read
 XREC_BYTES = 24  # include/mrgpu.h MRG_XREC_BYTES (ABI 3)
 ABI_VERSION = 6  # include/mrgpu.h MRG_ABI_VERSION
+ID_UNK = 0xFFFFFFFF  # MRG_ID_UNK: mrg_vocab_encode's id of a word that is not in the vocabulary
 
 OK, EINVAL, EUTF8, EHIP, ENOMEM, EIO, ECOMM = 0, -1, -2, -3, -4, -5, -6
 _CODES = {EINVAL: "EINVAL", EUTF8: "EUTF8", EHIP: "EHIP", ENOMEM: "ENOMEM", EIO: "EIO", ECOMM: "ECOMM"}
@@ -109,6 +110,11 @@ _SIGS = {
     "mrg_job_copy_final": (C.c_int, [_vp, _vp, C.c_uint64]),
     "mrg_job_topk": (C.c_int, [_vp, C.c_uint64, C.POINTER(_vp), _u64p, _u64p]),
     "mrg_job_copy_topk": (C.c_int, [_vp, _vp, C.c_uint64]),
+    "mrg_job_vocab": (C.c_int, [_vp, C.c_uint64, C.c_uint64, C.POINTER(_vp)]),
+    "mrg_vocab_size": (C.c_int, [_vp, _u64p, _u64p]),
+    "mrg_vocab_copy_text": (C.c_int, [_vp, _vp, C.c_uint64]),
+    "mrg_vocab_free": (None, [_vp]),
+    "mrg_vocab_encode": (C.c_int, [_vp, _vp, _vp, _u64p, C.c_uint32, _vp, C.c_uint64, _u64p]),
     "mrg_map": (C.c_int, [_vp, C.c_int, C.c_char_p, C.c_size_t, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32,
                           C.POINTER(_vp)]),
     "mrg_parts_get": (C.c_int, [_vp, C.c_uint32, C.POINTER(_vp), _u64p, C.POINTER(_vp), _u64p]),
@@ -195,6 +201,48 @@ class Parts:
     def __del__(self):
         try:
             self.free()
+        except Exception:
+            pass
+
+
+class Vocab:
+    """mrg_vocab: the most frequent words of a job as ids 0..n-1 (Context.vocab).  Owns its device
+    memory; outlives the job and the context that made it."""
+
+    def __init__(self, handle):
+        self.h = handle
+
+    def size(self):
+        """(words, bytes of the "word count\\n" text)"""
+        n, b = C.c_uint64(), C.c_uint64()
+        _check(load().mrg_vocab_size(self.h, C.byref(n), C.byref(b)))
+        return n.value, b.value
+
+    def text(self):
+        """The "word count\\n" lines in id order (bytes)."""
+        _, nb = self.size()
+        buf = C.create_string_buffer(max(nb, 1))
+        _check(load().mrg_vocab_copy_text(self.h, buf, nb))
+        return buf.raw[:nb]
+
+    def words(self):
+        """The words in id order (list of bytes)."""
+        return [ln.rsplit(b" ", 1)[0] for ln in self.text().split(b"\n") if ln]
+
+    def close(self):
+        if self.h:
+            load().mrg_vocab_free(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
         except Exception:
             pass
 
@@ -356,6 +404,36 @@ class Context:
         _check(f(self.h, info, pb))
         return {"n": info[0], "candidates": info[1], "passes": info[2], "dropped": info[3],
                 "pass_bytes": [b for b in pb if b]}
+
+    def vocab(self, max_words=0, min_count=1):
+        """mrg_job_vocab: the job's max_words (0: all) most frequent words with at least min_count
+        occurrences, as a Vocab whose ids are the ranks of topk(max_words); wc only."""
+        h = _vp()
+        _check(load().mrg_job_vocab(self.h, max_words, min_count, C.byref(h)))
+        return Vocab(h)
+
+    def encode(self, vocab, dev_ptr, doc_off, out_ptr=None, cap=0):
+        """mrg_vocab_encode: the tokens of every document (layout of set_input) as vocabulary ids, in
+        input order, into the device buffer out_ptr of cap uint32 (None: count only).  Returns tok_off:
+        document i's ids are out[tok_off[i]:tok_off[i + 1]]; ID_UNK marks words not in the vocabulary."""
+        if len(doc_off) < 1:
+            raise ValueError("doc_off needs n_docs + 1 entries (at least [0])")
+        n = len(doc_off) - 1
+        tok = (C.c_uint64 * (n + 1))()
+        _check(load().mrg_vocab_encode(self.h, vocab.h, dev_ptr, _u64arr(doc_off), n, out_ptr, cap, tok))
+        return list(tok)
+
+    def encode_info(self):
+        """Diagnostics of the last encode(): tokens, UNK and long tokens, non-ASCII 1 KiB chunks, table
+        probes, input and scratch bytes; HIP-event ms per pass and of the last vocab() (with set_timing)."""
+        f = load().mrg_encode_info
+        f.restype = C.c_int
+        f.argtypes = [_vp, _u64p, C.POINTER(C.c_double)]
+        info, ms = (C.c_uint64 * 8)(), (C.c_double * 4)()
+        _check(f(self.h, info, ms))
+        return {"tokens": info[0], "unk": info[1], "long_tokens": info[2], "nonascii_chunks": info[3],
+                "probes": info[4], "input_bytes": info[5], "scratch_bytes": info[6], "ms_count": ms[0],
+                "ms_offsets": ms[1], "ms_emit": ms[2], "ms_vocab": ms[3]}
 
     # ---- plugin surface (host buffers)
     def map_task(self, app, data, doc, doc_id, n_reduce, flags=0):

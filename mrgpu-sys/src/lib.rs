@@ -31,6 +31,8 @@ pub const fn mrg_flag_debug_hash_bits(n: u32) -> u32 {
 pub const fn mrg_flag_top(k: u32) -> u32 {
     (k & 0xFFFF) << 16
 }
+/// `mrg_vocab_encode`: the id of a word that is not in the vocabulary.
+pub const MRG_ID_UNK: u32 = 0xFFFF_FFFF;
 pub const MRG_XREC_BYTES: usize = 24;
 pub const MRG_ABI_VERSION: u32 = 6;
 pub const MRG_COMM_ID_BYTES: usize = 128;
@@ -45,6 +47,11 @@ pub struct mrg_parts {
 }
 #[repr(C)]
 pub struct mrg_comm {
+    _p: [u8; 0],
+}
+/// A frozen word -> id table made by `mrg_job_vocab`; owns its device memory.
+#[repr(C)]
+pub struct mrg_vocab {
     _p: [u8; 0],
 }
 
@@ -121,6 +128,11 @@ extern "C" {
     pub fn mrg_job_copy_final(ctx: *mut mrg_ctx, h_dst: *mut u8, cap: u64) -> c_int;
     pub fn mrg_job_topk(ctx: *mut mrg_ctx, k: u64, d_out: *mut *const u8, h_bytes: *mut u64, h_lines: *mut u64) -> c_int;
     pub fn mrg_job_copy_topk(ctx: *mut mrg_ctx, h_dst: *mut u8, cap: u64) -> c_int;
+    pub fn mrg_job_vocab(ctx: *mut mrg_ctx, max_words: u64, min_count: u64, out: *mut *mut mrg_vocab) -> c_int;
+    pub fn mrg_vocab_size(v: *const mrg_vocab, n_words: *mut u64, text_bytes: *mut u64) -> c_int;
+    pub fn mrg_vocab_copy_text(v: *const mrg_vocab, h_dst: *mut u8, cap: u64) -> c_int;
+    pub fn mrg_vocab_free(v: *mut mrg_vocab);
+    pub fn mrg_vocab_encode(ctx: *mut mrg_ctx, v: *const mrg_vocab, d_bytes: *const u8, h_doc_off: *const u64, n_docs: u32, d_ids: *mut u32, cap_ids: u64, h_tok_off: *mut u64) -> c_int;
 
     pub fn mrg_comm_get_id(id: *mut u8) -> c_int;
     pub fn mrg_comm_init(ctx: *mut mrg_ctx, id: *const u8, n_ranks: c_int, rank: c_int,
