@@ -119,7 +119,8 @@ typedef struct {
  * (6, additive): mrg_job_map_add, MRG_FLAG_STREAM, mrg_run_get_stream_stats; mrg_stats.reserved is now
  * map_batches (same size and offset)
  * (6, additive): mrg_job_vocab, mrg_vocab_size, mrg_vocab_copy_text, mrg_vocab_free, mrg_vocab_encode,
- * MRG_ID_UNK */
+ * MRG_ID_UNK
+ * (6, additive): mrg_vocab_from_text, mrg_vocab_decode */
 #define MRG_ABI_VERSION 6
 
 const char *mrg_last_error(void);
@@ -231,6 +232,51 @@ void mrg_vocab_free(mrg_vocab *v);
  * ends; on return the ids are complete and the caller may free or overwrite the input. */
 int mrg_vocab_encode(mrg_ctx *ctx, const mrg_vocab *v, const uint8_t *d_bytes, const uint64_t *h_doc_off,
                      uint32_t n_docs, uint32_t *d_ids, uint64_t cap_ids, uint64_t *h_tok_off);
+
+/* A vocabulary from its text, on any device.  h_text is host memory holding `bytes` bytes of
+ * "word count\n" lines: what mrg_vocab_copy_text returns, or the top.txt or final.txt of a word-count
+ * mrg_run_job (so the whole ranking of a multi-GPU job, which no single context holds, becomes a
+ * vocabulary this way).  The word on line i (0-based) gets id i; the lines need not be ordered by count
+ * (a final.txt, in key order, gives ids in key order).  The result is an ordinary mrg_vocab on ctx's
+ * device with the ownership and lifetime rules above: one device allocation of its own, it survives
+ * mrg_job_begin and mrg_close, it is read-only and any context of that device may use it from several
+ * threads.  mrg_vocab_copy_text of it returns h_text byte for byte; mrg_vocab_size returns (lines,
+ * bytes).  The call needs no job and touches no job state; its scratch comes from the context's pool
+ * and is all returned before it ends.  Of `flags` only the MRG_FLAG_DEBUG_HASH_BITS(n) bits are read
+ * (the role the job's flags play for mrg_job_vocab); any other bit set: MRG_EINVAL.  bytes = 0 gives
+ * the valid empty vocabulary (h_text may then be NULL).  More than 0xFFFFFFFE lines: MRG_EINVAL.
+ * Validation -- MRG_EINVAL unless stated, mrg_last_error names the 0-based line ("line N"), *out is
+ * NULL, nothing is leaked, the context and every other vocabulary stay usable:
+ *   - the text is empty or ends in '\n';
+ *   - every line is `word`, one ' ', then 1 to 20 ASCII digits (the count is not interpreted further):
+ *     an empty line, a missing count or a second space is an error; the word is not empty;
+ *   - the word is valid UTF-8 (else MRG_EUTF8, with the line named, as the map reports it);
+ *   - every codepoint of the word is \w by the map's tables, i.e. the word is accepted exactly when
+ *     wc::map over it produces that word as its single key (don't, a-dash-b and "a b" are rejected);
+ *   - no word stands on two lines ("duplicate", naming a line whose word also stands on another one);
+ *     words longer than 16 bytes are compared byte for byte, under MRG_FLAG_DEBUG_HASH_BITS too. */
+int mrg_vocab_from_text(mrg_ctx *ctx, const uint8_t *h_text, uint64_t bytes, uint32_t flags, mrg_vocab **out);
+/* Ids -> text, the inverse of mrg_vocab_encode with the same document layout: document i's ids are
+ * d_ids[h_tok_off[i] .. h_tok_off[i+1]) (d_ids: device memory, 4-byte aligned; h_tok_off: n_docs + 1
+ * non-decreasing entries).  Every id becomes its word's bytes followed by one separator byte: ' '
+ * inside a document, '\n' after the document's last id; an empty document produces no bytes.
+ * Document i's text is d_out[h_out_off[i] .. h_out_off[i+1]); h_out_off has n_docs + 1 entries and
+ * h_out_off[0] = 0.  Encoding d_out with h_out_off as document offsets returns the original ids and
+ * offsets, as long as the UNK bytes are \w-only and not a word of the vocabulary.
+ * MRG_ID_UNK is written as the unk_len (0..255) bytes at h_unk (host memory, not validated); with
+ * unk_len = 0 an MRG_ID_UNK is an error, as is any other id >= the vocabulary's words: MRG_EINVAL,
+ * mrg_last_error names the index in d_ids of the first such id ("index N"), d_out is then unspecified,
+ * the context and the vocabulary stay usable.
+ * d_out = NULL: sizes only -- h_out_off is filled, nothing is written.  Otherwise cap (bytes) <
+ * h_out_off[n_docs] returns MRG_EINVAL with d_out untouched.  n_docs = 0 or no ids: all-zero offsets,
+ * MRG_OK.  A vocabulary of another device: MRG_EINVAL.
+ * The call needs no job and touches no job state (it is legal between mrg_job_map_add batches).  It
+ * runs on the context's stream with scratch from the context's pool (about 1/8 byte per id for the
+ * boundary bitmap plus 8 bytes per 256 ids), all returned before the call ends; on return the text is
+ * complete. */
+int mrg_vocab_decode(mrg_ctx *ctx, const mrg_vocab *v, const uint32_t *d_ids, const uint64_t *h_tok_off,
+                     uint32_t n_docs, const uint8_t *h_unk, uint32_t unk_len, uint8_t *d_out, uint64_t cap,
+                     uint64_t *h_out_off);
 
 /* ---- multi-GPU: one rank per GPU, the shuffle as an RCCL all-to-all over xGMI ----
  * The reference moves map output to the reduce workers through mr-{m}-{r}.txt files in a shared

@@ -8,6 +8,10 @@
 //                              (no packed key holds a 0xFF byte), identity = byte compare against the
 //                              vocabulary's own text at line_off[id]
 // MRG_FLAG_DEBUG_HASH_BITS truncates the slot hash and the long words' stored hash.
+// mrg_vocab_from_text builds the same object from "word count\n" text: k_voc_check (one lane per line:
+// the line's form, the word's UTF-8 and \w classes, its length), the same build, then k_voc_verify (every
+// word looked up again must find its own line: a word on two lines does not).  k_voc_words fills the
+// id-indexed packed words that k_decode.hip reads.
 //
 // Encode (mrg_vocab_encode): tokens exactly as wc::map makes them (src/app/wc.rs:6-13), in input order.
 // One wave per 1 KiB chunk, 16 bytes per lane (one 16-byte load).  Three launches of the same chunk
@@ -165,6 +169,19 @@ __global__ __launch_bounds__(ENC_WG) void k_voc_insert(VocTable T, const uint32_
             slot = (slot + probe + 1u) & (T.cap - 1);
         }
         if (!placed) atomicAdd(fail, 1ull);
+    }
+}
+
+// The id-indexed packed words of mrg_vocab_decode: the first 16 bytes of word i as (k0, k1).
+__global__ __launch_bounds__(ENC_WG) void k_voc_words(VocTable T, VocWords W) {
+    const uint64_t i = (uint64_t)blockIdx.x * ENC_WG + threadIdx.x;
+    if (i < T.n) {
+        const uint8_t *w = T.text + T.line_off[i];
+        const uint32_t L = min(W.wlen[i], 16u);
+        uint64_t k0 = 0, k1 = 0;
+        for (uint32_t j = 0; j < L; ++j) mrg_key_append(k0, k1, j, w[j]);
+        W.pk[2 * i] = k0;
+        W.pk[2 * i + 1] = k1;
     }
 }
 
@@ -577,6 +594,66 @@ __global__ __launch_bounds__(ENC_WG) void k_enc(EncArgs A, VocTable T) {
     }
 }
 
+// ---------------------------------------------------------------- vocabulary from text
+// Line i = text[line_off[i], line_off[i + 1]), the last byte its '\n' (the host cut the lines there):
+// `word`, one ' ', 1 to 20 ASCII digits; the word non-empty, valid UTF-8, every codepoint \w.  One lane
+// per line; the first bad line wins by atomicMin on line * 4 + reason.
+__global__ __launch_bounds__(ENC_WG) void k_voc_check(VocTable T, uint32_t *wlen, unsigned long long *err) {
+    const uint64_t i = (uint64_t)blockIdx.x * ENC_WG + threadIdx.x;
+    if (i >= T.n) return;
+    const uint64_t lo = T.line_off[i], hi = T.line_off[i + 1] - 1u;  // [lo, hi): the line without its '\n'
+    const uint8_t *t = T.text;
+    uint64_t sp = lo;
+    while (sp < hi && t[sp] != 0x20u) ++sp;
+    const uint64_t nd = hi > sp ? hi - sp - 1u : 0u;  // bytes after the space
+    bool form = sp > lo && sp < hi && nd >= 1u && nd <= 20u;
+    for (uint64_t q = sp + 1u; form && q < hi; ++q) form = (uint32_t)t[q] - '0' < 10u;
+    uint32_t bad = form ? 3u : MRG_VOC_BAD_FORM;
+    if (form) {
+        auto rd = [&](uint64_t x) -> uint32_t { return t[x]; };
+        for (uint64_t p = lo; p < sp;) {
+            uint32_t cp, raw;
+            const int l = mrg_utf8_decode(rd, p, sp, &cp, &raw);
+            if (!l) {
+                bad = MRG_VOC_BAD_UTF8;
+                break;
+            }
+            if (mrg_uclass(cp) != MRG_CLS_W) {
+                bad = MRG_VOC_BAD_CLASS;
+                break;
+            }
+            p += (uint64_t)l;
+        }
+    }
+    wlen[i] = bad == 3u ? (uint32_t)(sp - lo) : 0u;
+    if (bad != 3u) atomicMin(err, (unsigned long long)(i * 4u + bad));
+}
+
+// Word i looked up in the finished table must find id i: a word that stands on two lines finds the
+// other line from at least one of them.  Long candidates are compared byte for byte.
+__global__ __launch_bounds__(ENC_WG) void k_voc_verify(VocTable T, const uint32_t *wlen, unsigned long long *dup) {
+    const uint64_t i = (uint64_t)blockIdx.x * ENC_WG + threadIdx.x;
+    if (i >= T.n) return;
+    const uint8_t *w = T.text + T.line_off[i];
+    const uint32_t L = wlen[i];
+    VocKey kb;
+    for (uint32_t j = 0; j < L; ++j) kb.push(w[j]);
+    uint32_t probes = 0, id;
+    if (L <= 16u) {
+        id = voc_find(T, kb.k0, kb.k1, false, [](uint32_t) { return true; }, probes);
+    } else {
+        auto same = [&](uint32_t cand) -> bool {
+            if (wlen[cand] != L) return false;
+            const uint8_t *x = T.text + T.line_off[cand];
+            bool eq = true;
+            for (uint32_t j = 0; j < L && eq; ++j) eq = x[j] == w[j];
+            return eq;
+        };
+        id = voc_find(T, kb.long_a(T.hash_bits), kb.long_b(), true, same, probes);
+    }
+    if (id != (uint32_t)i) atomicMin(dup, (unsigned long long)i);
+}
+
 // bit p of the boundary bitmap for every document offset (the end of the input included)
 __global__ __launch_bounds__(ENC_WG) void k_enc_bounds(const uint64_t *doc_off, uint32_t n_docs, uint32_t *bnd) {
     const uint64_t i = (uint64_t)blockIdx.x * ENC_WG + threadIdx.x;
@@ -595,6 +672,16 @@ void mrg_voc_launch_lines(const SortRec *top, uint64_t m, KeySet ks, uint64_t mi
 void mrg_voc_launch_build(const VocTable &t, const uint32_t *wlen, unsigned long long *fail, hipStream_t s) {
     hipLaunchKernelGGL(k_voc_clear, dim3(grid_for(t.cap)), dim3(ENC_WG), 0, s, t);
     if (t.n) hipLaunchKernelGGL(k_voc_insert, dim3(grid_for(t.n)), dim3(ENC_WG), 0, s, t, wlen, fail);
+}
+
+void mrg_voc_launch_words(const VocTable &t, const VocWords &w, hipStream_t s) {
+    if (t.n) hipLaunchKernelGGL(k_voc_words, dim3(grid_for(t.n)), dim3(ENC_WG), 0, s, t, w);
+}
+void mrg_voc_launch_check(const VocTable &t, uint32_t *wlen, unsigned long long *err, hipStream_t s) {
+    if (t.n) hipLaunchKernelGGL(k_voc_check, dim3(grid_for(t.n)), dim3(ENC_WG), 0, s, t, wlen, err);
+}
+void mrg_voc_launch_verify(const VocTable &t, const uint32_t *wlen, unsigned long long *dup, hipStream_t s) {
+    if (t.n) hipLaunchKernelGGL(k_voc_verify, dim3(grid_for(t.n)), dim3(ENC_WG), 0, s, t, wlen, dup);
 }
 
 uint64_t mrg_enc_bitmap_words(uint64_t ntiles) { return ntiles * 32u + 8u; }

@@ -558,6 +558,48 @@ void mrg_enc_launch_bounds(const EncPlan &p, hipStream_t s);
 void mrg_enc_launch_count(const EncPlan &p, const VocTable &t, hipStream_t s);    // fills cnt, err, info[3]
 void mrg_enc_launch_offsets(const EncPlan &p, const VocTable &t, hipStream_t s);  // after the scan of cnt
 void mrg_enc_launch_emit(const EncPlan &p, const VocTable &t, hipStream_t s);
+// The id-indexed side of a vocabulary (mrg_vocab_decode): wlen[i] = bytes of word i, pk[2 i], pk[2 i + 1]
+// = its first 16 bytes as the table packs them (k0, k1).
+struct VocWords {
+    uint32_t *wlen;              // [n]
+    uint64_t *pk;                // [2 n], 16-byte aligned
+};
+// pk of words [0, t.n) from t.text and w.wlen
+void mrg_voc_launch_words(const VocTable &t, const VocWords &w, hipStream_t s);
+// mrg_vocab_from_text: line i of t.text is [t.line_off[i], t.line_off[i + 1]), its '\n' included.  Checks
+// the form "word count\n" and the word's codepoints, writes wlen[i]; *err (all ones) = min over the bad
+// lines of line * 4 + reason (MRG_VOC_BAD_*).
+#define MRG_VOC_BAD_FORM 0u      // not `word`, one ' ', 1..20 ASCII digits
+#define MRG_VOC_BAD_UTF8 1u
+#define MRG_VOC_BAD_CLASS 2u     // a codepoint that is not \w
+void mrg_voc_launch_check(const VocTable &t, uint32_t *wlen, unsigned long long *err, hipStream_t s);
+// after the build: word i must find id i; *dup (all ones) = the smallest line whose word finds another
+void mrg_voc_launch_verify(const VocTable &t, const uint32_t *wlen, unsigned long long *dup, hipStream_t s);
+
+// ---- k_decode.hip: ids -> text
+// One decode call.  Positions are id indices from `in` (16-byte aligned); the documents' ids are
+// [lo, hi) with lo < 4; nchunks = chunks of MRG_DEC_CHUNK ids over [0, hi).
+#define MRG_DEC_CHUNK 256u
+struct DecPlan {
+    const uint32_t *in;
+    uint64_t lo, hi, nchunks;
+    uint32_t *bnd;               // [mrg_dec_bitmap_words(nchunks)] zeroed: bit p = id p is its document's last
+    const uint64_t *tok_off;     // [n_docs + 1] device copy of the offsets (relative to `in`)
+    uint32_t n_docs;
+    uint64_t *cnt;               // [nchunks + 1] zeroed: output bytes per chunk, then (scanned in place) chunk bases
+    uint64_t *out_off;           // [n_docs + 1]
+    uint8_t *out;                // the text (emit only)
+    uint64_t out_n;              // its bytes (out_off[n_docs])
+    unsigned long long *err;     // all ones: position of the first id that is not in the vocabulary
+    uint32_t unk_len;            // bytes written for MRG_ID_UNK (0: such an id is an error)
+    uint64_t unk_k0, unk_k1;     // unk_len <= 16: the bytes, packed as a key
+    const uint8_t *unk;          // unk_len > 16: the bytes, on the device
+};
+uint64_t mrg_dec_bitmap_words(uint64_t nchunks);
+void mrg_dec_launch_bounds(const DecPlan &p, hipStream_t s);
+void mrg_dec_launch_count(const DecPlan &p, const VocTable &t, const VocWords &w, hipStream_t s);    // fills cnt, err
+void mrg_dec_launch_offsets(const DecPlan &p, const VocTable &t, const VocWords &w, hipStream_t s);  // after the scan of cnt
+void mrg_dec_launch_emit(const DecPlan &p, const VocTable &t, const VocWords &w, hipStream_t s);
 
 // ---- k_gen.hip
 int mrg_gen_zipf_impl(uint8_t *dst, uint64_t n, uint64_t seed, uint64_t file_index, uint32_t vocab, double s, uint32_t style,

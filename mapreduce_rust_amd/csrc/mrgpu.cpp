@@ -395,15 +395,22 @@ struct mrg_ctx {
     uint64_t enc_info[8] = {};
     double enc_ms[4] = {};
     hipEvent_t enc_ev[6] = {};      // created on first use
+    // last mrg_vocab_decode (mrg_decode_info): ids, output bytes, chunks, scratch bytes; ms of the count,
+    // offsets (scan + boundaries) and emit passes, and of the last mrg_vocab_from_text (with mrg_set_timing)
+    uint64_t dec_info[8] = {};
+    double dec_ms[4] = {};
+    hipEvent_t dec_ev[6] = {};      // created on first use
 };
 
-// A vocabulary (mrg_job_vocab): one device allocation of its own -- the ranked "word count\n" lines, the
-// byte offset of every line, and the word -> id table over them (k_encode.hip).  Read-only once built.
+// A vocabulary (mrg_job_vocab, mrg_vocab_from_text): one device allocation of its own -- the "word count\n"
+// lines in id order, the byte offset of every line, the word -> id table over them (k_encode.hip), and
+// the id-indexed word lengths and packed words of the decoder (k_decode.hip).  Read-only once built.
 struct mrg_vocab {
     int device = 0;
     uint64_t n = 0, text_bytes = 0;
     void *block = nullptr;
     VocTable T{};
+    VocWords W{};
 };
 
 struct mrg_comm {
@@ -2487,6 +2494,61 @@ void vocab_destroy(mrg_vocab *v) {
     delete v;
 }
 
+struct VocDel {
+    void operator()(mrg_vocab *v) const { vocab_destroy(v); }
+};
+using VocPtr = std::unique_ptr<mrg_vocab, VocDel>;
+
+// The block of a vocabulary of n words over text_bytes of text, laid out and allocated; nothing in it is
+// written yet except line_off[0] of the empty vocabulary.  Layout: text | line_off | table k0, k1, id |
+// wlen | packed words (the last two are the decoder's: the encoder's part is as it was).
+VocPtr vocab_alloc(mrg_ctx *c, uint64_t n, uint64_t text_bytes, uint32_t hbits) {
+    if (n > 0xFFFFFFFEull) raise(MRG_EINVAL, "vocabulary of %llu words: ids are 32 bits", (unsigned long long)n);
+    VocPtr v(new mrg_vocab());
+    v->device = c->device;
+    v->n = n;
+    v->text_bytes = text_bytes;
+    const uint64_t cap = pow2_at_least(2 * n);
+    auto up = [](uint64_t x) { return (x + 255) & ~255ull; };
+    const uint64_t o_text = 0, o_loff = o_text + up(text_bytes + 16), o_k0 = o_loff + up(8 * (n + 1)),
+                   o_k1 = o_k0 + 8 * cap, o_id = o_k1 + 8 * cap, o_wlen = o_id + 4 * cap, o_pk = o_wlen + up(4 * n),
+                   total = o_pk + up(16 * n);
+    if (hipMalloc(&v->block, total) != hipSuccess) {
+        (void)hipGetLastError();
+        v->block = nullptr;
+        raise(MRG_ENOMEM, "vocabulary: device allocation of %llu bytes failed", (unsigned long long)total);
+    }
+    uint8_t *blk = (uint8_t *)v->block;
+    VocTable &T = v->T;
+    T.k0 = (uint64_t *)(blk + o_k0);
+    T.k1 = (uint64_t *)(blk + o_k1);
+    T.id = (uint32_t *)(blk + o_id);
+    T.cap = cap;
+    T.hash_bits = hbits;
+    T.text = blk + o_text;
+    T.line_off = (const uint64_t *)(blk + o_loff);
+    T.n = n;
+    v->W.wlen = (uint32_t *)(blk + o_wlen);
+    v->W.pk = (uint64_t *)(blk + o_pk);
+    if (!n) HIPCHK(hipMemsetAsync(blk + o_loff, 0, 8, c->stream));
+    return v;
+}
+
+// The table and the packed words over the block's text, line offsets and word lengths (enqueued before);
+// waits for the build.
+void vocab_build(mrg_ctx *c, mrg_vocab *v, Scratch &sc) {
+    hipStream_t s = c->stream;
+    unsigned long long *fail = sc.get<unsigned long long>(1);
+    HIPCHK(hipMemsetAsync(fail, 0, 8, s));
+    mrg_voc_launch_build(v->T, v->W.wlen, fail, s);
+    mrg_voc_launch_words(v->T, v->W, s);
+    HIPCHK(hipGetLastError());
+    unsigned long long hfail = 0;
+    HIPCHK(hipMemcpyAsync(&hfail, fail, 8, hipMemcpyDeviceToHost, s));
+    sync(c);
+    if (hfail) raise(MRG_EHIP, "vocabulary: %llu words found no table slot", hfail);
+}
+
 // The vocabulary of the job's keys: mrg_job_topk's ranked lines, cut at
 // min_count, copied with their line offsets into one allocation of the vocabulary's own, and the
 // word -> id table over that copy.
@@ -2520,45 +2582,14 @@ mrg_vocab *job_vocab(mrg_ctx *c, uint64_t max_words, uint64_t min_count) {
         sync(c);
         if (text_bytes > c->top_bytes) raise(MRG_EHIP, "vocabulary: line offsets exceed the ranked text");
     }
-    if (n > 0xFFFFFFFEull) raise(MRG_EINVAL, "vocabulary of %llu words: ids are 32 bits", (unsigned long long)n);
-    struct Del {
-        void operator()(mrg_vocab *v) const { vocab_destroy(v); }
-    };
-    std::unique_ptr<mrg_vocab, Del> v(new mrg_vocab());
-    v->device = c->device;
-    v->n = n;
-    v->text_bytes = text_bytes;
-    const uint64_t cap = pow2_at_least(2 * n);
-    auto up = [](uint64_t x) { return (x + 255) & ~255ull; };
-    const uint64_t o_text = 0, o_loff = o_text + up(text_bytes + 16), o_k0 = o_loff + up(8 * (n + 1)),
-                   o_k1 = o_k0 + 8 * cap, o_id = o_k1 + 8 * cap, total = o_id + 4 * cap;
-    if (hipMalloc(&v->block, total) != hipSuccess) {
-        (void)hipGetLastError();
-        v->block = nullptr;
-        raise(MRG_ENOMEM, "vocabulary: device allocation of %llu bytes failed", (unsigned long long)total);
-    }
+    VocPtr v = vocab_alloc(c, n, text_bytes, hash_bits(c));
     uint8_t *blk = (uint8_t *)v->block;
-    VocTable &T = v->T;
-    T.k0 = (uint64_t *)(blk + o_k0);
-    T.k1 = (uint64_t *)(blk + o_k1);
-    T.id = (uint32_t *)(blk + o_id);
-    T.cap = cap;
-    T.hash_bits = hash_bits(c);
-    T.text = blk + o_text;
-    T.line_off = (const uint64_t *)(blk + o_loff);
-    T.n = n;
-    if (text_bytes) HIPCHK(hipMemcpyAsync(blk + o_text, c->d_top, text_bytes, hipMemcpyDeviceToDevice, s));
-    if (n) HIPCHK(hipMemcpyAsync(blk + o_loff, loff, 8 * (n + 1), hipMemcpyDeviceToDevice, s));
-    else HIPCHK(hipMemsetAsync(blk + o_loff, 0, 8, s));
-    unsigned long long *fail = sc.get<unsigned long long>(1);
-    HIPCHK(hipMemsetAsync(fail, 0, 8, s));
-    mrg_voc_launch_build(T, wlen, fail, s);
-    HIPCHK(hipGetLastError());
-    unsigned long long hfail = 0;
-    HIPCHK(hipMemcpyAsync(&hfail, fail, 8, hipMemcpyDeviceToHost, s));
+    if (text_bytes) HIPCHK(hipMemcpyAsync(blk, c->d_top, text_bytes, hipMemcpyDeviceToDevice, s));
+    if (n) HIPCHK(hipMemcpyAsync((void *)v->T.line_off, loff, 8 * (n + 1), hipMemcpyDeviceToDevice, s));
+    if (n) HIPCHK(hipMemcpyAsync(v->W.wlen, wlen, 4 * n, hipMemcpyDeviceToDevice, s));
+    vocab_build(c, v.get(), sc);
     enc_rec(c, 5);
     sync(c);
-    if (hfail) raise(MRG_EHIP, "vocabulary: %llu words found no table slot", hfail);
     c->enc_ms[3] = enc_ms(c, 4, 5);
     return v.release();
 }
@@ -2653,6 +2684,175 @@ void vocab_encode(mrg_ctx *c, const mrg_vocab *v, const uint8_t *d_bytes, const 
     if (d_ids) c->enc_ms[2] = enc_ms(c, 2, 3);
     for (int i = 0; i < 5; ++i) c->enc_info[i] = hinfo[i];
     if (!d_ids) c->enc_info[0] = total;
+}
+
+void dec_events(mrg_ctx *c) {
+    if (!c->timing) return;
+    for (auto &e : c->dec_ev)
+        if (!e) HIPCHK(hipEventCreate(&e));
+}
+void dec_rec(mrg_ctx *c, int i) {
+    if (c->timing) HIPCHK(hipEventRecord(c->dec_ev[i], c->stream));
+}
+double dec_ms(mrg_ctx *c, int a, int b) {
+    if (!c->timing) return 0.0;
+    float ms = 0;
+    HIPCHK(hipEventSynchronize(c->dec_ev[b]));
+    HIPCHK(hipEventElapsedTime(&ms, c->dec_ev[a], c->dec_ev[b]));
+    return ms;
+}
+
+// A vocabulary from its text: the host cuts the lines, the device checks every
+// line's form and its word's codepoints (k_voc_check), builds the table as mrg_job_vocab does, and looks
+// every word up again to find a word that stands on two lines (k_voc_verify).  No job state is touched.
+mrg_vocab *vocab_from_text(mrg_ctx *c, const uint8_t *h_text, uint64_t bytes, uint32_t flags) {
+    if (!c) raise(MRG_EINVAL, "null context");
+    if (bytes && !h_text) raise(MRG_EINVAL, "mrg_vocab_from_text: null text");
+    if (flags & ~MRG_FLAG_DEBUG_HASH_BITS(0xFFu))
+        raise(MRG_EINVAL, "mrg_vocab_from_text: flags 0x%x: only MRG_FLAG_DEBUG_HASH_BITS is accepted", flags);
+    HIPCHK(hipSetDevice(c->device));
+    std::vector<uint64_t> loff(1, 0);
+    for (const uint8_t *p = h_text, *e = h_text + bytes; p < e;) {
+        const uint8_t *q = (const uint8_t *)memchr(p, '\n', (size_t)(e - p));
+        if (!q) raise(MRG_EINVAL, "mrg_vocab_from_text: line %llu: the text does not end in a newline",
+                      (unsigned long long)(loff.size() - 1));
+        p = q + 1;
+        loff.push_back((uint64_t)(p - h_text));
+        if (loff.size() - 1 > 0xFFFFFFFEull)
+            raise(MRG_EINVAL, "mrg_vocab_from_text: more than %llu lines: ids are 32 bits", 0xFFFFFFFEull);
+    }
+    const uint64_t n = loff.size() - 1;
+    hipStream_t s = c->stream;
+    Scratch sc(c->pool);
+    dec_events(c);
+    dec_rec(c, 4);
+    VocPtr v = vocab_alloc(c, n, bytes, (flags >> 8) & 0xFFu);
+    if (n) {
+        HIPCHK(hipMemcpyAsync((void *)v->T.text, h_text, bytes, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync((void *)v->T.line_off, loff.data(), 8 * (n + 1), hipMemcpyHostToDevice, s));
+        unsigned long long *err = sc.get<unsigned long long>(2);  // first bad line, first duplicate
+        HIPCHK(hipMemsetAsync(err, 0xFF, 16, s));
+        mrg_voc_launch_check(v->T, v->W.wlen, err, s);
+        HIPCHK(hipGetLastError());
+        unsigned long long herr = 0;
+        HIPCHK(hipMemcpyAsync(&herr, err, 8, hipMemcpyDeviceToHost, s));
+        sync(c);  // (also: the pageable text and offsets have been read)
+        if (herr != ~0ull) {
+            const unsigned long long line = herr >> 2;
+            switch ((uint32_t)(herr & 3u)) {
+                case MRG_VOC_BAD_UTF8:
+                    raise(MRG_EUTF8, "mrg_vocab_from_text: line %llu: the word is not valid UTF-8", line);
+                case MRG_VOC_BAD_CLASS:
+                    raise(MRG_EINVAL, "mrg_vocab_from_text: line %llu: the word holds a codepoint that is not \\w", line);
+                default:
+                    raise(MRG_EINVAL, "mrg_vocab_from_text: line %llu: not `word`, one space, 1 to 20 digits", line);
+            }
+        }
+        vocab_build(c, v.get(), sc);
+        mrg_voc_launch_verify(v->T, v->W.wlen, err + 1, s);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(&herr, err + 1, 8, hipMemcpyDeviceToHost, s));
+        dec_rec(c, 5);
+        sync(c);
+        if (herr != ~0ull) raise(MRG_EINVAL, "mrg_vocab_from_text: line %llu: duplicate word", herr);
+    } else {
+        dec_rec(c, 5);
+        sync(c);
+    }
+    c->dec_ms[3] = dec_ms(c, 4, 5);
+    return v.release();
+}
+
+// Ids -> text (k_decode.hip): boundary bitmap, count pass, scan, per-document offsets, emit pass.
+// Touches no job state; scratch comes from the pool and goes back on every exit.
+void vocab_decode(mrg_ctx *c, const mrg_vocab *v, const uint32_t *d_ids, const uint64_t *h_tok_off, uint32_t n_docs,
+                  const uint8_t *h_unk, uint32_t unk_len, uint8_t *d_out, uint64_t cap, uint64_t *h_out_off) {
+    if (!c) raise(MRG_EINVAL, "null context");
+    if (!v) raise(MRG_EINVAL, "null vocabulary");
+    if (!h_tok_off || !h_out_off) raise(MRG_EINVAL, "null offsets (h_tok_off and h_out_off need n_docs + 1 entries)");
+    if (v->device != c->device) raise(MRG_EINVAL, "the vocabulary lives on device %d, the context on device %d", v->device,
+                                      c->device);
+    if (n_docs == 0xFFFFFFFFu) raise(MRG_EINVAL, "n_docs out of range");
+    if ((uintptr_t)d_ids & 3u) raise(MRG_EINVAL, "the ids must be 4-byte aligned");
+    if (unk_len > 255u) raise(MRG_EINVAL, "unk_len %u: at most 255 bytes", unk_len);
+    if (unk_len && !h_unk) raise(MRG_EINVAL, "null h_unk with unk_len %u", unk_len);
+    for (uint32_t i = 0; i < n_docs; ++i)
+        if (h_tok_off[i + 1] < h_tok_off[i]) raise(MRG_EINVAL, "token offsets must be non-decreasing");
+    HIPCHK(hipSetDevice(c->device));
+    memset(c->dec_info, 0, sizeof c->dec_info);
+    c->dec_ms[0] = c->dec_ms[1] = c->dec_ms[2] = 0.0;
+    const uint64_t lo0 = h_tok_off[0], hi0 = h_tok_off[n_docs];
+    if (hi0 == lo0) {  // no ids: no bytes
+        for (uint32_t i = 0; i <= n_docs; ++i) h_out_off[i] = 0;
+        return;
+    }
+    if (!d_ids) raise(MRG_EINVAL, "null ids");
+    Pool &p = c->pool;
+    hipStream_t s = c->stream;
+    Scratch sc(p);
+    dec_events(c);
+    // positions relative to the 16-byte boundary at or below the first id
+    const uint64_t shift = (uint64_t)(((uintptr_t)(d_ids + lo0) & 15u) >> 2);
+    std::vector<uint64_t> rel(h_tok_off, h_tok_off + n_docs + 1);
+    for (auto &x : rel) x = x - lo0 + shift;
+    DecPlan P{};
+    P.in = d_ids + lo0 - shift;
+    P.lo = shift;
+    P.hi = shift + (hi0 - lo0);
+    P.nchunks = (P.hi + MRG_DEC_CHUNK - 1) / MRG_DEC_CHUNK;
+    P.n_docs = n_docs;
+    const uint64_t bw = mrg_dec_bitmap_words(P.nchunks);
+    P.bnd = sc.get<uint32_t>(bw);
+    uint64_t *d_off = sc.get<uint64_t>((uint64_t)n_docs + 1);
+    P.tok_off = d_off;
+    P.cnt = sc.get<uint64_t>(P.nchunks + 1);
+    P.out_off = sc.get<uint64_t>((uint64_t)n_docs + 1);
+    uint64_t *stmp = sc.get<uint64_t>(mrg_scan_tmp_elems(P.nchunks + 1));
+    unsigned long long *small = sc.get<unsigned long long>(1 + 32);  // err, the UNK bytes
+    P.err = small;
+    P.unk_len = unk_len;
+    P.unk = (const uint8_t *)(small + 1);
+    for (uint32_t i = 0; i < unk_len && i < 16u; ++i)
+        (i < 8u ? P.unk_k0 : P.unk_k1) |= (uint64_t)h_unk[i] << (56u - 8u * (i & 7u));
+    c->dec_info[0] = hi0 - lo0;
+    c->dec_info[2] = P.nchunks;
+    c->dec_info[3] = 4 * bw + 8 * (P.nchunks + 1) + 16 * ((uint64_t)n_docs + 1) + 8 * mrg_scan_tmp_elems(P.nchunks + 1) + 264;
+    HIPCHK(hipMemcpyAsync(d_off, rel.data(), 8 * ((uint64_t)n_docs + 1), hipMemcpyHostToDevice, s));
+    if (unk_len) HIPCHK(hipMemcpyAsync(small + 1, h_unk, unk_len, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(P.bnd, 0, 4 * bw, s));
+    HIPCHK(hipMemsetAsync(P.cnt, 0, 8 * (P.nchunks + 1), s));
+    HIPCHK(hipMemsetAsync(P.err, 0xFF, 8, s));
+    mrg_dec_launch_bounds(P, s);
+    dec_rec(c, 0);
+    mrg_dec_launch_count(P, v->T, v->W, s);
+    dec_rec(c, 1);
+    mrg_scan_u64(P.cnt, P.cnt, P.nchunks + 1, stmp, s);
+    mrg_dec_launch_offsets(P, v->T, v->W, s);
+    dec_rec(c, 2);
+    HIPCHK(hipGetLastError());
+    unsigned long long herr = 0;
+    HIPCHK(hipMemcpyAsync(h_out_off, P.out_off, 8 * ((uint64_t)n_docs + 1), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&herr, P.err, 8, hipMemcpyDeviceToHost, s));
+    sync(c);  // (also: the pageable `rel` and h_unk have been read)
+    c->dec_ms[0] = dec_ms(c, 0, 1);
+    c->dec_ms[1] = dec_ms(c, 1, 2);
+    if (herr != ~0ull)
+        raise(MRG_EINVAL, "mrg_vocab_decode: the id at index %llu is not in the vocabulary (%llu words%s)",
+              (unsigned long long)(herr - shift + lo0), (unsigned long long)v->n,
+              unk_len ? "" : "; MRG_ID_UNK needs unk_len > 0");
+    const uint64_t total = h_out_off[n_docs];
+    c->dec_info[1] = total;
+    if (!d_out) return;
+    if (cap < total) raise(MRG_EINVAL, "destination too small (%llu bytes < %llu bytes of text)", (unsigned long long)cap,
+                           (unsigned long long)total);
+    P.out = d_out;
+    P.out_n = total;
+    dec_rec(c, 2);
+    if (total) mrg_dec_launch_emit(P, v->T, v->W, s);
+    dec_rec(c, 3);
+    HIPCHK(hipGetLastError());
+    sync(c);
+    c->dec_ms[2] = dec_ms(c, 2, 3);
 }
 
 void export_sizes(mrg_ctx *c, uint32_t n_owners, uint64_t *h_rec, uint64_t *h_heap) {
@@ -3209,6 +3409,8 @@ int mrg_close(mrg_ctx *c) {
         for (auto &e : c->ev) (void)hipEventDestroy(e);
         for (auto &e : c->enc_ev)
             if (e) (void)hipEventDestroy(e);
+        for (auto &e : c->dec_ev)
+            if (e) (void)hipEventDestroy(e);
         (void)hipFree(c->d_cnt);
         (void)hipHostFree(c->h_cnt);
         if (c->h_stage) (void)hipHostFree(c->h_stage);
@@ -3404,6 +3606,30 @@ void mrg_vocab_free(mrg_vocab *v) { vocab_destroy(v); }
 int mrg_vocab_encode(mrg_ctx *c, const mrg_vocab *v, const uint8_t *d_bytes, const uint64_t *h_doc_off, uint32_t n_docs,
                      uint32_t *d_ids, uint64_t cap_ids, uint64_t *h_tok_off) {
     return guard([&] { vocab_encode(c, v, d_bytes, h_doc_off, n_docs, d_ids, cap_ids, h_tok_off); });
+}
+
+int mrg_vocab_from_text(mrg_ctx *c, const uint8_t *h_text, uint64_t bytes, uint32_t flags, mrg_vocab **out) {
+    return guard([&] {
+        if (!out) raise(MRG_EINVAL, "null out pointer");
+        *out = nullptr;
+        *out = vocab_from_text(c, h_text, bytes, flags);
+    });
+}
+
+int mrg_vocab_decode(mrg_ctx *c, const mrg_vocab *v, const uint32_t *d_ids, const uint64_t *h_tok_off, uint32_t n_docs,
+                     const uint8_t *h_unk, uint32_t unk_len, uint8_t *d_out, uint64_t cap, uint64_t *h_out_off) {
+    return guard([&] { vocab_decode(c, v, d_ids, h_tok_off, n_docs, h_unk, unk_len, d_out, cap, h_out_off); });
+}
+
+// Diagnostics of the last mrg_vocab_decode (not in include/mrgpu.h; tools/time_decode.py): h_info[0..4) =
+// ids, output bytes, chunks, scratch bytes; h_ms[0..4) = count pass, scan + document offsets, emit pass,
+// and the last mrg_vocab_from_text (HIP events, with mrg_set_timing).
+int mrg_decode_info(mrg_ctx *c, uint64_t *h_info, double *h_ms) {
+    return guard([&] {
+        if (!c) raise(MRG_EINVAL, "null context");
+        if (h_info) memcpy(h_info, c->dec_info, sizeof c->dec_info);
+        if (h_ms) memcpy(h_ms, c->dec_ms, sizeof c->dec_ms);
+    });
 }
 
 // Diagnostics of the last mrg_vocab_encode (not in include/mrgpu.h; tools/time_encode.py): h_info[0..7) =

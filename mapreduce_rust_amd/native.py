@@ -115,6 +115,8 @@ _SIGS = {
     "mrg_vocab_copy_text": (C.c_int, [_vp, _vp, C.c_uint64]),
     "mrg_vocab_free": (None, [_vp]),
     "mrg_vocab_encode": (C.c_int, [_vp, _vp, _vp, _u64p, C.c_uint32, _vp, C.c_uint64, _u64p]),
+    "mrg_vocab_from_text": (C.c_int, [_vp, C.c_char_p, C.c_uint64, C.c_uint32, C.POINTER(_vp)]),
+    "mrg_vocab_decode": (C.c_int, [_vp, _vp, _vp, _u64p, C.c_uint32, C.c_char_p, C.c_uint32, _vp, C.c_uint64, _u64p]),
     "mrg_map": (C.c_int, [_vp, C.c_int, C.c_char_p, C.c_size_t, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32,
                           C.POINTER(_vp)]),
     "mrg_parts_get": (C.c_int, [_vp, C.c_uint32, C.POINTER(_vp), _u64p, C.POINTER(_vp), _u64p]),
@@ -206,8 +208,9 @@ class Parts:
 
 
 class Vocab:
-    """mrg_vocab: the most frequent words of a job as ids 0..n-1 (Context.vocab).  Owns its device
-    memory; outlives the job and the context that made it."""
+    """mrg_vocab: words as ids 0..n-1, from a job's most frequent words (Context.vocab) or from
+    "word count\\n" text (Context.vocab_from_text, Context.vocab_load).  Owns its device memory; outlives
+    the job and the context that made it."""
 
     def __init__(self, handle):
         self.h = handle
@@ -228,6 +231,11 @@ class Vocab:
     def words(self):
         """The words in id order (list of bytes)."""
         return [ln.rsplit(b" ", 1)[0] for ln in self.text().split(b"\n") if ln]
+
+    def save(self, path):
+        """Write the text to a file that Context.vocab_load reads back, on any device."""
+        with open(path, "wb") as f:
+            f.write(self.text())
 
     def close(self):
         if self.h:
@@ -422,6 +430,45 @@ class Context:
         tok = (C.c_uint64 * (n + 1))()
         _check(load().mrg_vocab_encode(self.h, vocab.h, dev_ptr, _u64arr(doc_off), n, out_ptr, cap, tok))
         return list(tok)
+
+    def vocab_from_text(self, text, flags=0):
+        """mrg_vocab_from_text: a Vocab on this context's device from "word count\\n" lines (bytes): the
+        text of another Vocab, or the top.txt / final.txt of a word-count run_job.  Line i's word gets id i.
+        flags: debug_hash_bits(n) only."""
+        text = bytes(text)
+        h = _vp()
+        _check(load().mrg_vocab_from_text(self.h, text, len(text), flags, C.byref(h)))
+        return Vocab(h)
+
+    def vocab_load(self, path, flags=0):
+        """vocab_from_text of a file's bytes (Vocab.save, top.txt, final.txt)."""
+        with open(path, "rb") as f:
+            return self.vocab_from_text(f.read(), flags)
+
+    def decode(self, vocab, ids_ptr, tok_off, out_ptr=None, cap=0, unk=b""):
+        """mrg_vocab_decode: the ids of every document (layout of encode's output: uint32 ids at the device
+        pointer ids_ptr, document i = ids[tok_off[i]:tok_off[i + 1]]) as text on the device: each word and a
+        ' ', a '\\n' after a document's last word.  Returns out_off (len(tok_off) entries): document i's
+        text is out[out_off[i]:out_off[i + 1]].  out_ptr None: sizes only.  unk: the bytes written for
+        ID_UNK (empty: ID_UNK is an error)."""
+        if len(tok_off) < 1:
+            raise ValueError("tok_off needs n_docs + 1 entries (at least [0])")
+        n = len(tok_off) - 1
+        off = (C.c_uint64 * (n + 1))()
+        unk = bytes(unk)
+        _check(load().mrg_vocab_decode(self.h, vocab.h, ids_ptr, _u64arr(tok_off), n, unk, len(unk), out_ptr, cap, off))
+        return list(off)
+
+    def decode_info(self):
+        """Diagnostics of the last decode(): ids, output bytes, 256-id chunks, scratch bytes; HIP-event ms
+        per pass and of the last vocab_from_text() (with set_timing)."""
+        f = load().mrg_decode_info
+        f.restype = C.c_int
+        f.argtypes = [_vp, _u64p, C.POINTER(C.c_double)]
+        info, ms = (C.c_uint64 * 8)(), (C.c_double * 4)()
+        _check(f(self.h, info, ms))
+        return {"ids": info[0], "output_bytes": info[1], "chunks": info[2], "scratch_bytes": info[3],
+                "ms_count": ms[0], "ms_offsets": ms[1], "ms_emit": ms[2], "ms_from_text": ms[3]}
 
     def encode_info(self):
         """Diagnostics of the last encode(): tokens, UNK and long tokens, non-ASCII 1 KiB chunks, table
