@@ -259,10 +259,13 @@ uint64_t mrg_format(const FormatArgs &f, DevPool &pool, uint8_t **out_buf, uint6
         // no round trip for the byte count: the buffer is sized by a bound ("key count\n" with at most
         // 16 short-key bytes or the long key's heap bytes, and 20 digits), the count read with part_off
         const uint64_t bound = n * (16u + 2u + 20u) + f.heap_bytes + 16u;
-        if (bound > *out_cap) {
-            if (*out_buf) pool.put(*out_buf);
+        if (bound > *out_cap) {  // (if the allocation fails the caller holds no buffer, never a returned one)
+            uint8_t *old = *out_buf;
+            *out_buf = nullptr;
+            *out_cap = 0;
+            if (old) pool.put(old);
+            *out_buf = (uint8_t *)pool.get(bound);
             *out_cap = bound;
-            *out_buf = (uint8_t *)pool.get(*out_cap);
         }
         if (n)
             hipLaunchKernelGGL(k_wc_write, grid_for(n), dim3(256), 0, s, recs, n, f.ks, f.heap, L, O, f.carried, *out_buf);
@@ -302,9 +305,12 @@ uint64_t mrg_format(const FormatArgs &f, DevPool &pool, uint8_t **out_buf, uint6
         hipMemcpyAsync(&total, total_d, sizeof total, hipMemcpyDeviceToHost, s);
         hipStreamSynchronize(s);
         if (total + 16 > *out_cap) {
-            if (*out_buf) pool.put(*out_buf);
+            uint8_t *old = *out_buf;
+            *out_buf = nullptr;
+            *out_cap = 0;
+            if (old) pool.put(old);
+            *out_buf = (uint8_t *)pool.get(total + 16);
             *out_cap = total + 16;
-            *out_buf = (uint8_t *)pool.get(*out_cap);
         }
         if (n)
             hipLaunchKernelGGL(k_idx_write, grid_for(n), dim3(256), 0, s, recs, n, G, f.ks, f.heap, head, E, H, P, GL,

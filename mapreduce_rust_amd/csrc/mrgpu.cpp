@@ -21,6 +21,7 @@
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
+#include <exception>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -287,6 +288,52 @@ T *pget(Pool &p, uint64_t n) {
     return (T *)p.get(sizeof(T) * (n ? n : 1));
 }
 
+// The pool blocks of one scope, returned on every exit from it, an exception included.  A block goes
+// back at the point the host reaches, while kernels that use it may still be queued on the context's
+// stream: every later user of the block runs on that same stream, behind them.  put() returns one block
+// early, so the allocations that follow can reuse it; release() hands one to an owner that outlives
+// the scope (c->keys, c->wide, c->d_out, another Scratch).
+struct Scratch {
+    Pool &p;
+    std::vector<void *> b;
+    explicit Scratch(Pool &pool) : p(pool) {}
+    Scratch(const Scratch &) = delete;
+    Scratch &operator=(const Scratch &) = delete;
+    Scratch(Scratch &&o) : p(o.p), b(std::move(o.b)) { o.b.clear(); }
+    Scratch &operator=(Scratch &&o) {  // (of the same pool)
+        put_all();
+        b = std::move(o.b);
+        o.b.clear();
+        return *this;
+    }
+    template <class T>
+    T *get(uint64_t n) {
+        b.push_back(nullptr);
+        return (T *)(b.back() = pget<T>(p, n));
+    }
+    template <class T>
+    T *adopt(T *q) {
+        if (q) b.push_back((void *)q);
+        return q;
+    }
+    template <class T>
+    T *release(T *q) {
+        auto it = std::find(b.begin(), b.end(), (void *)q);
+        if (it != b.end()) b.erase(it);
+        return q;
+    }
+    template <class T>
+    void put(T *q) {
+        if (q) p.put((void *)release(q));
+    }
+    void put_all() {
+        for (void *q : b) p.put(q);
+        b.clear();
+    }
+    void keep() { b.clear(); }  // every block has found its longer-lived owner
+    ~Scratch() { put_all(); }
+};
+
 struct KeysBuf {
     KeySet ks{};
     uint64_t n = 0, cap = 0;
@@ -510,25 +557,41 @@ void read_counters(mrg_ctx *c) {
     sync(c);
 }
 
-void ev_rec(mrg_ctx *c, int i) {
-    if (c->timing) HIPCHK(hipEventRecord(c->ev[i], c->stream));
+// Timing events (mrg_set_timing) of one of the context's event arrays: c->ev (made by mrg_open), or
+// c->enc_ev / c->dec_ev, which ev_make creates on first use.
+template <size_t N>
+void ev_make(mrg_ctx *c, hipEvent_t (&ev)[N]) {
+    if (!c->timing) return;
+    for (auto &e : ev)
+        if (!e) HIPCHK(hipEventCreate(&e));
 }
-double ev_ms(mrg_ctx *c, int a, int b) {
+void ev_rec(mrg_ctx *c, hipEvent_t *ev, int i) {
+    if (c->timing) HIPCHK(hipEventRecord(ev[i], c->stream));
+}
+double ev_ms(mrg_ctx *c, hipEvent_t *ev, int a, int b) {
     if (!c->timing) return 0.0;
     float ms = 0;
-    HIPCHK(hipEventSynchronize(c->ev[b]));
-    HIPCHK(hipEventElapsedTime(&ms, c->ev[a], c->ev[b]));
+    HIPCHK(hipEventSynchronize(ev[b]));
+    HIPCHK(hipEventElapsedTime(&ms, ev[a], ev[b]));
     return ms;
 }
 
-void keys_release(mrg_ctx *c) {
-    KeysBuf &k = c->keys;
-    Pool &p = c->pool;
-    p.put(k.ks.k0); p.put(k.ks.k1); p.put(k.ks.cnt); p.put(k.ks.hoff);
-    p.put(k.ks.doc); p.put(k.ks.len); p.put(k.ks.part);
-    p.put(k.heap);
-    k = KeysBuf{};
-}
+// Drops the staged writes (stage_h2d / stage_fill) that are still pending when its scope ends by an
+// exception: their destinations are scratch blocks the same exit returns to the pool, and the next
+// flush_stage -- the next job's, at the latest -- would write them into memory that another call owns
+// by then.  The staging bytes they used had no copy issued, so the bump pointer goes back over them.
+struct StageDrop {
+    mrg_ctx *c;
+    int live = std::uncaught_exceptions();
+    explicit StageDrop(mrg_ctx *ctx) : c(ctx) {}
+    StageDrop(const StageDrop &) = delete;
+    StageDrop &operator=(const StageDrop &) = delete;
+    ~StageDrop() {
+        if (std::uncaught_exceptions() == live || c->pend.empty()) return;
+        c->pend.clear();
+        c->stage_used = c->pend_lo;
+    }
+};
 
 void keysbuf_release(Pool &p, KeysBuf &k) {
     p.put(k.ks.k0); p.put(k.ks.k1); p.put(k.ks.cnt); p.put(k.ks.hoff);
@@ -549,18 +612,21 @@ void acc_release(mrg_ctx *c) {
     c->acc = Acc{};
 }
 
+// c->keys with room for `cap` keys; on a failure it is left empty
 void keys_reserve(mrg_ctx *c, uint64_t cap) {
-    keys_release(c);
-    KeysBuf &k = c->keys;
-    Pool &p = c->pool;
-    k.ks.k0 = pget<uint64_t>(p, cap);
-    k.ks.k1 = pget<uint64_t>(p, cap);
-    k.ks.cnt = pget<uint64_t>(p, cap);
-    k.ks.hoff = pget<uint64_t>(p, cap);
-    k.ks.doc = pget<uint32_t>(p, cap);
-    k.ks.len = pget<uint32_t>(p, cap);
-    k.ks.part = pget<uint32_t>(p, cap);
-    k.cap = cap;
+    keysbuf_release(c->pool, c->keys);  // (first: the new arrays may be the old blocks)
+    Scratch sc(c->pool);
+    KeySet ks{};
+    ks.k0 = sc.get<uint64_t>(cap);
+    ks.k1 = sc.get<uint64_t>(cap);
+    ks.cnt = sc.get<uint64_t>(cap);
+    ks.hoff = sc.get<uint64_t>(cap);
+    ks.doc = sc.get<uint32_t>(cap);
+    ks.len = sc.get<uint32_t>(cap);
+    ks.part = sc.get<uint32_t>(cap);
+    sc.keep();
+    c->keys.ks = ks;
+    c->keys.cap = cap;
 }
 
 uint64_t pow2_at_least(uint64_t x) {
@@ -580,37 +646,36 @@ struct ShortSrc {
 // Sum short-key records in the HBM table (exact; device-scope CAS) and append the distinct keys to
 // c->keys (counter CNT_KEYS, which the caller has initialised).
 void table_aggregate(mrg_ctx *c, const ShortSrc &src) {
-    Pool &p = c->pool;
+    Scratch sc(c->pool);
     hipStream_t s = c->stream;
     const bool idx = is_idx(c);
     if (src.n) {
         TableArgs T{};
         T.cap = pow2_at_least(2 * src.n);
-        T.tk0 = pget<uint64_t>(p, T.cap);
-        T.tk1 = pget<uint64_t>(p, T.cap);
-        T.tcnt = pget<uint64_t>(p, T.cap);
-        T.tdoc = idx ? pget<uint32_t>(p, T.cap) : nullptr;
+        T.tk0 = sc.get<uint64_t>(T.cap);
+        T.tk1 = sc.get<uint64_t>(T.cap);
+        T.tcnt = sc.get<uint64_t>(T.cap);
+        T.tdoc = idx ? sc.get<uint32_t>(T.cap) : nullptr;
         T.hash_bits = hash_bits(c);
         mrg_launch_table_clear(T, idx, s);
         if (src.x) mrg_launch_table_insert_x(T, src.x, src.n, idx, s);
         else if (src.lx) mrg_launch_table_insert_l(T, src.lx, src.n, idx, s);
         else mrg_launch_table_insert(T, src.k0, src.k1, src.cnt, src.doc, src.n, idx, s);
         mrg_launch_table_compact(T, idx, c->keys.ks, &c->d_cnt[CNT_KEYS], s);
-        p.put(T.tk0); p.put(T.tk1); p.put(T.tcnt); p.put(T.tdoc);
     }
 }
 
 // Long keys: fingerprint sort + full-byte tie-break grouping; appends to c->keys and owns the heap.
 void long_aggregate(mrg_ctx *c, LongItems li) {
-    Pool &p = c->pool;
+    Scratch sc(c->pool);
     hipStream_t s = c->stream;
     const bool idx = is_idx(c);
     if (li.n) {
         const uint64_t n = li.n;
-        uint64_t *k0 = pget<uint64_t>(p, n), *k1 = pget<uint64_t>(p, n), *fp = pget<uint64_t>(p, n);
-        uint64_t *fl64 = pget<uint64_t>(p, n), *hoff = pget<uint64_t>(p, n), *acc = pget<uint64_t>(p, n);
-        uint32_t *fl = pget<uint32_t>(p, n), *ix = pget<uint32_t>(p, n), *rep = pget<uint32_t>(p, n);
-        uint64_t *scantmp = pget<uint64_t>(p, mrg_scan_tmp_elems(n));
+        uint64_t *k0 = sc.get<uint64_t>(n), *k1 = sc.get<uint64_t>(n), *fp = sc.get<uint64_t>(n);
+        uint64_t *fl64 = sc.get<uint64_t>(n), *hoff = sc.get<uint64_t>(n), *acc = sc.get<uint64_t>(n);
+        uint32_t *fl = sc.get<uint32_t>(n), *ix = sc.get<uint32_t>(n), *rep = sc.get<uint32_t>(n);
+        uint64_t *scantmp = sc.get<uint64_t>(mrg_scan_tmp_elems(n));
         mrg_launch_long_prep(li.base, li.start, li.rawlen, n, k0, k1, fl, fl64, fp, hash_bits(c), li.verbatim, s);
         mrg_scan_u64(fl64, hoff, n, scantmp, s);
         uint64_t last[2];
@@ -618,23 +683,21 @@ void long_aggregate(mrg_ctx *c, LongItems li) {
         HIPCHK(hipMemcpyAsync(&last[1], fl64 + (n - 1), 8, hipMemcpyDeviceToHost, s));
         sync(c);
         const uint64_t heap_bytes = last[0] + last[1];
-        c->keys.heap = pget<uint8_t>(p, heap_bytes + 16);
+        c->keys.heap = pget<uint8_t>(c->pool, heap_bytes + 16);
         c->keys.heap_bytes = heap_bytes;
         mrg_launch_long_gather(li.base, li.start, li.rawlen, n, hoff, c->keys.heap, li.verbatim, s);
         // fingerprint sort (collision-safe: k_long_group compares full bytes inside equal runs)
-        uint64_t *fps = pget<uint64_t>(p, n);
+        uint64_t *fps = sc.get<uint64_t>(n);
         HIPCHK(hipMemcpyAsync(fps, fp, 8 * n, hipMemcpyDeviceToDevice, s));
         mrg_launch_iota_u32(ix, n, s);
-        uint64_t *kv = pget<uint64_t>(p, 4 * n);
-        void *stmp = p.get(mrg_sort_tmp_bytes(n));
+        uint64_t *kv = sc.get<uint64_t>(4 * n);
+        void *stmp = sc.get<uint8_t>(mrg_sort_tmp_bytes(n));
         check_sort_n(n, "long-key fingerprint sort");
         mrg_radix_sort_u64(fps, ix, kv, n, stmp, s);
         mrg_launch_long_group(fps, ix, idx ? li.doc : nullptr, c->keys.heap, hoff, fl, n, rep, s);
         HIPCHK(hipMemsetAsync(acc, 0, 8 * n, s));
         mrg_launch_long_emit(rep, li.cnt, k0, k1, fl, hoff, li.doc, n, (unsigned long long *)acc, c->keys.ks,
                              &c->d_cnt[CNT_KEYS], idx, s);
-        p.put(k0); p.put(k1); p.put(fp); p.put(fl64); p.put(hoff); p.put(acc);
-        p.put(fl); p.put(ix); p.put(rep); p.put(scantmp); p.put(fps); p.put(kv); p.put(stmp);
         c->keys.any_long = true;
     }
 }
@@ -663,43 +726,29 @@ void aggregate(mrg_ctx *c, const ShortSrc &src, LongItems li) {
     finish_keys(c);
 }
 
-struct MapBufs {
-    uint64_t *pool = nullptr, *rbase = nullptr;
-    uint32_t *bcap = nullptr, *bcount = nullptr;
-    uint64_t *pool16 = nullptr, *rbase16 = nullptr;
-    uint32_t *bcap16 = nullptr, *bcount16 = nullptr;
-    MapArgs *dargs = nullptr;
-    uint64_t *ovf = nullptr;
-    uint32_t *onext = nullptr;
-    uint64_t *fk0 = nullptr, *fk1 = nullptr;
-    uint32_t *fcnt = nullptr, *fdoc = nullptr, *foff = nullptr;
-    uint64_t *lstart = nullptr;
-    uint32_t *llen = nullptr, *ldoc = nullptr, *lcount = nullptr;
-    uint64_t *dstart = nullptr;  // long-token records packed densely after the map
-    uint32_t *dlen = nullptr, *ddoc = nullptr;
-    uint32_t *gbits = nullptr;
-    unsigned long long *prof = nullptr;
-    unsigned long long *pool_ctr = nullptr;  // the load-balance pool's part counters
-    void release(Pool &p) {
-        p.put(prof);
-        p.put(pool_ctr);
-        p.put(lcount); p.put(dstart); p.put(dlen); p.put(ddoc);
-        p.put(pool); p.put(rbase); p.put(bcap); p.put(bcount); p.put(dargs); p.put(ovf); p.put(onext);
-        p.put(pool16); p.put(rbase16); p.put(bcap16); p.put(bcount16);
-        p.put(fk0); p.put(fk1); p.put(fcnt); p.put(fdoc); p.put(foff);
-        p.put(lstart); p.put(llen); p.put(ldoc); p.put(gbits);
-        *this = MapBufs{};
-    }
-};
-
-struct MapSteal;
-void set_steal(mrg_ctx *c, MapArgs &A, MapBufs &M, const MapSteal &ms, uint64_t n_chunks);
-
+// One launch of the per-bucket aggregation; owns its overflow list (B.ok0, ok1, ocnt, odoc).
 struct AggLaunch {
     BucketArgs B{};
     uint64_t nlong = 0;  // long keys the launch reserved key slots for
-    bool c32 = false, live = false;
+    bool c32 = false;
+    Scratch own;
+    explicit AggLaunch(Pool &p) : own(p) {}
+    AggLaunch(AggLaunch &&) = default;
+    AggLaunch &operator=(AggLaunch &&) = default;
+    bool live() const { return !own.b.empty(); }
+    void drop() { own.put_all(); }  // the overflow list back to the pool
 };
+
+// the LDS-combine map's output (tail regions, overflow lists, flushed tables) as the aggregations read it
+BucketArgs map_output(const MapArgs &A, uint32_t nreg, uint32_t regcap) {
+    BucketArgs B{};
+    B.pool = A.pool; B.rbase = A.rbase; B.bcap = A.bcap; B.bcount = A.bcount;
+    B.pool16 = A.pool16; B.rbase16 = A.rbase16; B.bcap16 = A.bcap16; B.bcount16 = A.bcount16;
+    B.movf = A.ovf; B.monext = A.onext; B.mocap = A.ocap;
+    B.fk0 = A.fk0; B.fk1 = A.fk1; B.fcnt = A.fcnt; B.fdoc = A.fdoc; B.foff = A.foff;
+    B.nreg = nreg; B.regcap = regcap;
+    return B;
+}
 
 uint64_t agg_ocap(mrg_ctx *c) {
     uint64_t ocap = std::max<uint64_t>(c->ovf_hint, 1u << 20);
@@ -707,24 +756,20 @@ uint64_t agg_ocap(mrg_ctx *c) {
     return ocap;
 }
 
-// one launch of the per-bucket aggregation over the map's output (its overflow list is returned to
-// the pool by agg_put); zero: clear the two counters it adds to (the map launch zeroed them)
+// one launch of the per-bucket aggregation over the map's output (its overflow list goes back to the
+// pool with the AggLaunch, or by drop()); zero: clear the two counters it adds to (the map launch
+// zeroed them)
 AggLaunch agg_launch(mrg_ctx *c, const MapArgs &A, uint32_t nreg, uint32_t regcap, uint64_t ocap, uint32_t nsub,
                      uint64_t nlong, bool c32, bool zero) {
-    Pool &p = c->pool;
     hipStream_t s = c->stream;
     const bool idx = is_idx(c);
     // every workgroup (bucket, sub-range) may emit a full table of keys
     keys_reserve(c, (uint64_t)MRG_NBUCKET * std::max<uint32_t>(nsub, 1u) * MRG_BA_CAP + ocap + nlong + 1);
-    AggLaunch L;
+    AggLaunch L(c->pool);
     BucketArgs &B = L.B;
-    B.pool = A.pool; B.rbase = A.rbase; B.bcap = A.bcap; B.bcount = A.bcount;
-    B.pool16 = A.pool16; B.rbase16 = A.rbase16; B.bcap16 = A.bcap16; B.bcount16 = A.bcount16;
-    B.movf = A.ovf; B.monext = A.onext; B.mocap = A.ocap;
-    B.fk0 = A.fk0; B.fk1 = A.fk1; B.fcnt = A.fcnt; B.fdoc = A.fdoc; B.foff = A.foff;
-    B.nreg = nreg; B.regcap = regcap;
-    B.ok0 = pget<uint64_t>(p, ocap); B.ok1 = pget<uint64_t>(p, ocap);
-    B.ocnt = pget<uint32_t>(p, ocap); B.odoc = idx ? pget<uint32_t>(p, ocap) : nullptr;
+    B = map_output(A, nreg, regcap);
+    B.ok0 = L.own.get<uint64_t>(ocap); B.ok1 = L.own.get<uint64_t>(ocap);
+    B.ocnt = L.own.get<uint32_t>(ocap); B.odoc = idx ? L.own.get<uint32_t>(ocap) : nullptr;
     B.ocap = ocap;
     B.out = c->keys.ks;
     B.counters = c->d_cnt;
@@ -740,15 +785,7 @@ AggLaunch agg_launch(mrg_ctx *c, const MapArgs &A, uint32_t nreg, uint32_t regca
     mrg_launch_bucket_agg(B, idx, c32, s);
     L.nlong = nlong;
     L.c32 = c32;
-    L.live = true;
     return L;
-}
-
-void agg_put(mrg_ctx *c, AggLaunch &L) {
-    if (!L.live) return;
-    Pool &p = c->pool;
-    p.put(L.B.ok0); p.put(L.B.ok1); p.put(L.B.ocnt); p.put(L.B.odoc);
-    L.live = false;
 }
 
 // Map-side records: per-bucket LDS aggregation of tail chunks + flushed map tables, exact overflow
@@ -766,26 +803,25 @@ bool bucket_aggregate(mrg_ctx *c, const MapArgs &A, uint32_t nreg, uint32_t regc
     uint32_t agg_launches = 0;
     uint32_t nsub = c->agg_nsub;
     if (const uint64_t t = env_u64("MRG_TEST_AGG_NSUB", 0)) nsub = (uint32_t)t;
-    const bool dirty = pre && pre->live;  // a launch since the map: its counters need clearing before another
+    const bool dirty = pre && pre->live();  // a launch since the map: its counters need clearing before another
     for (;;) {
         ++agg_launches;
         // 32-bit LDS counts (larger table) when no key can reach 2^32: fewer tokens than that
         const bool c32 = c->h_cnt[CNT_TOKENS] < 0xFFFFFFFFull && nreg <= 512;
-        AggLaunch L;
+        AggLaunch L(c->pool);  // (its overflow list goes back where an attempt ends: before the next one's blocks)
         // the queued launch is reused only when it ran with this job's parameters: sub-ranges, overflow
         // capacity, count width, and key slots for at least the long keys the map produced (the map
         // reruns whenever its long keys exceed their capacity, which drops the queued launch, so li.n <= nlong
         // holds here; it is checked rather than assumed)
-        if (pre && pre->live && agg_launches == 1 && pre->B.nsub == nsub && pre->B.ocap == ocap &&
+        if (pre && pre->live() && agg_launches == 1 && pre->B.nsub == nsub && pre->B.ocap == ocap &&
             li.n <= pre->nlong &&
             pre->B.kcap >= (uint64_t)MRG_NBUCKET * std::max<uint32_t>(nsub, 1u) * MRG_BA_CAP + ocap + li.n + 1 &&
             pre->c32 == c32) {
-            L = *pre;  // its counters came with the map's
-            pre->live = false;
+            L = std::move(*pre);  // its counters came with the map's
             c->st.spec_agg = 1;
         } else {
-            if (pre && pre->live) c->st.spec_agg = 2;
-            if (pre) agg_put(c, *pre);
+            if (pre && pre->live()) c->st.spec_agg = 2;
+            if (pre) pre->drop();
             L = agg_launch(c, A, nreg, regcap, ocap, nsub, li.n, c32, agg_launches > 1 || dirty);
             read_counters(c);
         }
@@ -802,21 +838,18 @@ bool bucket_aggregate(mrg_ctx *c, const MapArgs &A, uint32_t nreg, uint32_t regc
         // to 16; the count is remembered by the context.  Beyond that, the wide aggregation.
         const uint64_t heavy = env_u64("MRG_TEST_AGG_WIDE_OVF", 4ull << 20);
         if (novf > heavy && nsub < 16 && !env_u64("MRG_TEST_AGG_NSUB", 0)) {
-            agg_put(c, L);
             nsub = c->agg_nsub = std::min<uint32_t>(16, 2 * nsub);  // overflow counts records, not keys: double
             if (getenv("MRG_DEBUG")) fprintf(stderr, "[mrgpu] bucket agg: %llu overflow records -> %u workgroups per bucket\n", (unsigned long long)novf, nsub);
             continue;
         }
         const char *wenv = getenv("MRG_WIDE");  // MRG_WIDE=0 pins the bucket path (tests of its overflow)
         if (!idx && novf > heavy && !(wenv && atoi(wenv) == 0)) {
-            agg_put(c, L);
             c->agg_nsub = 1;  // the next job starts from one workgroup per bucket (a low-cardinality job
                               // would otherwise stream every bucket 16 times)
             if (getenv("MRG_DEBUG")) fprintf(stderr, "[mrgpu] bucket agg: %llu overflow records -> wide\n", (unsigned long long)novf);
             return false;
         }
         if (novf > ocap) {  // overflow list too small: grow (remembered) and run again
-            agg_put(c, L);
             ocap = c->ovf_hint = novf + novf / 8 + 1024;
             continue;
         }
@@ -825,7 +858,6 @@ bool bucket_aggregate(mrg_ctx *c, const MapArgs &A, uint32_t nreg, uint32_t regc
             src.k0 = B.ok0; src.k1 = B.ok1; src.cnt = B.ocnt; src.doc = B.odoc; src.n = novf;
             table_aggregate(c, src);
         }
-        agg_put(c, L);
         c->st.overflow_keys = novf;
         c->st.agg_launches = agg_launches;
         c->spec_agg = !idx;
@@ -857,42 +889,42 @@ uint32_t bytes_for(uint64_t maxval) {
     return b;
 }
 
+// radix sort by (partition < R, the 16 key bytes of a short key)
+SortPlan part_key_plan(uint32_t R) {
+    SortPlan plan{};
+    plan.use_part = R > 1;
+    plan.part_bytes = bytes_for(R - 1);
+    plan.use_k0 = plan.use_k1 = true;
+    return plan;
+}
+
 // Wide (sort-based) aggregation for high-cardinality inputs (k_keys.hip k_wide_*): every map
 // record is gathered with its partition, sorted by (partition, key) and summed per key; the key set
 // comes out in output order.
 void wide_aggregate_radix(mrg_ctx *c, const MapArgs &A, uint32_t nreg, uint32_t regcap, LongItems li) {
-    Pool &p = c->pool;
     hipStream_t s = c->stream;
-    BucketArgs B{};
-    B.pool = A.pool; B.rbase = A.rbase; B.bcap = A.bcap; B.bcount = A.bcount;
-    B.pool16 = A.pool16; B.rbase16 = A.rbase16; B.bcap16 = A.bcap16; B.bcount16 = A.bcount16;
-    B.movf = A.ovf; B.monext = A.onext; B.mocap = A.ocap;
-    B.fk0 = A.fk0; B.fk1 = A.fk1; B.fcnt = A.fcnt; B.fdoc = A.fdoc; B.foff = A.foff;
-    B.nreg = nreg; B.regcap = regcap;
+    Scratch sc(c->pool);
+    const BucketArgs B = map_output(A, nreg, regcap);
     const uint64_t nseg = 2ull * nreg * MRG_NBUCKET + nreg + MRG_NBUCKET;
-    uint64_t *segc = pget<uint64_t>(p, nseg + 1), *sego = pget<uint64_t>(p, nseg + 1);
-    uint64_t *stmp1 = pget<uint64_t>(p, mrg_scan_tmp_elems(nseg + 1));
+    uint64_t *segc = sc.get<uint64_t>(nseg + 1), *sego = sc.get<uint64_t>(nseg + 1);
+    uint64_t *stmp1 = sc.get<uint64_t>(mrg_scan_tmp_elems(nseg + 1));
     HIPCHK(hipMemsetAsync(segc + nseg, 0, 8, s));
     mrg_launch_wide_counts(B, segc, nseg, s);
     mrg_scan_u64(segc, sego, nseg + 1, stmp1, s);  // sego[nseg] = total
     uint64_t n = 0;
     HIPCHK(hipMemcpyAsync(&n, sego + nseg, 8, hipMemcpyDeviceToHost, s));
     sync(c);
-    SortRec *a = pget<SortRec>(p, std::max<uint64_t>(n, 1)), *b = pget<SortRec>(p, std::max<uint64_t>(n, 1));
+    SortRec *a = sc.get<SortRec>(std::max<uint64_t>(n, 1)), *b = sc.get<SortRec>(std::max<uint64_t>(n, 1));
     mrg_launch_wide_gather(B, sego, nseg, c->R, a, s);
-    p.put(segc); p.put(sego); p.put(stmp1);
-    SortPlan plan{};
-    plan.use_part = c->R > 1;
-    plan.part_bytes = bytes_for(c->R - 1);
-    plan.use_k0 = plan.use_k1 = true;
-    void *stmp = p.get(mrg_sort_tmp_bytes(n));
+    sc.put(segc); sc.put(sego); sc.put(stmp1);
+    void *stmp = sc.get<uint8_t>(mrg_sort_tmp_bytes(n));
     int passes = 0;
     check_sort_n(n, "wide aggregation");
-    SortRec *r = mrg_radix_sort(a, b, n, plan, stmp, s, &passes);
-    p.put(stmp);
-    uint64_t *head = pget<uint64_t>(p, n + 1), *cv = pget<uint64_t>(p, n + 1);
-    uint64_t *E = pget<uint64_t>(p, n + 1), *C = pget<uint64_t>(p, n + 1);
-    uint64_t *stmp2 = pget<uint64_t>(p, mrg_scan_tmp_elems(n + 1));
+    SortRec *r = mrg_radix_sort(a, b, n, part_key_plan(c->R), stmp, s, &passes);
+    sc.put(stmp);
+    uint64_t *head = sc.get<uint64_t>(n + 1), *cv = sc.get<uint64_t>(n + 1);
+    uint64_t *E = sc.get<uint64_t>(n + 1), *C = sc.get<uint64_t>(n + 1);
+    uint64_t *stmp2 = sc.get<uint64_t>(mrg_scan_tmp_elems(n + 1));
     mrg_launch_wide_heads(r, n, head, cv, s);
     mrg_scan_u64(head, E, n, stmp2, s);
     mrg_scan_u64(cv, C, n, stmp2, s);
@@ -906,12 +938,12 @@ void wide_aggregate_radix(mrg_ctx *c, const MapArgs &A, uint32_t nreg, uint32_t 
     sync(c);
     const uint64_t runs = tail[0] + tail[1], ctot = tail[2] + tail[3];
     keys_reserve(c, runs + li.n + 1);
-    uint64_t *F = pget<uint64_t>(p, runs + 1);
+    uint64_t *F = sc.get<uint64_t>(runs + 1);
     mrg_launch_wide_keys(r, n, head, E, c->keys.ks, F, s);
     mrg_launch_wide_cnt(F, runs, n, C, ctot, c->keys.ks, s);
     HIPCHK(hipMemcpyAsync(&c->d_cnt[CNT_KEYS], &runs, 8, hipMemcpyHostToDevice, s));
     sync(c);  // `runs` is a host local
-    p.put(a); p.put(b); p.put(head); p.put(cv); p.put(E); p.put(C); p.put(stmp2); p.put(F);
+    sc.put_all();  // (the long keys' blocks may reuse them)
     c->st.overflow_keys = 0;
     c->keys.sorted = li.n == 0;
     long_aggregate(c, li);
@@ -923,21 +955,19 @@ void wide_aggregate_radix(mrg_ctx *c, const MapArgs &A, uint32_t nreg, uint32_t 
 void wide_densify(mrg_ctx *c, uint64_t extra) {
     WideRes &w = c->wide;
     if (!w.ready) return;
-    Pool &p = c->pool;
+    Scratch sc(c->pool);
     hipStream_t s = c->stream;
     const uint64_t nl = (uint64_t)w.B1 * MRG_WIDE_MAXB2;
-    uint32_t *doff = pget<uint32_t>(p, nl + 1);
-    uint32_t *tmp = pget<uint32_t>(p, mrg_scan_tmp_elems(nl + 1));
+    uint32_t *doff = sc.get<uint32_t>(nl + 1);
+    uint32_t *tmp = sc.get<uint32_t>(mrg_scan_tmp_elems(nl + 1));
     mrg_scan_u32(w.leaf_nd, doff, nl, tmp, s);
     keys_reserve(c, w.distinct + extra + 1);
     mrg_wide_launch_dense(w.kout, w.ocnt, w.leaf_pk, w.leaf_out, w.leaf_nd, doff, w.B1, w.B1r, c->keys.ks, s);
     HIPCHK(hipMemcpyAsync(&c->d_cnt[CNT_KEYS], &w.distinct, 8, hipMemcpyHostToDevice, s));
     sync(c);
-    p.put(doff);
-    p.put(tmp);
     c->keys.n = w.distinct;
     c->keys.sorted = true;
-    w.release(p);
+    w.release(c->pool);
 }
 
 // Wide aggregation by the two-level sample sort (k_wide.hip): the map's count-1 records go through
@@ -946,11 +976,11 @@ void wide_densify(mrg_ctx *c, uint64_t extra) {
 // The wide aggregation after L1: L2 leaves inside every L1 bucket (input: the L1 output K1 in bucket
 // order with bstart, or -- rin != null -- the wide map's regions, segments soff), the leaves, the
 // overflowing leaves' fallback, then the long keys.  K1 becomes the output key array; bid holds the
-// L2 leaf id of every record.  Takes ownership of K1 (kept in c->wide), bstart, spl1, bid, wk*.
-void wide_finish(mrg_ctx *c, LongItems li, uint64_t n, uint64_t nw, uint32_t B1, uint32_t B1r, uint64_t *K1,
-                 uint64_t *bstart, uint64_t *spl1, uint16_t *bid, uint64_t *wk0, uint64_t *wk1, uint64_t *wcnt,
-                 uint32_t *wpart, bool dbg, hipEvent_t *pe, int &npe, const WmapIn &wm) {
-    Pool &p = c->pool;
+// L2 leaf id of every record.  `own` holds K1 (kept in c->wide), bstart, spl1, bid and wk*; the blocks
+// taken here join them, and all go back before the long keys' blocks are taken.
+void wide_finish(mrg_ctx *c, Scratch &own, LongItems li, uint64_t n, uint64_t nw, uint32_t B1, uint32_t B1r,
+                 uint64_t *K1, uint64_t *bstart, uint64_t *spl1, uint16_t *bid, uint64_t *wk0, uint64_t *wk1,
+                 uint64_t *wcnt, uint32_t *wpart, bool dbg, hipEvent_t *pe, int &npe, const WmapIn &wm) {
     hipStream_t s = c->stream;
     const uint32_t R = c->R;
     auto mark = [&]() {
@@ -972,31 +1002,32 @@ void wide_finish(mrg_ctx *c, LongItems li, uint64_t n, uint64_t nw, uint32_t B1,
     }
     sp.sample_min = (uint32_t)env_u64("MRG_TEST_L2_MIN", sp.sample_min);  // (tests: sample small buckets)
     if (sp.on) {
-        sp.redo_flags = pget<uint32_t>(p, B1);
+        sp.redo_flags = own.get<uint32_t>(B1);
         HIPCHK(hipMemsetAsync(sp.redo_flags, 0, 4ull * B1, s));
     }
     const uint64_t nrec2 = sp.on ? 9 * n / 4 + 16 : n + 1;  // K2 records
-    uint64_t *K2 = pget<uint64_t>(p, 2 * nrec2 + 2);
-    uint32_t *nleaf = pget<uint32_t>(p, B1);
-    uint64_t *leaf_lo = pget<uint64_t>(p, NL + 1), *leaf_lb = pget<uint64_t>(p, 2 * NL + 2);
-    uint64_t *leaf_hi = pget<uint64_t>(p, NL + 1), *leaf_dlo = pget<uint64_t>(p, NL + 1);
+    uint64_t *K2 = own.get<uint64_t>(2 * nrec2 + 2);
+    uint32_t *nleaf = own.get<uint32_t>(B1);
+    uint64_t *leaf_lo = own.get<uint64_t>(NL + 1), *leaf_lb = own.get<uint64_t>(2 * NL + 2);
+    uint64_t *leaf_hi = own.get<uint64_t>(NL + 1), *leaf_dlo = own.get<uint64_t>(NL + 1);
     // records per leaf: the wide map's digit leaves come out near the target (320: r05 v61; 256 when cut
     // from the sampled histogram, whose leaves vary more: r06 v09, v11), the sampled splitters' leaves
     // vary like 8-sample gaps (256 keeps most under the one-wave capacity)
     const uint32_t target = (uint32_t)env_u64("MRG_TEST_LEAF_TARGET", wm.rin ? (sp.on ? 256 : 320) : 256);
     mrg_wide_launch_l2(wm.rin ? nullptr : K1, K2, bstart, spl1, B1, B1r, target, nleaf, leaf_lo, leaf_hi, leaf_dlo, leaf_lb,
                        bid, s, wm, sp);
-    p.put(sp.redo_flags);
-    p.put(bid);
+    own.put(sp.redo_flags);
+    own.put(bid);
     mark();  // 4: L2
     // ---- leaves: aggregate + sort + line bytes (K1 becomes the output key array)
     WideRes &w = c->wide;
+    Pool &p = c->pool;
     w.release(p);
     w.B1 = B1;
     w.B1r = B1r;
-    w.kout = K1;
+    w.kout = own.release(K1);
     w.ocnt = pget<uint64_t>(p, n + nw + 1);
-    w.nleaf = nleaf;
+    w.nleaf = own.release(nleaf);
     w.leaf_out = pget<uint64_t>(p, NL);
     w.leaf_nd = pget<uint32_t>(p, NL + 1);
     w.leaf_bytes = pget<uint64_t>(p, NL + 1);
@@ -1005,7 +1036,7 @@ void wide_finish(mrg_ctx *c, LongItems li, uint64_t n, uint64_t nw, uint32_t B1,
     HIPCHK(hipMemsetAsync(w.leaf_pk, 0, 4 * NL, s));
     HIPCHK(hipMemsetAsync(w.leaf_nd, 0, 4 * (NL + 1), s));
     HIPCHK(hipMemsetAsync(w.leaf_bytes, 0, 8 * (NL + 1), s));
-    uint32_t *ovf_list = pget<uint32_t>(p, NL);
+    uint32_t *ovf_list = own.get<uint32_t>(NL);
     HIPCHK(hipMemsetAsync(&c->d_cnt[CNT_KEYS], 0, 8, s));
     HIPCHK(hipMemsetAsync(&c->d_cnt[CNT_OVF2], 0, 8, s));
     WideLeafArgs L{};
@@ -1015,11 +1046,11 @@ void wide_finish(mrg_ctx *c, LongItems li, uint64_t n, uint64_t nw, uint32_t B1,
     L.maxd = (uint32_t)env_u64("MRG_TEST_LEAF_CAP", 0);
     L.ocnt = w.ocnt; L.leaf_out = w.leaf_out; L.leaf_nd = w.leaf_nd; L.leaf_bytes = w.leaf_bytes;
     L.leaf_last = w.leaf_last; L.ovf_list = ovf_list; L.ovf_n = &c->d_cnt[CNT_OVF2]; L.nkeys = &c->d_cnt[CNT_KEYS];
-    L.wr = pget<uint64_t>(p, 2 * NL);
-    L.prof = pget<unsigned long long>(p, 16);
+    L.wr = own.get<uint64_t>(2 * NL);
+    L.prof = own.get<unsigned long long>(16);
     HIPCHK(hipMemsetAsync(L.prof, 0, 128, s));
-    L.big_list = pget<uint32_t>(p, NL);
-    L.big_n = pget<unsigned long long>(p, 1);
+    L.big_list = own.get<uint32_t>(NL);
+    L.big_n = own.get<unsigned long long>(1);
     L.leaf_pk = w.leaf_pk;
     // counts packed into the key slots of leaves whose keys are <= 12 bytes: every count fits 32 bits
     // when the job has fewer than 2^32 tokens (MRG_TEST_NO_PACK: the unpacked layout everywhere)
@@ -1092,10 +1123,7 @@ void wide_finish(mrg_ctx *c, LongItems li, uint64_t n, uint64_t nw, uint32_t B1,
         fprintf(stderr, "[mrgpu] wide: %llu records, %llu weighted, B1 %u (x%u), %llu distinct, %llu leaves overflowed\n",
                 (unsigned long long)n, (unsigned long long)nw, B1, B1r, (unsigned long long)w.distinct,
                 (unsigned long long)novf);
-    p.put(K2); p.put(leaf_lo); p.put(leaf_lb); p.put(leaf_hi); p.put(leaf_dlo); p.put(ovf_list); p.put(spl1); p.put(bstart);
-    p.put(L.wr);
-    p.put(L.prof); p.put(L.big_list); p.put(L.big_n);
-    p.put(wk0); p.put(wk1); p.put(wcnt); p.put(wpart);
+    own.put_all();
     c->st.overflow_keys = novf;
     c->keys.n = 0;
     c->st.distinct_keys = w.distinct;
@@ -1113,14 +1141,10 @@ void wide_aggregate(mrg_ctx *c, const MapArgs &A, uint32_t nreg, uint32_t regcap
         wide_aggregate_radix(c, A, nreg, regcap, li);
         return;
     }
-    Pool &p = c->pool;
+    Scratch sc(c->pool);   // what the L1 passes need
+    Scratch fin(c->pool);  // what wide_finish takes over
     hipStream_t s = c->stream;
-    BucketArgs B{};
-    B.pool = A.pool; B.rbase = A.rbase; B.bcap = A.bcap; B.bcount = A.bcount;
-    B.pool16 = A.pool16; B.rbase16 = A.rbase16; B.bcap16 = A.bcap16; B.bcount16 = A.bcount16;
-    B.movf = A.ovf; B.monext = A.onext; B.mocap = A.ocap;
-    B.fk0 = A.fk0; B.fk1 = A.fk1; B.fcnt = A.fcnt; B.fdoc = A.fdoc; B.foff = A.foff;
-    B.nreg = nreg; B.regcap = regcap;
+    const BucketArgs B = map_output(A, nreg, regcap);
     // MRG_DEBUG: HIP-event time of each phase
     const bool dbg = getenv("MRG_DEBUG") != nullptr;
     hipEvent_t pe[8] = {};
@@ -1133,9 +1157,9 @@ void wide_aggregate(mrg_ctx *c, const MapArgs &A, uint32_t nreg, uint32_t regcap
     mark();
     // ---- segment sizes: main (count 1) and flushed tables (weighted)
     const uint64_t nsm = 2ull * nreg * MRG_NBUCKET + MRG_NBUCKET;  // 12-byte regions, overflow lists, 16-byte regions
-    uint64_t *cm = pget<uint64_t>(p, nsm + 1), *om = pget<uint64_t>(p, nsm + 1), *segptr = pget<uint64_t>(p, nsm);
-    uint64_t *cf = pget<uint64_t>(p, nreg + 1), *of = pget<uint64_t>(p, nreg + 1);
-    uint64_t *st1 = pget<uint64_t>(p, mrg_scan_tmp_elems(nsm + 1));
+    uint64_t *cm = sc.get<uint64_t>(nsm + 1), *om = sc.get<uint64_t>(nsm + 1), *segptr = sc.get<uint64_t>(nsm);
+    uint64_t *cf = sc.get<uint64_t>(nreg + 1), *of = sc.get<uint64_t>(nreg + 1);
+    uint64_t *st1 = sc.get<uint64_t>(mrg_scan_tmp_elems(nsm + 1));
     HIPCHK(hipMemsetAsync(cm + nsm, 0, 8, s));
     HIPCHK(hipMemsetAsync(cf + nreg, 0, 8, s));
     mrg_wide_launch_counts(B, cm, segptr, cf, s);
@@ -1150,19 +1174,20 @@ void wide_aggregate(mrg_ctx *c, const MapArgs &A, uint32_t nreg, uint32_t regcap
                                   (unsigned long long)n);
     // ---- weighted keys: HBM-table aggregation of the flushed entries, sorted by (partition, key)
     uint64_t nw = 0;
-    uint64_t *wk0 = pget<uint64_t>(p, nf + 1), *wk1 = pget<uint64_t>(p, nf + 1), *wcnt = pget<uint64_t>(p, nf + 1);
-    uint32_t *wpart = pget<uint32_t>(p, nf + 1);
+    uint64_t *wk0 = fin.get<uint64_t>(nf + 1), *wk1 = fin.get<uint64_t>(nf + 1), *wcnt = fin.get<uint64_t>(nf + 1);
+    uint32_t *wpart = fin.get<uint32_t>(nf + 1);
     if (nf) {
-        uint64_t *fk0 = pget<uint64_t>(p, nf), *fk1 = pget<uint64_t>(p, nf);
-        uint32_t *fc = pget<uint32_t>(p, nf);
+        Scratch t(c->pool);
+        uint64_t *fk0 = t.get<uint64_t>(nf), *fk1 = t.get<uint64_t>(nf);
+        uint32_t *fc = t.get<uint32_t>(nf);
         mrg_wide_launch_flush_gather(B, of, fk0, fk1, fc, s);
         KeySet ks{};
-        ks.k0 = pget<uint64_t>(p, nf); ks.k1 = pget<uint64_t>(p, nf); ks.cnt = pget<uint64_t>(p, nf);
-        ks.hoff = pget<uint64_t>(p, nf); ks.doc = pget<uint32_t>(p, nf); ks.len = pget<uint32_t>(p, nf);
-        ks.part = pget<uint32_t>(p, nf);
+        ks.k0 = t.get<uint64_t>(nf); ks.k1 = t.get<uint64_t>(nf); ks.cnt = t.get<uint64_t>(nf);
+        ks.hoff = t.get<uint64_t>(nf); ks.doc = t.get<uint32_t>(nf); ks.len = t.get<uint32_t>(nf);
+        ks.part = t.get<uint32_t>(nf);
         TableArgs T{};
         T.cap = pow2_at_least(2 * nf);
-        T.tk0 = pget<uint64_t>(p, T.cap); T.tk1 = pget<uint64_t>(p, T.cap); T.tcnt = pget<uint64_t>(p, T.cap);
+        T.tk0 = t.get<uint64_t>(T.cap); T.tk1 = t.get<uint64_t>(T.cap); T.tcnt = t.get<uint64_t>(T.cap);
         T.hash_bits = hash_bits(c);
         HIPCHK(hipMemsetAsync(&c->d_cnt[CNT_KEYS], 0, 8, s));
         mrg_launch_table_clear(T, false, s);
@@ -1171,49 +1196,39 @@ void wide_aggregate(mrg_ctx *c, const MapArgs &A, uint32_t nreg, uint32_t regcap
         read_counters(c);
         nw = c->h_cnt[CNT_KEYS];
         mrg_launch_partition(ks, nullptr, nw, R, s);
-        SortRec *ra = pget<SortRec>(p, nw), *rb = pget<SortRec>(p, nw);
-        void *stmp = p.get(mrg_sort_tmp_bytes(nw));
+        SortRec *ra = t.get<SortRec>(nw), *rb = t.get<SortRec>(nw);
+        void *stmp = t.get<uint8_t>(mrg_sort_tmp_bytes(nw));
         mrg_launch_make_sortrec(ks, nw, nullptr, ra, s);
-        SortPlan plan{};
-        plan.use_part = R > 1;
-        plan.part_bytes = bytes_for(R - 1);
-        plan.use_k0 = plan.use_k1 = true;
         int passes = 0;
-        SortRec *srt = mrg_radix_sort(ra, rb, nw, plan, stmp, s, &passes);
+        SortRec *srt = mrg_radix_sort(ra, rb, nw, part_key_plan(R), stmp, s, &passes);
         mrg_wide_launch_weights(srt, nw, ks, wk0, wk1, wcnt, wpart, s);
         sync(c);
-        p.put(fk0); p.put(fk1); p.put(fc); p.put(ks.k0); p.put(ks.k1); p.put(ks.cnt); p.put(ks.hoff); p.put(ks.doc);
-        p.put(ks.len); p.put(ks.part); p.put(T.tk0); p.put(T.tk1); p.put(T.tcnt); p.put(ra); p.put(rb); p.put(stmp);
     }
     mark();  // 1: weighted keys done
     // ---- L1 buckets: R partitions x B1r quantile ranges of about 2^18 records
     uint32_t B1r = (uint32_t)std::min<uint64_t>((n + ((uint64_t)R << 18) - 1) / ((uint64_t)R << 18), 64);
     B1r = std::max<uint32_t>(1, std::min<uint32_t>(B1r, std::max<uint32_t>(1, 4096 / R)));
     const uint32_t B1 = R * B1r;
-    uint64_t *spl1 = pget<uint64_t>(p, 2ull * R * B1r + 2);
+    uint64_t *spl1 = fin.get<uint64_t>(2ull * R * B1r + 2);
     if (B1r > 1 && n) {
+        Scratch t(c->pool);
         const uint32_t S1 = (uint32_t)std::min<uint64_t>(64ull * B1, n);
-        SortRec *sa = pget<SortRec>(p, S1), *sb = pget<SortRec>(p, S1);
-        void *stmp = p.get(mrg_sort_tmp_bytes(S1));
+        SortRec *sa = t.get<SortRec>(S1), *sb = t.get<SortRec>(S1);
+        void *stmp = t.get<uint8_t>(mrg_sort_tmp_bytes(S1));
         mrg_wide_launch_sample1(B, om, nsm, n, S1, R, sa, s);
-        SortPlan plan{};
-        plan.use_part = R > 1;
-        plan.part_bytes = bytes_for(R - 1);
-        plan.use_k0 = plan.use_k1 = true;
         int passes = 0;
-        SortRec *srt = mrg_radix_sort(sa, sb, S1, plan, stmp, s, &passes);
+        SortRec *srt = mrg_radix_sort(sa, sb, S1, part_key_plan(R), stmp, s, &passes);
         mrg_wide_launch_split1(srt, S1, R, B1r, spl1, s);
         sync(c);
-        p.put(sa); p.put(sb); p.put(stmp);
     }
     mark();  // 2: splitters
     const uint32_t ntiles = (uint32_t)std::max<uint64_t>(1, (n + MRG_WIDE_T1 - 1) / MRG_WIDE_T1);
-    uint32_t *cnt1 = pget<uint32_t>(p, (uint64_t)B1 * ntiles + 1);
-    uint32_t *st2 = pget<uint32_t>(p, mrg_scan_tmp_elems((uint64_t)B1 * ntiles + 1));
-    uint64_t *K1 = pget<uint64_t>(p, 2 * (n + nw) + 2);
-    uint64_t *bstart = pget<uint64_t>(p, B1 + 1);
-    uint16_t *bid = pget<uint16_t>(p, std::max<uint64_t>(n, 1));   // L1 bucket, then L2 leaf, of each record
-    uint8_t *ix1 = getenv("MRG_TEST_NO_L1IX") ? nullptr : pget<uint8_t>(p, 260ull * R);
+    uint32_t *cnt1 = sc.get<uint32_t>((uint64_t)B1 * ntiles + 1);
+    uint32_t *st2 = sc.get<uint32_t>(mrg_scan_tmp_elems((uint64_t)B1 * ntiles + 1));
+    uint64_t *K1 = fin.get<uint64_t>(2 * (n + nw) + 2);
+    uint64_t *bstart = fin.get<uint64_t>(B1 + 1);
+    uint16_t *bid = fin.get<uint16_t>(std::max<uint64_t>(n, 1));   // L1 bucket, then L2 leaf, of each record
+    uint8_t *ix1 = getenv("MRG_TEST_NO_L1IX") ? nullptr : sc.get<uint8_t>(260ull * R);
     if (n) {
         mrg_wide_launch_l1(B, om, segptr, nsm, n, spl1, R, B1r, cnt1, ntiles, K1, bid, ix1, false, s);
         mrg_scan_u32(cnt1, cnt1, (uint64_t)B1 * ntiles, st2, s);
@@ -1222,10 +1237,9 @@ void wide_aggregate(mrg_ctx *c, const MapArgs &A, uint32_t nreg, uint32_t regcap
         HIPCHK(hipMemsetAsync(cnt1, 0, 4ull * B1 * ntiles, s));
     }
     mrg_wide_launch_bstart(cnt1, B1, ntiles, n, bstart, s);
-    p.put(cnt1); p.put(st2); p.put(cm); p.put(om); p.put(cf); p.put(of); p.put(st1); p.put(segptr);
-    if (ix1) p.put(ix1);
+    sc.put_all();
     mark();  // 3: L1
-    wide_finish(c, li, n, nw, B1, B1r, K1, bstart, spl1, bid, wk0, wk1, wcnt, wpart, dbg, pe, npe, WmapIn{});
+    wide_finish(c, fin, li, n, nw, B1, B1r, K1, bstart, spl1, bid, wk0, wk1, wcnt, wpart, dbg, pe, npe, WmapIn{});
 }
 
 void need_job(mrg_ctx *c) {
@@ -1240,7 +1254,7 @@ void job_begin(mrg_ctx *c, int app, uint32_t R, uint32_t flags) {
     flush_stage(c);     // (nothing is pending between jobs: every map launch flushes first)
     c->stage_used = 0;  // the previous job's staged copies are done
     c->pend_lo = 0;
-    keys_release(c);
+    keysbuf_release(c->pool, c->keys);
     c->wide.release(c->pool);
     acc_release(c);
     c->keyed = false;
@@ -1280,7 +1294,8 @@ struct WideMapPlan {
 // MRG_WIDE_MAP=1).  Taken when the sample is near-unique: fewer than 1 in 16 sampled tokens repeat a
 // sampled neighbour in key order.  (Until r05 only the hint sampled: a cold near-unique job ran the
 // LDS-combine map, overflowed its tail regions, reran it and took the L1 count + scatter passes.)
-WideMapPlan wide_map_plan(mrg_ctx *c, const uint64_t *d_doc_off, uint32_t nd, uint64_t total, int grid) {
+// The splitters (and their index) of a plan that is on are blocks of `keep`.
+WideMapPlan wide_map_plan(mrg_ctx *c, Scratch &keep, const uint64_t *d_doc_off, uint32_t nd, uint64_t total, int grid) {
     WideMapPlan P;
     const char *env = getenv("MRG_WIDE_MAP");
     P.forced = env && atoi(env) != 0;
@@ -1291,55 +1306,46 @@ WideMapPlan wide_map_plan(mrg_ctx *c, const uint64_t *d_doc_off, uint32_t nd, ui
     uint32_t B1r = std::min<uint32_t>(64, std::max<uint32_t>(1, MRG_WMAP_MAXB1 / R));
     if (const uint64_t t = env_u64("MRG_TEST_WMAP_B1R", 0)) B1r = (uint32_t)std::min<uint64_t>(B1r, t);
     const uint32_t B1 = R * B1r;
-    Pool &p = c->pool;
+    Scratch sc(c->pool);
     hipStream_t s = c->stream;
     const uint32_t S = (uint32_t)std::min<uint64_t>(64ull * B1, 1u << 20);
     flush_stage(c);  // the document tables, read by the sampling kernels
     if (!P.forced && !c->wide_hint) {  // no hint (a cold context): the one-launch test on 8192 samples first
+        Scratch t(c->pool);
         const uint32_t S0 = std::min<uint32_t>(S, 8192);
-        SortRec *s0 = pget<SortRec>(p, S0);
-        unsigned long long *d0 = pget<unsigned long long>(p, 2);
+        SortRec *s0 = t.get<SortRec>(S0);
+        unsigned long long *d0 = t.get<unsigned long long>(2);
         mrg_wide_launch_sample_text(c->d_in, d_doc_off, nd, total, S0, R, s0, s);
         mrg_wide_launch_sample_uniq(s0, S0, d0, s);
         unsigned long long *h0 = &c->h_cnt[CNT_N];  // pinned scratch
         HIPCHK(hipMemcpyAsync(h0, d0, 16, hipMemcpyDeviceToHost, s));
         sync(c);
-        const unsigned long long rep = h0[0];
-        p.put(s0); p.put(d0);
-        if (rep * 16 >= S0) {  // repeats: the LDS combine pays
+        if (h0[0] * 16 >= S0) {  // repeats: the LDS combine pays
             P.repeats = true;
             return P;
         }
     }
-    SortRec *sa = pget<SortRec>(p, S), *sb = pget<SortRec>(p, S);
-    void *stmp = p.get(mrg_sort_tmp_bytes(S));
-    unsigned long long *dups = pget<unsigned long long>(p, 2);
+    SortRec *sa = sc.get<SortRec>(S), *sb = sc.get<SortRec>(S);
+    void *stmp = sc.get<uint8_t>(mrg_sort_tmp_bytes(S));
+    unsigned long long *dups = sc.get<unsigned long long>(2);
     HIPCHK(hipMemsetAsync(dups, 0, 16, s));
     mrg_wide_launch_sample_text(c->d_in, d_doc_off, nd, total, S, R, sa, s);
-    SortPlan plan{};
-    plan.use_part = R > 1;
-    plan.part_bytes = bytes_for(R - 1);
-    plan.use_k0 = plan.use_k1 = true;
     int passes = 0;
-    SortRec *srt = mrg_radix_sort(sa, sb, S, plan, stmp, s, &passes);
+    SortRec *srt = mrg_radix_sort(sa, sb, S, part_key_plan(R), stmp, s, &passes);
     mrg_wide_launch_sample_dups(srt, S, dups, s);
-    uint64_t *spl1 = pget<uint64_t>(p, 2ull * R * B1r + 2);
+    uint64_t *spl1 = sc.get<uint64_t>(2ull * R * B1r + 2);
     uint8_t *ix1 = nullptr;
     if (B1r > 1) {
         mrg_wide_launch_split1(srt, S, R, B1r, spl1, s);
         if (B1r >= 5 && R <= MRG_WMAP_IXR) {
-            ix1 = pget<uint8_t>(p, (uint64_t)MRG_WIDE_IX1 * R);
+            ix1 = sc.get<uint8_t>((uint64_t)MRG_WIDE_IX1 * R);
             mrg_wide_launch_l1ix(spl1, R, B1r, ix1, s);
         }
     }
     unsigned long long dh[2] = {0, 0};
     HIPCHK(hipMemcpyAsync(dh, dups, 16, hipMemcpyDeviceToHost, s));
     sync(c);
-    const unsigned long long nd_h = dh[0];
-    p.put(sa); p.put(sb); p.put(stmp); p.put(dups);
-    if (!P.forced && nd_h * 16 >= S) {  // repeats: the LDS combine pays
-        p.put(spl1);
-        p.put(ix1);
+    if (!P.forced && dh[0] * 16 >= S) {  // repeats: the LDS combine pays
         c->wide_hint = false;
         return P;
     }
@@ -1352,8 +1358,8 @@ WideMapPlan wide_map_plan(mrg_ctx *c, const uint64_t *d_doc_off, uint32_t nd, ui
     if (const char *e = getenv("MRG_TEST_WMAP_W12")) P.w12 = atoi(e) != 0;
     P.B1 = B1;
     P.B1r = B1r;
-    P.spl1 = spl1;
-    P.ix1 = ix1;
+    P.spl1 = keep.adopt(sc.release(spl1));
+    P.ix1 = keep.adopt(sc.release(ix1));
     return P;
 }
 
@@ -1385,24 +1391,121 @@ MapSteal map_steal(uint64_t n_chunks, int grid) {
     return m;
 }
 
-// the steal plan into a launch's arguments, with its pool counters (zeroed on the stream)
-void set_steal(mrg_ctx *c, MapArgs &A, MapBufs &M, const MapSteal &ms, uint64_t n_chunks) {
+// ---- what the LDS-combine map (job_map) and the wide map (job_map_wide) share.  The device blocks of
+// one launch belong to a Scratch of the attempt (`att`), which a rerun returns before it takes its own.
+
+// The input of a map: the document, block and id tables on the device, the grid, the documents' ids.
+struct MapIn {
+    const uint64_t *doc_off = nullptr, *chunk_base = nullptr;
+    const uint32_t *doc_id = nullptr;
+    uint32_t nd = 0;
+    uint64_t n_chunks = 0, total = 0;
+    int grid = 0;
+    std::vector<uint32_t> ids;
+};
+
+// the steal plan into a launch's arguments, with its pool counters (zeroed by a staged write)
+void set_steal(mrg_ctx *c, Scratch &att, MapArgs &A, const MapSteal &ms, uint64_t n_chunks) {
     if (n_chunks * MRG_MAP_NSUB >= 0xFFFFFFFFull) raise(MRG_ENOMEM, "input too large for one map launch");
     A.n_static = ms.n_static;
     A.steal_max = ms.steal_max;
     A.pool_ctr = nullptr;
     if (ms.n_static < n_chunks) {
-        if (!M.pool_ctr) M.pool_ctr = pget<unsigned long long>(c->pool, 8 * 16);
-        stage_fill(c, M.pool_ctr, 0, 8ull * 8 * 16);
-        A.pool_ctr = M.pool_ctr;
+        A.pool_ctr = att.get<unsigned long long>(8 * 16);
+        stage_fill(c, A.pool_ctr, 0, 8ull * 8 * 16);
     }
 }
 
-void job_map_wide(mrg_ctx *c, WideMapPlan &wp, uint64_t *d_doc_off, uint64_t *d_cb, uint32_t *d_ids, uint32_t nd,
-                  uint64_t n_chunks, uint64_t total, int grid, const std::vector<uint32_t> &ids) {
-    Pool &p = c->pool;
+// The arguments both maps' launches have: the input, the counters, the long-token regions (one of lper
+// records per workgroup + a shared list of lovf), the non-ASCII tile lists (one entry per tile of a
+// workgroup's share and steal budget at most) and the steal plan.  Returns the long-token slots.
+// knobs: MRG_TEST_LONG_PER / MRG_TEST_LONG_LIST apply (the LDS-combine map's first launch only: a
+// rerun grows the regions from the measured demand).
+uint64_t map_args_shared(mrg_ctx *c, Scratch &att, MapArgs &A, const MapIn &in, const MapSteal &ms, uint64_t lcap,
+                         bool knobs) {
+    A.in = c->d_in;
+    A.doc_off = in.doc_off;
+    A.chunk_base = in.chunk_base;
+    A.doc_id = in.doc_id;
+    A.n_docs = in.nd;
+    A.n_chunks = in.n_chunks;
+    A.counters = c->d_cnt;
+    A.hash_bits = hash_bits(c);
+    uint64_t lper = std::max<uint64_t>(c->lper_hint, (uint64_t)(ms.wg_scale * (double)((lcap + in.grid - 1) / in.grid)) + 16);
+    uint64_t lovf = lcap / 4 + 1024;
+    if (knobs) {
+        if (const uint64_t t = env_u64("MRG_TEST_LONG_PER", 0)) lper = t;
+        if (const uint64_t t = env_u64("MRG_TEST_LONG_LIST", 0)) lovf = t;
+    }
+    if (lper > 0xFFFFFFF0ull) raise(MRG_ENOMEM, "input too large for one map launch");
+    const uint64_t lslots = (uint64_t)in.grid * lper + lovf;
+    A.lstart = att.get<uint64_t>(lslots);
+    A.llen = att.get<uint32_t>(lslots);
+    A.ldoc = att.get<uint32_t>(lslots);
+    A.lcount = att.get<uint32_t>((uint64_t)in.grid);
+    A.lper = (uint32_t)lper;
+    A.lovf = lovf;
+    A.kwords = (uint32_t)(MRG_MAP_NSUB * ms.per_wg_blocks);
+    A.gbits = att.get<uint32_t>((uint64_t)in.grid * A.kwords);
+    set_steal(c, att, A, ms, in.n_chunks);
+    return lslots;
+}
+
+// A workgroup's long tokens overflowed its region and the shared list: grow both (remembered).
+void grow_long_regions(mrg_ctx *c, const MapArgs &A, int grid, uint64_t &lcap) {
+    std::vector<uint32_t> lc((uint64_t)grid);
+    HIPCHK(hipMemcpyAsync(lc.data(), A.lcount, 4ull * grid, hipMemcpyDeviceToHost, c->stream));
+    sync(c);
+    const uint64_t mx = *std::max_element(lc.begin(), lc.end());
+    const uint64_t nl = c->h_cnt[CNT_LONG];
+    c->lper_hint = mx + mx / 4 + 64;
+    lcap = c->long_hint = std::max<uint64_t>(lcap, nl + nl / 8 + 1024);
+}
+
+// mrg_stats of a finished map, from its counters
+void map_stats(mrg_ctx *c, uint32_t launches, uint64_t total) {
+    c->st.ms_map = ev_ms(c, c->ev, 0, 1);
+    c->st.map_launches = launches;
+    c->st.input_bytes = total;
+    c->st.tokens = c->h_cnt[CNT_TOKENS];
+    c->st.long_tokens = c->h_cnt[CNT_LONG];
+    c->st.map_records = c->h_cnt[CNT_REC];
+    c->st.nonascii_tiles = c->h_cnt[CNT_NONASCII];
+}
+
+// The map found invalid UTF-8 (the reference's read_to_string panic): raise it with the document.
+void check_map_utf8(mrg_ctx *c, const std::vector<uint32_t> &ids) {
+    const uint64_t errpos = c->h_cnt[CNT_ERRPOS];
+    if (errpos == ~0ull) return;
+    const uint32_t nd = (uint32_t)ids.size();
+    uint32_t d = 0;
+    while (d + 1 < nd && c->doc_off[d + 1] <= errpos) ++d;
+    const char *nm = ids[d] < c->names.size() ? c->names[ids[d]].c_str() : "";
+    raise(MRG_EUTF8, "stream did not contain valid UTF-8: document %u (id %u%s%s), byte offset %llu", d, ids[d],
+          *nm ? ", " : "", nm, (unsigned long long)(errpos - c->doc_off[d]));
+}
+
+// The map's long tokens: the workgroups' regions and the shared list packed densely (blocks of sc).
+LongItems long_items(mrg_ctx *c, Scratch &sc, const MapArgs &A, int grid) {
+    LongItems li{};
+    li.base = c->d_in;
+    li.cnt = nullptr;
+    li.n = c->h_cnt[CNT_LONG];
+    if (li.n) {
+        uint64_t *dstart = sc.get<uint64_t>(li.n);
+        uint32_t *dlen = sc.get<uint32_t>(li.n), *ddoc = sc.get<uint32_t>(li.n);
+        mrg_launch_long_compact(A, grid, dstart, dlen, ddoc, c->stream);
+        li.start = dstart; li.rawlen = dlen; li.doc = ddoc;
+    }
+    return li;
+}
+
+// (sc: the blocks of the whole call, with the input tables and the plan's splitters)
+void job_map_wide(mrg_ctx *c, Scratch &sc, const WideMapPlan &wp, const MapIn &in) {
     hipStream_t s = c->stream;
     const uint32_t B1 = wp.B1;
+    const int grid = in.grid;
+    const uint64_t total = in.total, n_chunks = in.n_chunks;
     // records per (bucket, workgroup) region: the splitters make the buckets about equal; a token per
     // ~10 input bytes, +30 %, or the last run's demand
     const MapSteal ms = map_steal(n_chunks, grid);
@@ -1411,9 +1514,7 @@ void job_map_wide(mrg_ctx *c, WideMapPlan &wp, uint64_t *d_doc_off, uint64_t *d_
     if (const uint64_t t = env_u64("MRG_TEST_WMAP_CAP", 0)) wcap = t;
     uint64_t lcap = std::max<uint64_t>(c->long_hint, total / 1024 + 1024);
     MapArgs A{};
-    MapBufs M;
-    uint64_t *wrec = nullptr, *wl16 = nullptr;
-    uint32_t *wcnt = nullptr, *wl16n = nullptr;
+    Scratch att(c->pool);
     uint32_t launches = 0;
     bool w12 = wp.w12;
     // the 16-byte lists of 12-byte regions: four times the sampled share of such keys, at least 2 K each
@@ -1422,55 +1523,34 @@ void job_map_wide(mrg_ctx *c, WideMapPlan &wp, uint64_t *d_doc_off, uint64_t *d_
     if (const uint64_t t = env_u64("MRG_TEST_WMAP_L16", 0)) wl16cap = t;
     for (;;) {
         if (wcap > 0xFFFFFFF0ull) raise(MRG_ENOMEM, "input too large for one map launch");
-        M.dargs = pget<MapArgs>(p, 1);
-        uint64_t lper = std::max<uint64_t>(c->lper_hint, (uint64_t)(ms.wg_scale * (double)((lcap + grid - 1) / grid)) + 16);
-        const uint64_t lovf = lcap / 4 + 1024;
-        const uint64_t lslots = (uint64_t)grid * lper + lovf;
-        M.lstart = pget<uint64_t>(p, lslots);
-        M.llen = pget<uint32_t>(p, lslots);
-        M.ldoc = pget<uint32_t>(p, lslots);
-        M.lcount = pget<uint32_t>(p, (uint64_t)grid);
+        MapArgs *dargs = att.get<MapArgs>(1);
         A = MapArgs{};
-        A.kwords = (uint32_t)(MRG_MAP_NSUB * ms.per_wg_blocks);
-        M.gbits = pget<uint32_t>(p, (uint64_t)grid * A.kwords);
-        set_steal(c, A, M, ms, n_chunks);
+        map_args_shared(c, att, A, in, ms, lcap, false);
         const uint64_t nslots = (uint64_t)B1 * grid * wcap;
-        wrec = pget<uint64_t>(p, w12 ? (12 * nslots + 16 + 7) / 8 : 2 * nslots + 2);
-        wcnt = pget<uint32_t>(p, (uint64_t)B1 * grid);
+        A.wrec = att.get<uint64_t>(w12 ? (12 * nslots + 16 + 7) / 8 : 2 * nslots + 2);
+        A.wcnt = att.get<uint32_t>((uint64_t)B1 * grid);
         if (w12) {
             if (wl16cap > 0xFFFFFFF0ull) raise(MRG_ENOMEM, "input too large for one map launch");
-            wl16 = pget<uint64_t>(p, 2ull * B1 * wl16cap + 2);
-            wl16n = pget<uint32_t>(p, B1);
-            HIPCHK(hipMemsetAsync(wl16n, 0, 4ull * B1, s));
+            A.wl16 = att.get<uint64_t>(2ull * B1 * wl16cap + 2);
+            A.wl16n = att.get<uint32_t>(B1);
+            HIPCHK(hipMemsetAsync(A.wl16n, 0, 4ull * B1, s));
         }
-        A.in = c->d_in;
-        A.doc_off = d_doc_off;
-        A.chunk_base = d_cb;
-        A.doc_id = d_ids;
-        A.n_docs = nd;
-        A.n_chunks = n_chunks;
-        A.lstart = M.lstart; A.llen = M.llen; A.ldoc = M.ldoc; A.lper = (uint32_t)lper; A.lovf = lovf;
-        A.lcount = M.lcount;
-        A.gbits = M.gbits;
-        A.counters = c->d_cnt;
-        A.hash_bits = hash_bits(c);
-        A.wrec = wrec; A.wcnt = wcnt; A.wspl = wp.spl1; A.wix = wp.ix1;
+        A.wspl = wp.spl1; A.wix = wp.ix1;
         A.wR = c->R; A.wB1r = wp.B1r; A.wcap = (uint32_t)wcap;
-        A.w12 = w12 ? 1u : 0u; A.wl16cap = (uint32_t)wl16cap; A.wl16 = wl16; A.wl16n = wl16n;
+        A.w12 = w12 ? 1u : 0u; A.wl16cap = (uint32_t)wl16cap;
         // the kernel's LDS cursors, splitters and index rows are sized by these bounds (k_map.hip)
         if (A.wB1r == 0 || (uint64_t)A.wR * A.wB1r > MRG_WMAP_MAXB1 || (A.wix && A.wR > MRG_WMAP_IXR))
             raise(MRG_EINVAL, "wide map plan exceeds the kernel's LDS bounds");
         HIPCHK(hipMemsetAsync(c->d_cnt, 0, sizeof(unsigned long long) * CNT_N, s));
         HIPCHK(hipMemsetAsync(&c->d_cnt[CNT_ERRPOS], 0xFF, sizeof(unsigned long long), s));
         flush_stage(c);  // (set_steal's pool counters)
-        ev_rec(c, 0);
-        h2d(c, M.dargs, &A, sizeof(MapArgs));
-        mrg_launch_map(nullptr, M.dargs, c->app, grid, c->lds_cap, s, true);
-        ev_rec(c, 1);
+        ev_rec(c, c->ev, 0);
+        h2d(c, dargs, &A, sizeof(MapArgs));
+        mrg_launch_map(nullptr, dargs, c->app, grid, c->lds_cap, s, true);
+        ev_rec(c, c->ev, 1);
         HIPCHK(hipGetLastError());
         ++launches;
         read_counters(c);
-        const uint64_t nl = c->h_cnt[CNT_LONG];
         const bool long_full = c->h_cnt[CNT_LONGX] > A.lovf;
         const bool l16_full = c->h_cnt[CNT_W16] != 0;
         if (c->h_cnt[CNT_OVF] == 0 && !long_full && !l16_full) break;
@@ -1480,93 +1560,55 @@ void job_map_wide(mrg_ctx *c, WideMapPlan &wp, uint64_t *d_doc_off, uint64_t *d_
         }
         if (c->h_cnt[CNT_OVF]) {  // a region overflowed: every region sized to the largest demand
             std::vector<uint32_t> wc((uint64_t)B1 * grid);
-            HIPCHK(hipMemcpyAsync(wc.data(), wcnt, 4ull * wc.size(), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(wc.data(), A.wcnt, 4ull * wc.size(), hipMemcpyDeviceToHost, s));
             sync(c);
             const uint64_t mx = *std::max_element(wc.begin(), wc.end());
             wcap = c->wcap_hint = std::max<uint64_t>(wcap, mx + mx / 4 + 64);
         }
-        if (long_full) {
-            std::vector<uint32_t> lc((uint64_t)grid);
-            HIPCHK(hipMemcpyAsync(lc.data(), M.lcount, 4ull * grid, hipMemcpyDeviceToHost, s));
-            sync(c);
-            const uint64_t mx = *std::max_element(lc.begin(), lc.end());
-            c->lper_hint = mx + mx / 4 + 64;
-            lcap = c->long_hint = std::max<uint64_t>(lcap, nl + nl / 8 + 1024);
-        }
+        if (long_full) grow_long_regions(c, A, grid, lcap);
         if (getenv("MRG_DEBUG"))
             fprintf(stderr, "[mrgpu] wide map rerun: region overflow %llu (cap now %llu), long %llu\n",
-                    (unsigned long long)c->h_cnt[CNT_OVF], (unsigned long long)wcap, (unsigned long long)nl);
-        M.release(p);
-        p.put(wrec); p.put(wcnt); p.put(wl16); p.put(wl16n);
-        wl16 = nullptr;
-        wl16n = nullptr;
+                    (unsigned long long)c->h_cnt[CNT_OVF], (unsigned long long)wcap,
+                    (unsigned long long)c->h_cnt[CNT_LONG]);
+        att.put_all();
     }
-    c->st.ms_map = ev_ms(c, 0, 1);
-    c->st.map_launches = launches;
-    c->st.input_bytes = total;
-    c->st.tokens = c->h_cnt[CNT_TOKENS];
-    c->st.long_tokens = c->h_cnt[CNT_LONG];
-    c->st.map_records = c->h_cnt[CNT_REC];
-    c->st.nonascii_tiles = c->h_cnt[CNT_NONASCII];
+    map_stats(c, launches, total);
     c->st.tail_records_16 = 0;
     c->st.map_spill = 0;
-    const uint64_t errpos = c->h_cnt[CNT_ERRPOS];
-    auto release_all = [&]() {
-        M.release(p);
-        p.put(wrec); p.put(wcnt); p.put(wl16); p.put(wl16n);
-        p.put(d_doc_off); p.put(d_cb); p.put(d_ids);
-    };
-    if (errpos != ~0ull) {
-        release_all();
-        p.put(wp.spl1); p.put(wp.ix1);
-        uint32_t d = 0;
-        while (d + 1 < nd && c->doc_off[d + 1] <= errpos) ++d;
-        const char *nm = ids[d] < c->names.size() ? c->names[ids[d]].c_str() : "";
-        raise(MRG_EUTF8, "stream did not contain valid UTF-8: document %u (id %u%s%s), byte offset %llu", d, ids[d],
-              *nm ? ", " : "", nm, (unsigned long long)(errpos - c->doc_off[d]));
-    }
-    ev_rec(c, 2);
-    LongItems li{};
-    li.base = c->d_in; li.cnt = nullptr;
-    li.n = c->h_cnt[CNT_LONG];
-    if (li.n) {
-        M.dstart = pget<uint64_t>(p, li.n);
-        M.dlen = pget<uint32_t>(p, li.n);
-        M.ddoc = pget<uint32_t>(p, li.n);
-        mrg_launch_long_compact(A, grid, M.dstart, M.dlen, M.ddoc, s);
-    }
-    li.start = M.dstart; li.rawlen = M.dlen; li.doc = M.ddoc;
+    check_map_utf8(c, in.ids);
+    ev_rec(c, c->ev, 2);
+    const LongItems li = long_items(c, att, A, grid);
     // ---- the regions as L1 buckets: per-bucket segment starts, bucket offsets, then L2 and the leaves
-    uint32_t *soff = pget<uint32_t>(p, (uint64_t)B1 * (grid + 2));
-    uint64_t *nbk = pget<uint64_t>(p, (uint64_t)B1 + 1);
-    uint64_t *bstart = pget<uint64_t>(p, (uint64_t)B1 + 1);
-    uint64_t *tmp = pget<uint64_t>(p, mrg_scan_tmp_elems((uint64_t)B1 + 1));
+    Scratch fin(c->pool);  // what wide_finish takes over
+    uint32_t *soff = att.get<uint32_t>((uint64_t)B1 * (grid + 2));
+    uint64_t *nbk = att.get<uint64_t>((uint64_t)B1 + 1);
+    uint64_t *bstart = fin.get<uint64_t>((uint64_t)B1 + 1);
+    uint64_t *tmp = att.get<uint64_t>(mrg_scan_tmp_elems((uint64_t)B1 + 1));
     HIPCHK(hipMemsetAsync(nbk + B1, 0, 8, s));
-    mrg_wmap_launch_seg(wcnt, B1, (uint32_t)grid, (uint32_t)wcap, w12 ? wl16n : nullptr, (uint32_t)wl16cap, soff, nbk, s);
+    mrg_wmap_launch_seg(A.wcnt, B1, (uint32_t)grid, (uint32_t)wcap, A.wl16n, (uint32_t)wl16cap, soff, nbk, s);
     mrg_scan_u64(nbk, bstart, (uint64_t)B1 + 1, tmp, s);  // bstart[B1] = records
     uint64_t n = 0;
     HIPCHK(hipMemcpyAsync(&n, bstart + B1, 8, hipMemcpyDeviceToHost, s));
     sync(c);
     if (n >= 0xFFFFFFF0ull) raise(MRG_ENOMEM, "wide aggregation: %llu records exceed one GPU's 32-bit record index",
                                   (unsigned long long)n);
-    uint64_t *K1 = pget<uint64_t>(p, 2 * n + 2);  // the leaves' output keys
-    uint16_t *bid = pget<uint16_t>(p, std::max<uint64_t>(n, 1));
-    uint64_t *wk0 = pget<uint64_t>(p, 1), *wk1 = pget<uint64_t>(p, 1), *wk = pget<uint64_t>(p, 1);
-    uint32_t *wpart = pget<uint32_t>(p, 1);
+    uint64_t *K1 = fin.get<uint64_t>(2 * n + 2);  // the leaves' output keys
+    uint16_t *bid = fin.get<uint16_t>(std::max<uint64_t>(n, 1));
+    uint64_t *wk0 = fin.get<uint64_t>(1), *wk1 = fin.get<uint64_t>(1), *wk = fin.get<uint64_t>(1);
+    uint32_t *wpart = fin.get<uint32_t>(1);
+    fin.adopt(sc.release(wp.spl1));
     const bool dbg = getenv("MRG_DEBUG") != nullptr;
     hipEvent_t pe[8] = {};
     int npe = 0;
     c->st.agg_path = 2;
     c->spec_agg = false;
     WmapIn wm;
-    wm.rin = wrec; wm.soff = soff; wm.grid = (uint32_t)grid; wm.wcap = (uint32_t)wcap;
-    wm.w12 = w12 ? 1u : 0u; wm.wl16cap = (uint32_t)wl16cap; wm.wl16 = wl16;
-    wide_finish(c, li, n, 0, B1, wp.B1r, K1, bstart, wp.spl1, bid, wk0, wk1, wk, wpart, dbg, pe, npe, wm);
-    p.put(soff); p.put(nbk); p.put(tmp); p.put(wp.ix1);
+    wm.rin = A.wrec; wm.soff = soff; wm.grid = (uint32_t)grid; wm.wcap = (uint32_t)wcap;
+    wm.w12 = w12 ? 1u : 0u; wm.wl16cap = (uint32_t)wl16cap; wm.wl16 = A.wl16;
+    wide_finish(c, fin, li, n, 0, B1, wp.B1r, K1, bstart, wp.spl1, bid, wk0, wk1, wk, wpart, dbg, pe, npe, wm);
     c->st.map_kind = 1;
-    ev_rec(c, 3);
-    release_all();
-    c->st.ms_aggregate = ev_ms(c, 2, 3);
+    ev_rec(c, c->ev, 3);
+    c->st.ms_aggregate = ev_ms(c, c->ev, 2, 3);
     // the hint holds while the input stays near-unique
     c->wide_hint = 2 * c->st.distinct_keys > c->st.tokens;
     c->wc_sized = true;
@@ -1579,31 +1621,35 @@ void job_map(mrg_ctx *c) {
     c->wide.release(c->pool);  // a second map of the same job replaces the first one's keys
     c->mapped = c->reduced = c->keyed = false;
     c->st.spec_agg = c->st.agg_path = c->st.map_kind = 0;
-    Pool &p = c->pool;
+    Scratch sc(c->pool);  // the blocks of the whole call
+    StageDrop undo(c);    // (an error exit returns blocks that staged writes still point at)
     hipStream_t s = c->stream;
     const uint32_t nd = (uint32_t)c->doc_off.size() - 1;
     const uint64_t total = c->doc_off[nd] - c->doc_off[0];
     std::vector<uint64_t> cb(nd + 1, 0);
     for (uint32_t d = 0; d < nd; ++d) cb[d + 1] = cb[d] + mrg_map_tiles(c->doc_off[d], c->doc_off[d + 1]);
     const uint64_t n_chunks = cb[nd];
-    std::vector<uint32_t> ids = c->doc_ids;
-    if (ids.empty()) for (uint32_t d = 0; d < nd; ++d) ids.push_back(d);
+    MapIn in;
+    in.ids = c->doc_ids;
+    if (in.ids.empty()) for (uint32_t d = 0; d < nd; ++d) in.ids.push_back(d);
 
-    uint64_t *d_doc_off = pget<uint64_t>(p, nd + 1), *d_cb = pget<uint64_t>(p, nd + 1);
-    uint32_t *d_ids = pget<uint32_t>(p, nd);
+    uint64_t *d_doc_off = sc.get<uint64_t>(nd + 1), *d_cb = sc.get<uint64_t>(nd + 1);
+    uint32_t *d_ids = sc.get<uint32_t>(nd);
     stage_h2d(c, d_doc_off, c->doc_off.data(), 8ull * (nd + 1));
     stage_h2d(c, d_cb, cb.data(), 8ull * (nd + 1));
-    stage_h2d(c, d_ids, ids.data(), 4ull * nd);
+    stage_h2d(c, d_ids, in.ids.data(), 4ull * nd);
 
     if (!c->map_grid) c->map_grid = mrg_map_max_grid(c->app, c->lds_cap, c->device);
     // (MRG_TEST_MAP_GRID: more workgroups than fit at once, run in waves: an A/B knob for load balance)
     const uint64_t grid_want = env_u64("MRG_TEST_MAP_GRID", (uint64_t)c->map_grid);
     const int grid = (int)std::max<uint64_t>(1, std::min<uint64_t>(grid_want, n_chunks));
+    in.doc_off = d_doc_off; in.chunk_base = d_cb; in.doc_id = d_ids;
+    in.nd = nd; in.n_chunks = n_chunks; in.total = total; in.grid = grid;
     bool cold_repeats = false;  // a cold context whose sample found repeats: queue the aggregation too
     {  // near-unique input: the wide map (every key straight to its L1 bucket)
-        WideMapPlan wp = wide_map_plan(c, d_doc_off, nd, total, grid);
+        const WideMapPlan wp = wide_map_plan(c, sc, d_doc_off, nd, total, grid);
         if (wp.on) {
-            job_map_wide(c, wp, d_doc_off, d_cb, d_ids, nd, n_chunks, total, grid, ids);
+            job_map_wide(c, sc, wp, in);
             return;
         }
         cold_repeats = wp.repeats;
@@ -1640,8 +1686,8 @@ void job_map(mrg_ctx *c) {
     }
     if (const uint64_t t = env_u64("MRG_TEST_OVF_CAP", 0)) ocap = t;
     MapArgs A{};
-    MapBufs M;
-    AggLaunch spec;  // the aggregation launched right behind the map (wc, the last job took the bucket path)
+    Scratch att(c->pool);
+    AggLaunch spec(c->pool);  // the aggregation launched right behind the map (wc, the last job took the bucket path)
     uint32_t launches = 0;
     for (;;) {
         std::vector<uint64_t> rbase(MRG_NBUCKET, 0), rbase16(MRG_NBUCKET, 0);
@@ -1657,76 +1703,45 @@ void job_map(mrg_ctx *c) {
             rbase16[b] = rtot16;
             rtot16 += (uint64_t)grid * bcap16[b];
         }
-        M.rbase = pget<uint64_t>(p, MRG_NBUCKET);
-        M.bcap = pget<uint32_t>(p, MRG_NBUCKET);
-        M.bcount = pget<uint32_t>(p, (uint64_t)grid * MRG_NBUCKET);
-        M.rbase16 = pget<uint64_t>(p, MRG_NBUCKET);
-        M.bcap16 = pget<uint32_t>(p, MRG_NBUCKET);
-        M.bcount16 = pget<uint32_t>(p, (uint64_t)grid * MRG_NBUCKET);
-        M.dargs = pget<MapArgs>(p, 1);
+        uint64_t *d_rbase = att.get<uint64_t>(MRG_NBUCKET);
+        uint32_t *d_bcap = att.get<uint32_t>(MRG_NBUCKET);
+        A.bcount = att.get<uint32_t>((uint64_t)grid * MRG_NBUCKET);
+        uint64_t *d_rbase16 = att.get<uint64_t>(MRG_NBUCKET);
+        uint32_t *d_bcap16 = att.get<uint32_t>(MRG_NBUCKET);
+        A.bcount16 = att.get<uint32_t>((uint64_t)grid * MRG_NBUCKET);
+        MapArgs *dargs = att.get<MapArgs>(1);
         if (ocap > 0xFFFFFFF0ull) raise(MRG_ENOMEM, "input too large for one map launch");
-        M.ovf = pget<uint64_t>(p, (uint64_t)MRG_NBUCKET * ocap * RW);
-        M.onext = pget<uint32_t>(p, MRG_NBUCKET);
-        stage_fill(c, M.onext, 0, 4ull * MRG_NBUCKET);
-        stage_h2d(c, M.rbase, rbase.data(), 8ull * MRG_NBUCKET);
-        stage_h2d(c, M.bcap, bcap32.data(), 4ull * MRG_NBUCKET);
-        stage_h2d(c, M.rbase16, rbase16.data(), 8ull * MRG_NBUCKET);
-        stage_h2d(c, M.bcap16, bcap16_32.data(), 4ull * MRG_NBUCKET);
-        A.in = c->d_in;
-        A.doc_off = d_doc_off;
-        A.chunk_base = d_cb;
-        A.doc_id = d_ids;
-        A.n_docs = nd;
-        A.n_chunks = n_chunks;
+        A.ovf = att.get<uint64_t>((uint64_t)MRG_NBUCKET * ocap * RW);
+        A.onext = att.get<uint32_t>(MRG_NBUCKET);
+        A.ocap = (uint32_t)ocap;
+        stage_fill(c, A.onext, 0, 4ull * MRG_NBUCKET);
+        stage_h2d(c, d_rbase, rbase.data(), 8ull * MRG_NBUCKET);
+        stage_h2d(c, d_bcap, bcap32.data(), 4ull * MRG_NBUCKET);
+        stage_h2d(c, d_rbase16, rbase16.data(), 8ull * MRG_NBUCKET);
+        stage_h2d(c, d_bcap16, bcap16_32.data(), 4ull * MRG_NBUCKET);
+        A.rbase = d_rbase; A.bcap = d_bcap; A.rbase16 = d_rbase16; A.bcap16 = d_bcap16;
         // 12-byte (wc) / 24-byte (indexer) records, + 16 bytes: readers may load a 12-byte record as 16
-        M.pool = pget<uint64_t>(p, (rtot * MRG_TAIL_BYTES(idx) + 16 + 7) / 8);
-        M.pool16 = pget<uint64_t>(p, 2 * rtot16 + 2);
-        M.fk0 = pget<uint64_t>(p, (uint64_t)grid * cap);
-        M.fk1 = pget<uint64_t>(p, (uint64_t)grid * cap);
-        M.fcnt = pget<uint32_t>(p, (uint64_t)grid * cap);
-        M.fdoc = idx ? pget<uint32_t>(p, (uint64_t)grid * cap) : nullptr;
-        M.foff = pget<uint32_t>(p, (uint64_t)grid * (MRG_NBUCKET + 1));
-        // long tokens: per-workgroup regions of lper records + a shared list of lovf
-        uint64_t lper = std::max<uint64_t>(c->lper_hint, (uint64_t)(ms.wg_scale * (double)((lcap + grid - 1) / grid)) + 16);
-        uint64_t lovf = lcap / 4 + 1024;
-        if (launches == 0) {  // test knobs (first launch only: a rerun grows them from the measured demand)
-            if (const uint64_t t = env_u64("MRG_TEST_LONG_PER", 0)) lper = t;
-            if (const uint64_t t = env_u64("MRG_TEST_LONG_LIST", 0)) lovf = t;
-        }
-        if (lper > 0xFFFFFFF0ull) raise(MRG_ENOMEM, "input too large for one map launch");
-        const uint64_t lslots = (uint64_t)grid * lper + lovf;
-        M.lstart = pget<uint64_t>(p, lslots);
-        M.llen = pget<uint32_t>(p, lslots);
-        M.ldoc = pget<uint32_t>(p, lslots);
-        M.lcount = pget<uint32_t>(p, (uint64_t)grid);
-        A.pool = M.pool; A.rbase = M.rbase; A.bcap = M.bcap; A.bcount = M.bcount;
-        A.pool16 = M.pool16; A.rbase16 = M.rbase16; A.bcap16 = M.bcap16; A.bcount16 = M.bcount16;
-        A.ovf = M.ovf; A.onext = M.onext; A.ocap = (uint32_t)ocap;
-        A.fk0 = M.fk0; A.fk1 = M.fk1; A.fcnt = M.fcnt; A.fdoc = M.fdoc; A.foff = M.foff;
-        A.lstart = M.lstart; A.llen = M.llen; A.ldoc = M.ldoc; A.lper = (uint32_t)lper; A.lovf = lovf;
-        A.lcount = M.lcount;
-        {  // non-ASCII tile lists: one entry per tile of a workgroup's share and steal budget at most
-            A.kwords = (uint32_t)(MRG_MAP_NSUB * ms.per_wg_blocks);
-            M.gbits = pget<uint32_t>(p, (uint64_t)grid * A.kwords);
-            A.gbits = M.gbits;
-        }
-        set_steal(c, A, M, ms, n_chunks);
-        A.counters = c->d_cnt;
-        A.hash_bits = hash_bits(c);
+        A.pool = att.get<uint64_t>((rtot * MRG_TAIL_BYTES(idx) + 16 + 7) / 8);
+        A.pool16 = att.get<uint64_t>(2 * rtot16 + 2);
+        A.fk0 = att.get<uint64_t>((uint64_t)grid * cap);
+        A.fk1 = att.get<uint64_t>((uint64_t)grid * cap);
+        A.fcnt = att.get<uint32_t>((uint64_t)grid * cap);
+        A.fdoc = idx ? att.get<uint32_t>((uint64_t)grid * cap) : nullptr;
+        A.foff = att.get<uint32_t>((uint64_t)grid * (MRG_NBUCKET + 1));
+        const uint64_t lslots = map_args_shared(c, att, A, in, ms, lcap, launches == 0);
         A.ablate = getenv("MRG_ABLATE") ? (uint32_t)atoi(getenv("MRG_ABLATE")) : 0u;
         A.prof = nullptr;
         if (getenv("MRG_PROF")) {
-            M.prof = pget<unsigned long long>(p, 8 + 8ull * grid);
-            HIPCHK(hipMemsetAsync(M.prof, 0, 8ull * (8 + 8ull * grid), s));
-            A.prof = M.prof;
+            A.prof = att.get<unsigned long long>(8 + 8ull * grid);
+            HIPCHK(hipMemsetAsync(A.prof, 0, 8ull * (8 + 8ull * grid), s));
         }
         stage_fill(c, c->d_cnt, 0, sizeof(unsigned long long) * CNT_N);
         stage_fill(c, &c->d_cnt[CNT_ERRPOS], 0xFF, sizeof(unsigned long long));
-        stage_h2d(c, M.dargs, &A, sizeof(MapArgs));
+        stage_h2d(c, dargs, &A, sizeof(MapArgs));
         flush_stage(c);
-        ev_rec(c, 0);
-        mrg_launch_map(nullptr, M.dargs, c->app, grid, c->lds_cap, s);  // also with no tiles: writes empty flush regions
-        ev_rec(c, 1);
+        ev_rec(c, c->ev, 0);
+        mrg_launch_map(nullptr, dargs, c->app, grid, c->lds_cap, s);  // also with no tiles: writes empty flush regions
+        ev_rec(c, c->ev, 1);
         HIPCHK(hipGetLastError());
         ++launches;
         // the aggregation queued behind the map before the host sees the map's counters (one host
@@ -1737,9 +1752,9 @@ void job_map(mrg_ctx *c) {
         // (r06: also on a cold context's first job when its sample found repeats; the 32-bit-count guess
         // is then "fewer than 2^32 tokens" -- true unless the input holds billions of one-letter words --
         // and bucket_aggregate checks it like every guess: a wrong one only drops the queued launch)
-        if (launches == 1 && !idx && (c->spec_agg || cold_repeats) && !M.prof && !wide_forced() &&
+        if (launches == 1 && !idx && (c->spec_agg || cold_repeats) && !A.prof && !wide_forced() &&
             !getenv("MRG_NO_SPEC_AGG") && grid <= 2048) {
-            ev_rec(c, 2);
+            ev_rec(c, c->ev, 2);
             uint32_t nsub = c->agg_nsub;
             if (const uint64_t t = env_u64("MRG_TEST_AGG_NSUB", 0)) nsub = (uint32_t)t;
             const bool c32 = c->spec_agg ? c->spec_c32 : true;
@@ -1747,13 +1762,13 @@ void job_map(mrg_ctx *c) {
         }
         // overflow-list fill into pinned scratch, then the counters: one host wait for both
         uint32_t *onext = (uint32_t *)&c->h_cnt[CNT_N + 8];
-        HIPCHK(hipMemcpyAsync(onext, M.onext, 4ull * MRG_NBUCKET, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(onext, A.onext, 4ull * MRG_NBUCKET, hipMemcpyDeviceToHost, s));
         read_counters(c);
         c->st.map_spill = 0;
         for (int b = 0; b < MRG_NBUCKET; ++b) c->st.map_spill += std::min<uint64_t>(onext[b], ocap);
-        if (M.prof) {
+        if (A.prof) {
             unsigned long long pr[8];
-            HIPCHK(hipMemcpy(pr, M.prof, sizeof pr, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(pr, A.prof, sizeof pr, hipMemcpyDeviceToHost));
             double tot = 0;
             for (int i = 0; i < 7; ++i) tot += (double)pr[i];
             static const char *nm[7] = {"load-wait", "classify", "stage+scan+queue", "token rounds", "slow tokens",
@@ -1763,7 +1778,7 @@ void job_map(mrg_ctx *c) {
             fprintf(stderr, "\n");
             // workgroup start/end wall clocks (100 MHz; written by -DMRG_MAP_PROF builds only)
             std::vector<unsigned long long> wt(8ull * grid);
-            HIPCHK(hipMemcpy(wt.data(), M.prof + 8, 8ull * wt.size(), hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(wt.data(), A.prof + 8, 8ull * wt.size(), hipMemcpyDeviceToHost));
             if (wt[1]) {
                 unsigned long long t0 = ~0ull, t1 = 0, ls = 0;
                 std::vector<double> dur(grid), end(grid), lend(grid);
@@ -1800,16 +1815,15 @@ void job_map(mrg_ctx *c) {
                 fprintf(stderr, "\n");
             }
         }
-        const uint64_t nl = c->h_cnt[CNT_LONG];
         const bool long_full = c->h_cnt[CNT_LONGX] > A.lovf;
         if (c->h_cnt[CNT_OVF] == 0 && !long_full) break;
-        if (spec.live) c->st.spec_agg = 2;  // the rerun invalidates the queued aggregation
-        agg_put(c, spec);
+        if (spec.live()) c->st.spec_agg = 2;  // the rerun invalidates the queued aggregation
+        spec.drop();
         // capacity exceeded: grow each bucket's regions to its demand (remembered), run again
         if (c->h_cnt[CNT_OVF]) {
             std::vector<uint32_t> cnt((uint64_t)grid * MRG_NBUCKET), cnt16((uint64_t)grid * MRG_NBUCKET, 0);
-            HIPCHK(hipMemcpyAsync(cnt.data(), M.bcount, 4ull * cnt.size(), hipMemcpyDeviceToHost, s));
-            if (!idx) HIPCHK(hipMemcpyAsync(cnt16.data(), M.bcount16, 4ull * cnt16.size(), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(cnt.data(), A.bcount, 4ull * cnt.size(), hipMemcpyDeviceToHost, s));
+            if (!idx) HIPCHK(hipMemcpyAsync(cnt16.data(), A.bcount16, 4ull * cnt16.size(), hipMemcpyDeviceToHost, s));
             sync(c);
             c->bcap_rate.assign(MRG_NBUCKET, 0.0);
             c->bcap16_rate.assign(MRG_NBUCKET, 0.0);
@@ -1828,63 +1842,28 @@ void job_map(mrg_ctx *c) {
             }
             ocap = c->ocap_hint = 4 * ocap;
         }
-        if (long_full) {  // a workgroup's long tokens overflowed its region and the list: grow both
-            std::vector<uint32_t> lc((uint64_t)grid);
-            HIPCHK(hipMemcpyAsync(lc.data(), M.lcount, 4ull * grid, hipMemcpyDeviceToHost, s));
-            sync(c);
-            const uint64_t mx = *std::max_element(lc.begin(), lc.end());
-            c->lper_hint = mx + mx / 4 + 64;
-            lcap = c->long_hint = std::max<uint64_t>(lcap, nl + nl / 8 + 1024);
-        }
+        if (long_full) grow_long_regions(c, A, grid, lcap);
         if (getenv("MRG_DEBUG"))
             fprintf(stderr, "[mrgpu] map rerun: tail overflow %llu, long %llu (list %llu of %llu)\n",
-                    (unsigned long long)c->h_cnt[CNT_OVF], (unsigned long long)nl,
+                    (unsigned long long)c->h_cnt[CNT_OVF], (unsigned long long)c->h_cnt[CNT_LONG],
                     (unsigned long long)c->h_cnt[CNT_LONGX], (unsigned long long)A.lovf);
-        M.release(p);
+        att.put_all();
     }
     if (getenv("MRG_DEBUG"))
         fprintf(stderr, "[mrgpu] map: %llu tokens, %llu tail records, %llu long, %u launches, grid %d\n",
                 (unsigned long long)c->h_cnt[CNT_TOKENS], (unsigned long long)c->h_cnt[CNT_REC],
                 (unsigned long long)c->h_cnt[CNT_LONG], launches, grid);
-    c->st.ms_map = ev_ms(c, 0, 1);
-    c->st.map_launches = launches;
-    c->st.input_bytes = total;
-    c->st.tokens = c->h_cnt[CNT_TOKENS];
-    c->st.long_tokens = c->h_cnt[CNT_LONG];
-    c->st.map_records = c->h_cnt[CNT_REC];
-    c->st.nonascii_tiles = c->h_cnt[CNT_NONASCII];
+    map_stats(c, launches, total);
     c->st.tail_records_16 = is_idx(c) ? 0 : c->h_cnt[CNT_REC16];  // the indexer's are all 24-byte records
-    const uint64_t errpos = c->h_cnt[CNT_ERRPOS];
-    auto release_map = [&]() {
-        agg_put(c, spec);
-        M.release(p);
-        p.put(d_doc_off); p.put(d_cb); p.put(d_ids);
-    };
-    if (errpos != ~0ull) {
-        release_map();
-        uint32_t d = 0;
-        while (d + 1 < nd && c->doc_off[d + 1] <= errpos) ++d;
-        const char *nm = ids[d] < c->names.size() ? c->names[ids[d]].c_str() : "";
-        raise(MRG_EUTF8, "stream did not contain valid UTF-8: document %u (id %u%s%s), byte offset %llu", d, ids[d],
-              *nm ? ", " : "", nm, (unsigned long long)(errpos - c->doc_off[d]));
-    }
-    if (!spec.live) ev_rec(c, 2);
-    LongItems li{};
-    li.base = c->d_in; li.cnt = nullptr;
-    li.n = c->h_cnt[CNT_LONG];
-    if (li.n) {  // pack the workgroups' regions and the shared list densely
-        M.dstart = pget<uint64_t>(p, li.n);
-        M.dlen = pget<uint32_t>(p, li.n);
-        M.ddoc = pget<uint32_t>(p, li.n);
-        mrg_launch_long_compact(A, grid, M.dstart, M.dlen, M.ddoc, s);
-    }
-    li.start = M.dstart; li.rawlen = M.dlen; li.doc = M.ddoc;
+    check_map_utf8(c, in.ids);
+    if (!spec.live()) ev_rec(c, c->ev, 2);
+    const LongItems li = long_items(c, att, A, grid);
     // high cardinality (most tokens missed the map-side combine): sort-based aggregation
     bool wide = !idx && c->h_cnt[CNT_REC] > (32ull << 20) && 2 * c->h_cnt[CNT_REC] > c->h_cnt[CNT_TOKENS];
     if (const char *v = getenv("MRG_WIDE")) wide = !idx && atoi(v) != 0;  // test / tuning override
-    if (wide && spec.live) {  // the queued aggregation was not needed: its counters back to the map's zeros
+    if (wide && spec.live()) {  // the queued aggregation was not needed: its counters back to the map's zeros
         c->st.spec_agg = 2;
-        agg_put(c, spec);
+        spec.drop();
         HIPCHK(hipMemsetAsync(&c->d_cnt[CNT_KEYS], 0, 8, s));
         HIPCHK(hipMemsetAsync(&c->d_cnt[CNT_OVF2], 0, 8, s));
     }
@@ -1895,28 +1874,22 @@ void job_map(mrg_ctx *c) {
         c->wide_hint = !idx;
         wide_aggregate(c, A, (uint32_t)grid, cap, li);
     }
-    ev_rec(c, 3);
-    release_map();
-    c->st.ms_aggregate = ev_ms(c, 2, 3);
+    ev_rec(c, c->ev, 3);
+    c->st.ms_aggregate = ev_ms(c, c->ev, 2, 3);
     if (!idx && total >= (64ull << 20)) c->wc_sized = true;
     c->mapped = c->keyed = true;
 }
 
 // ---- the accumulator of mrg_job_map_add (k_acc.hip)
 
-AccTable acc_table_get(mrg_ctx *c, uint64_t cap) {
-    Pool &p = c->pool;
+// a cleared table of `cap` slots; its arrays are blocks of sc until the caller has made it c->acc.T
+AccTable acc_table_get(mrg_ctx *c, Scratch &sc, uint64_t cap) {
     AccTable T{};
-    try {
-        T.k0 = pget<uint64_t>(p, cap);
-        T.k1 = pget<uint64_t>(p, cap);
-        T.cnt = pget<uint64_t>(p, cap);
-        T.doc = pget<uint32_t>(p, cap);
-        T.part = pget<uint32_t>(p, cap);
-    } catch (...) {
-        acc_table_put(p, T);
-        throw;
-    }
+    T.k0 = sc.get<uint64_t>(cap);
+    T.k1 = sc.get<uint64_t>(cap);
+    T.cnt = sc.get<uint64_t>(cap);
+    T.doc = sc.get<uint32_t>(cap);
+    T.part = sc.get<uint32_t>(cap);
     T.cap = cap;
     T.hash_bits = hash_bits(c);
     mrg_acc_launch_clear(T, c->stream);
@@ -1930,16 +1903,19 @@ AccTable acc_table_get(mrg_ctx *c, uint64_t cap) {
 void acc_reserve(mrg_ctx *c, uint64_t more) {
     Acc &A = c->acc;
     const uint64_t need = pow2_at_least(2 * (A.n + more));
+    Scratch sc(c->pool);
     if (!A.T.cap) {
         const uint64_t t = env_u64("MRG_TEST_ACC_CAP", 0);
-        A.T = acc_table_get(c, t ? pow2_at_least(t) : need);
+        A.T = acc_table_get(c, sc, t ? pow2_at_least(t) : need);
+        sc.keep();
     }
     if (A.T.cap >= need) return;
-    AccTable N = acc_table_get(c, std::max<uint64_t>(need, 2 * A.T.cap));
+    AccTable N = acc_table_get(c, sc, std::max<uint64_t>(need, 2 * A.T.cap));
     mrg_acc_launch_rehash(A.T, N, is_idx(c), c->stream);
     HIPCHK(hipGetLastError());
     acc_table_put(c->pool, A.T);  // (the pool is stream-ordered: reused only behind the rehash)
     A.T = N;
+    sc.keep();
     ++A.rehashes;
     if (getenv("MRG_DEBUG"))
         fprintf(stderr, "[mrgpu] accumulator: %llu keys rehashed into %llu slots\n", (unsigned long long)A.n,
@@ -1956,72 +1932,60 @@ void acc_fold(mrg_ctx *c, KeysBuf &b) {
     Pool &p = c->pool;
     hipStream_t s = c->stream;
     const bool idx = is_idx(c);
-    struct Tmp {  // released on every path
+    struct Batch {  // b's blocks back on every path
         Pool &p; KeysBuf &b;
-        unsigned long long *d_n = nullptr;
-        uint64_t *start = nullptr, *cnt = nullptr;
-        uint32_t *rawlen = nullptr, *doc = nullptr;
-        uint8_t *heap = nullptr;
-        ~Tmp() {
-            p.put(d_n); p.put(start); p.put(cnt); p.put(rawlen); p.put(doc); p.put(heap);
-            keysbuf_release(p, b);
-        }
-    } t{p, b};
+        ~Batch() { keysbuf_release(p, b); }
+    } batch{p, b};
+    Scratch sc(p);
     A.dirty = true;  // (also when nothing is added: the view is rebuilt from the accumulator)
     if (!b.n) return;
     acc_reserve(c, b.n);
-    t.d_n = pget<unsigned long long>(p, 2);  // [0] keys new to the table, [1] the batch's long keys
-    HIPCHK(hipMemsetAsync(t.d_n, 0, 16, s));
+    unsigned long long *d_n = sc.get<unsigned long long>(2);  // [0] keys new to the table, [1] the batch's long keys
+    HIPCHK(hipMemsetAsync(d_n, 0, 16, s));
     bool relong = false;
     if (b.any_long) {
         const uint64_t cap = A.lng.n + b.n;
-        t.start = pget<uint64_t>(p, cap);
-        t.cnt = pget<uint64_t>(p, cap);
-        t.rawlen = pget<uint32_t>(p, cap);
-        t.doc = pget<uint32_t>(p, cap);
-        t.heap = pget<uint8_t>(p, A.lng.heap_bytes + b.heap_bytes + 16);
+        LongItems li{};
+        li.start = sc.get<uint64_t>(cap);
+        li.cnt = sc.get<uint64_t>(cap);
+        li.rawlen = sc.get<uint32_t>(cap);
+        li.doc = sc.get<uint32_t>(cap);
+        uint8_t *heap = sc.get<uint8_t>(A.lng.heap_bytes + b.heap_bytes + 16);
+        li.base = heap;
+        li.verbatim = 1;  // both heaps hold exact key bytes
         if (A.lng.n) {  // the accumulated rows first, their heap in front
-            HIPCHK(hipMemcpyAsync(t.start, A.lng.ks.hoff, 8 * A.lng.n, hipMemcpyDeviceToDevice, s));
-            HIPCHK(hipMemcpyAsync(t.cnt, A.lng.ks.cnt, 8 * A.lng.n, hipMemcpyDeviceToDevice, s));
-            HIPCHK(hipMemcpyAsync(t.rawlen, A.lng.ks.len, 4 * A.lng.n, hipMemcpyDeviceToDevice, s));
-            HIPCHK(hipMemcpyAsync(t.doc, A.lng.ks.doc, 4 * A.lng.n, hipMemcpyDeviceToDevice, s));
+            HIPCHK(hipMemcpyAsync(li.start, A.lng.ks.hoff, 8 * A.lng.n, hipMemcpyDeviceToDevice, s));
+            HIPCHK(hipMemcpyAsync(li.cnt, A.lng.ks.cnt, 8 * A.lng.n, hipMemcpyDeviceToDevice, s));
+            HIPCHK(hipMemcpyAsync(li.rawlen, A.lng.ks.len, 4 * A.lng.n, hipMemcpyDeviceToDevice, s));
+            HIPCHK(hipMemcpyAsync(li.doc, A.lng.ks.doc, 4 * A.lng.n, hipMemcpyDeviceToDevice, s));
             if (A.lng.heap_bytes)
-                HIPCHK(hipMemcpyAsync(t.heap, A.lng.heap, A.lng.heap_bytes, hipMemcpyDeviceToDevice, s));
+                HIPCHK(hipMemcpyAsync(heap, A.lng.heap, A.lng.heap_bytes, hipMemcpyDeviceToDevice, s));
         }
         if (b.heap_bytes)
-            HIPCHK(hipMemcpyAsync(t.heap + A.lng.heap_bytes, b.heap, b.heap_bytes, hipMemcpyDeviceToDevice, s));
-        mrg_acc_launch_long(b.ks, b.n, A.lng.heap_bytes, A.lng.n, cap, t.start, t.rawlen, t.doc, t.cnt, &t.d_n[1], s);
+            HIPCHK(hipMemcpyAsync(heap + A.lng.heap_bytes, b.heap, b.heap_bytes, hipMemcpyDeviceToDevice, s));
+        mrg_acc_launch_long(b.ks, b.n, A.lng.heap_bytes, A.lng.n, cap, li.start, li.rawlen, li.doc, li.cnt, &d_n[1], s);
         HIPCHK(hipGetLastError());
         uint64_t nl = 0;
-        HIPCHK(hipMemcpyAsync(&nl, &t.d_n[1], 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(&nl, &d_n[1], 8, hipMemcpyDeviceToHost, s));
         sync(c);
         if (nl > b.n) raise(MRG_EHIP, "internal: accumulator long-key count");
-        if (nl) {
-            LongItems li{};
-            li.base = t.heap;
-            li.start = t.start; li.rawlen = t.rawlen; li.doc = t.doc; li.cnt = t.cnt;
+        if (nl) {  // (a failure from here on leaves a partial set in c->keys: the callers drop it)
             li.n = A.lng.n + nl;
-            li.verbatim = 1;  // both heaps hold exact key bytes
             keys_reserve(c, li.n + 1);  // (c->keys is free here: the caller moved the batch out of it)
             HIPCHK(hipMemsetAsync(&c->d_cnt[CNT_KEYS], 0, sizeof(unsigned long long), s));
-            try {
-                long_aggregate(c, li);
-                read_counters(c);
-                c->keys.n = c->h_cnt[CNT_KEYS];
-                if (c->keys.n > li.n) raise(MRG_EHIP, "internal: accumulator long-key set overflow");
-                mrg_launch_partition(c->keys.ks, c->keys.heap, c->keys.n, c->R, s);
-                HIPCHK(hipGetLastError());
-            } catch (...) {
-                keys_release(c);
-                throw;
-            }
+            long_aggregate(c, li);
+            read_counters(c);
+            c->keys.n = c->h_cnt[CNT_KEYS];
+            if (c->keys.n > li.n) raise(MRG_EHIP, "internal: accumulator long-key set overflow");
+            mrg_launch_partition(c->keys.ks, c->keys.heap, c->keys.n, c->R, s);
+            HIPCHK(hipGetLastError());
             relong = true;
         }
     }
-    mrg_acc_launch_fold(A.T, b.ks, b.n, idx, &t.d_n[0], s);
+    mrg_acc_launch_fold(A.T, b.ks, b.n, idx, &d_n[0], s);
     HIPCHK(hipGetLastError());
     uint64_t made = 0;
-    HIPCHK(hipMemcpyAsync(&made, &t.d_n[0], 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&made, &d_n[0], 8, hipMemcpyDeviceToHost, s));
     sync(c);
     A.n += made;
     if (relong) {
@@ -2094,6 +2058,7 @@ void job_map_add(mrg_ctx *c) {
                 acc_fold(c, b);
             } catch (...) {  // (out of memory with the keys already moved: the job is left without keys)
                 acc_release(c);
+                keysbuf_release(c->pool, c->keys);  // (a long-key set the fold had begun)
                 c->mapped = false;
                 throw;
             }
@@ -2111,10 +2076,10 @@ void job_map_add(mrg_ctx *c) {
         c->keys = KeysBuf{};
         c->keyed = false;
         acc_fold(c, b);
-        ev_rec(c, 7);
-        A.ms_fold = ev_ms(c, 3, 7);
+        ev_rec(c, c->ev, 7);
+        A.ms_fold = ev_ms(c, c->ev, 3, 7);
     } catch (...) {
-        keys_release(c);
+        keysbuf_release(c->pool, c->keys);
         c->wide.release(c->pool);
         c->keyed = false;
         c->st = st0;
@@ -2142,21 +2107,17 @@ void job_map_add(mrg_ctx *c) {
 }
 
 // Indexer document order = bytewise order of the names (the indexer reduce sorts its values):
-// rank of each global document id, and the names concatenated in rank order, on the device.
+// rank of each global document id, and the names concatenated in rank order, on the device (blocks of
+// the caller's Scratch).
 struct DocRank {
     uint32_t *rank = nullptr;
     uint8_t *names = nullptr;
     uint64_t *name_off = nullptr;
-    void release(Pool &p) {
-        p.put(rank); p.put(names); p.put(name_off);
-        *this = DocRank{};
-    }
 };
 
-DocRank doc_ranks(mrg_ctx *c) {
+DocRank doc_ranks(mrg_ctx *c, Scratch &sc) {
     DocRank d;
     if (!is_idx(c)) return d;
-    Pool &p = c->pool;
     hipStream_t s = c->stream;
     const uint32_t nn = (uint32_t)c->names.size();
     if (nn == 0) raise(MRG_EINVAL, "indexer needs document names (mrg_job_set_doc_names)");
@@ -2171,9 +2132,9 @@ DocRank doc_ranks(mrg_ctx *c) {
         cat += c->names[order[r]];
         noff[r + 1] = cat.size();
     }
-    d.rank = pget<uint32_t>(p, nn);
-    d.names = pget<uint8_t>(p, cat.size() + 1);
-    d.name_off = pget<uint64_t>(p, nn + 1);
+    d.rank = sc.get<uint32_t>(nn);
+    d.names = sc.get<uint8_t>(cat.size() + 1);
+    d.name_off = sc.get<uint64_t>(nn + 1);
     HIPCHK(hipMemcpyAsync(d.rank, rank.data(), 4ull * nn, hipMemcpyHostToDevice, s));
     if (!cat.empty()) HIPCHK(hipMemcpyAsync(d.names, cat.data(), cat.size(), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(d.name_off, noff.data(), 8ull * (nn + 1), hipMemcpyHostToDevice, s));
@@ -2235,39 +2196,41 @@ int compat_drop_last(const mrg_ctx *c) { return (c->flags & MRG_FLAG_NO_COMPAT_D
 // non-empty leaf of every partition, a scan of the leaf byte totals, the line writer.
 void wide_reduce(mrg_ctx *c) {
     WideRes &w = c->wide;
-    Pool &p = c->pool;
+    Scratch sc(c->pool);
     hipStream_t s = c->stream;
     const uint64_t NL = (uint64_t)w.B1 * MRG_WIDE_MAXB2;
-    ev_rec(c, 4);
-    uint32_t *drop = pget<uint32_t>(p, NL);
+    ev_rec(c, c->ev, 4);
+    uint32_t *drop = sc.get<uint32_t>(NL);
     HIPCHK(hipMemsetAsync(drop, 0, 4 * NL, s));
-    uint64_t *bytes = pget<uint64_t>(p, NL + 1), *off = pget<uint64_t>(p, NL + 1);
-    uint64_t *tmp = pget<uint64_t>(p, mrg_scan_tmp_elems(NL + 1));
+    uint64_t *bytes = sc.get<uint64_t>(NL + 1), *off = sc.get<uint64_t>(NL + 1);
+    uint64_t *tmp = sc.get<uint64_t>(mrg_scan_tmp_elems(NL + 1));
     HIPCHK(hipMemcpyAsync(bytes, w.leaf_bytes, 8 * (NL + 1), hipMemcpyDeviceToDevice, s));
     if (compat_drop_last(c)) mrg_wide_launch_drop(w.nleaf, w.B1r, c->R, w.leaf_nd, bytes, w.leaf_last, drop, s);
     mrg_scan_u64(bytes, off, NL + 1, tmp, s);  // off[NL] = total (bytes[NL] == 0)
     uint64_t total = 0;
     HIPCHK(hipMemcpyAsync(&total, off + NL, 8, hipMemcpyDeviceToHost, s));
     sync(c);
-    ev_rec(c, 5);
-    if (total + 16 > c->out_cap) {
-        if (c->d_out) p.put(c->d_out);
+    ev_rec(c, c->ev, 5);
+    if (total + 16 > c->out_cap) {  // (on a failure the context holds no buffer, never a returned one)
+        uint8_t *old = c->d_out;
+        c->d_out = nullptr;
+        c->out_cap = 0;
+        c->pool.put(old);
+        c->d_out = pget<uint8_t>(c->pool, total + 16);
         c->out_cap = total + 16;
-        c->d_out = pget<uint8_t>(p, c->out_cap);
     }
     if (getenv("MRG_DEBUG_FILL_OUT")) HIPCHK(hipMemsetAsync(c->d_out, 0xEE, total, s));  // diagnostics: unwritten bytes show
     mrg_wide_launch_write(w.kout, w.ocnt, w.leaf_pk, w.nleaf, w.leaf_out, w.leaf_nd, drop, off, w.B1, c->d_out, s);
-    uint64_t *poff = pget<uint64_t>(p, c->R + 1);
+    uint64_t *poff = sc.get<uint64_t>(c->R + 1);
     mrg_wide_launch_part_off(off, w.B1r, c->R, total, poff, s);
     c->part_off.assign(c->R + 1, 0);
     HIPCHK(hipMemcpyAsync(c->part_off.data(), poff, 8ull * (c->R + 1), hipMemcpyDeviceToHost, s));
-    ev_rec(c, 6);
+    ev_rec(c, c->ev, 6);
     sync(c);
     HIPCHK(hipGetLastError());
-    p.put(drop); p.put(bytes); p.put(off); p.put(tmp); p.put(poff);
     c->out_bytes = total;
-    c->st.ms_sort = ev_ms(c, 4, 5);
-    c->st.ms_format = ev_ms(c, 5, 6);
+    c->st.ms_sort = ev_ms(c, c->ev, 4, 5);
+    c->st.ms_format = ev_ms(c, c->ev, 5, 6);
     c->st.output_bytes = total;
     c->reduced = true;
 }
@@ -2280,13 +2243,13 @@ void job_reduce(mrg_ctx *c) {
         wide_reduce(c);
         return;
     }
-    Pool &p = c->pool;
+    Scratch sc(c->pool);
     hipStream_t s = c->stream;
     const uint64_t n = c->keys.n;
-    DocRank dr = doc_ranks(c);
-    ev_rec(c, 4);
-    SortRec *a = pget<SortRec>(p, n), *b = pget<SortRec>(p, n);
-    void *stmp = p.get(mrg_sort_tmp_bytes(n));
+    const DocRank dr = doc_ranks(c, sc);
+    ev_rec(c, c->ev, 4);
+    SortRec *a = sc.get<SortRec>(n), *b = sc.get<SortRec>(n);
+    void *stmp = sc.get<uint8_t>(mrg_sort_tmp_bytes(n));
     SortRec *sorted = a;
     const bool presorted = c->keys.sorted && !c->keys.any_long && !is_idx(c);
     // the oversized-bucket check of the key sort waits for format's own sync (add_first below is
@@ -2303,22 +2266,20 @@ void job_reduce(mrg_ctx *c) {
         if (c->keys.any_long) mrg_launch_fix_runs(sorted, n, c->keys.ks, c->keys.heap, s);
         mrg_launch_add_first(sorted, c->keys.ks, c->extra_first, s);
     }
-    ev_rec(c, 5);
+    ev_rec(c, c->ev, 5);
     const FormatArgs f = format_args(c, sorted, c->keys.ks, c->R, compat_drop_last(c), dr, carry);
     c->part_off.assign(c->R + 1, 0);
-    c->out_bytes = mrg_format(f, p, &c->d_out, &c->out_cap, c->part_off.data(), s);
+    c->out_bytes = mrg_format(f, c->pool, &c->d_out, &c->out_cap, c->part_off.data(), s);
     const uint32_t n_big = *(const uint32_t *)&c->h_cnt[CNT_N];  // written by the sort's async copy
     if (defer && n > 1 && n_big) {  // oversized MSD buckets: sort them, format again
         sorted = mrg_msd_sort_finish(a, b, n, sort_plan(c, c->R), stmp, s, n_big);
         const FormatArgs f2 = format_args(c, sorted, c->keys.ks, c->R, compat_drop_last(c), dr, carry);
-        c->out_bytes = mrg_format(f2, p, &c->d_out, &c->out_cap, c->part_off.data(), s);
+        c->out_bytes = mrg_format(f2, c->pool, &c->d_out, &c->out_cap, c->part_off.data(), s);
     }
-    ev_rec(c, 6);
+    ev_rec(c, c->ev, 6);
     HIPCHK(hipGetLastError());
-    p.put(a); p.put(b); p.put(stmp);
-    dr.release(p);
-    c->st.ms_sort = ev_ms(c, 4, 5);
-    c->st.ms_format = ev_ms(c, 5, 6);
+    c->st.ms_sort = ev_ms(c, c->ev, 4, 5);
+    c->st.ms_format = ev_ms(c, c->ev, 5, 6);
     c->st.output_bytes = c->out_bytes;
     c->reduced = true;
 }
@@ -2331,14 +2292,14 @@ void job_final(mrg_ctx *c) {
     if (!c->mapped) raise(MRG_EINVAL, "no keys: call mrg_job_map or mrg_job_import first");
     acc_emit(c);
     wide_densify(c, 0);
-    Pool &p = c->pool;
+    Scratch sc(c->pool);
     hipStream_t s = c->stream;
     const uint64_t n = c->keys.n;
-    DocRank dr = doc_ranks(c);
-    SortRec *a = pget<SortRec>(p, n), *b = pget<SortRec>(p, n);
-    void *stmp = p.get(mrg_sort_tmp_bytes(n));
+    const DocRank dr = doc_ranks(c, sc);
+    SortRec *a = sc.get<SortRec>(n), *b = sc.get<SortRec>(n);
+    void *stmp = sc.get<uint8_t>(mrg_sort_tmp_bytes(n));
     const int drop = compat_drop_last(c);
-    uint32_t *part2 = pget<uint32_t>(p, std::max<uint64_t>(n, 1));
+    uint32_t *part2 = sc.get<uint32_t>(std::max<uint64_t>(n, 1));
     KeySet ks2 = c->keys.ks;
     ks2.part = part2;
     if (drop) {
@@ -2352,10 +2313,8 @@ void job_final(mrg_ctx *c) {
     SortRec *s2 = sort_keys(c, ks2, R2, dr.rank, a, b, stmp);
     const FormatArgs f = format_args(c, s2, ks2, R2, 0, dr);
     uint64_t po[3] = {0, 0, 0};
-    mrg_format(f, p, &c->d_final, &c->final_cap, po, s);
+    mrg_format(f, c->pool, &c->d_final, &c->final_cap, po, s);
     HIPCHK(hipGetLastError());
-    p.put(a); p.put(b); p.put(stmp); p.put(part2);
-    dr.release(p);
     c->final_bytes = po[1];
     c->finalized = true;
 }
@@ -2364,15 +2323,15 @@ void job_final(mrg_ctx *c) {
 // sorting the keys (k_topk.hip): at most R keys are dropped, so these lines lie
 // within the k + R best keys; a radix select finds those, and only they are sorted and formatted.
 // Reads the key set only: reduce, final and export afterwards give what they give without it.
-// keep: *keep receives the ranked records of the lines written (idx = key index in c->keys), a pool
-// block the caller returns; null when no line was written (mrg_job_vocab).
-void job_topk(mrg_ctx *c, uint64_t k, SortRec **keep = nullptr) {
+// keep: the ranked records of the lines written (idx = key index in c->keys) become a block of *keep and
+// are returned; null when no line was written (mrg_job_vocab).
+SortRec *job_topk(mrg_ctx *c, uint64_t k, Scratch *keep = nullptr) {
     need_job(c);
     if (is_idx(c)) raise(MRG_EINVAL, "mrg_job_topk: word count only (the indexer has no counts to rank)");
     if (!c->mapped) raise(MRG_EINVAL, "no keys: call mrg_job_map or mrg_job_import first");
     acc_emit(c);
     wide_densify(c, 0);
-    Pool &p = c->pool;
+    Scratch sc(c->pool);
     hipStream_t s = c->stream;
     const uint64_t n = c->keys.n;
     const KeySet ks = c->keys.ks;
@@ -2381,11 +2340,11 @@ void job_topk(mrg_ctx *c, uint64_t k, SortRec **keep = nullptr) {
     c->top_info[0] = n;
     c->top_bytes = c->top_lines = 0;
     c->topped = true;  // (an empty answer is an answer; a failure below clears it again)
-    if (k == 0 || n == 0) return;
+    if (k == 0 || n == 0) return nullptr;
     c->topped = false;
     check_sort_n(n, "top-k");
     const uint64_t want = std::min<uint64_t>(n, k > n ? n : k + c->R);  // (k > n: no overflow of k + R)
-    TopkState *st = pget<TopkState>(p, 1);
+    TopkState *st = sc.get<TopkState>(1);
     HIPCHK(hipMemsetAsync(st, 0, sizeof(TopkState), s));
     TopkState h{};
     uint64_t m = n;  // candidates
@@ -2399,8 +2358,8 @@ void job_topk(mrg_ctx *c, uint64_t k, SortRec **keep = nullptr) {
         for (uint32_t d = 0; d < MRG_TOPK_DIGITS; ++d)
             if (h.parts[d]) c->top_pass_bytes[d] = 8 * n + (d >= 8 ? 8 * h.parts[8] : 0) + (d >= 16 ? 8 * h.parts[16] : 0);
     }
-    SortRec *a = pget<SortRec>(p, m), *b = pget<SortRec>(p, m);
-    void *stmp = p.get(mrg_sort_tmp_bytes(m));
+    SortRec *a = sc.get<SortRec>(m), *b = sc.get<SortRec>(m);
+    void *stmp = sc.get<uint8_t>(mrg_sort_tmp_bytes(m));
     mrg_topk_compact(ks, n, st, a, m, s);
     // key order of the candidates (part unused), full-string order where long keys share a prefix
     uint32_t n_big = 0;
@@ -2409,15 +2368,15 @@ void job_topk(mrg_ctx *c, uint64_t k, SortRec **keep = nullptr) {
     // drop-last: the byte-largest candidate of a partition is dropped iff no key of the partition exceeds it
     uint32_t *cand_last = nullptr, *exceeded = nullptr;
     if (compat_drop_last(c)) {
-        cand_last = pget<uint32_t>(p, 2ull * c->R);
+        cand_last = sc.get<uint32_t>(2ull * c->R);
         exceeded = cand_last + c->R;
         HIPCHK(hipMemsetAsync(cand_last, 0, 8ull * c->R, s));
         mrg_topk_cand_last(sorted, m, ks, c->R, cand_last, s);
         if (m < n) mrg_topk_exceed(ks, c->keys.heap, n, sorted, c->R, cand_last, exceeded, s);  // (m == n: none can)
     }
     // then a stable sort by ~count: count descending, key order kept among equal counts
-    uint64_t *ckeys = pget<uint64_t>(p, m), *kvtmp = pget<uint64_t>(p, 4 * m);
-    uint32_t *vals = pget<uint32_t>(p, m);
+    uint64_t *ckeys = sc.get<uint64_t>(m), *kvtmp = sc.get<uint64_t>(4 * m);
+    uint32_t *vals = sc.get<uint32_t>(m);
     mrg_topk_count_keys(sorted, m, ks, c->R, cand_last, exceeded, ckeys, vals, st, s);
     mrg_radix_sort_u64(ckeys, vals, kvtmp, m, stmp, s);
     SortRec *top = sorted == a ? b : a;
@@ -2435,51 +2394,15 @@ void job_topk(mrg_ctx *c, uint64_t k, SortRec **keep = nullptr) {
     f.heap_bytes = c->keys.heap_bytes;
     f.n_reduce = 1;
     uint64_t po[2] = {0, 0};
-    mrg_format(f, p, &c->d_top, &c->top_cap, po, s);
+    mrg_format(f, c->pool, &c->d_top, &c->top_cap, po, s);
     HIPCHK(hipGetLastError());
-    p.put(st); p.put(sorted); p.put(stmp); p.put(cand_last); p.put(ckeys); p.put(kvtmp); p.put(vals);
-    if (keep) *keep = top;
-    else p.put(top);
     c->top_bytes = po[1];
     c->top_lines = lines;
     c->topped = true;
     c->top_info[1] = m;
     c->top_info[2] = h.passes;
     c->top_info[3] = h.ndrop;
-}
-
-// Pool blocks of one call, returned on every exit.
-struct Scratch {
-    Pool &p;
-    std::vector<void *> b;
-    explicit Scratch(Pool &pool) : p(pool) {}
-    Scratch(const Scratch &) = delete;
-    Scratch &operator=(const Scratch &) = delete;
-    template <class T>
-    T *get(uint64_t n) {
-        b.push_back(nullptr);
-        return (T *)(b.back() = pget<T>(p, n));
-    }
-    void adopt(void *q) { b.push_back(q); }
-    ~Scratch() {
-        for (void *q : b) p.put(q);
-    }
-};
-
-void enc_events(mrg_ctx *c) {
-    if (!c->timing) return;
-    for (auto &e : c->enc_ev)
-        if (!e) HIPCHK(hipEventCreate(&e));
-}
-void enc_rec(mrg_ctx *c, int i) {
-    if (c->timing) HIPCHK(hipEventRecord(c->enc_ev[i], c->stream));
-}
-double enc_ms(mrg_ctx *c, int a, int b) {
-    if (!c->timing) return 0.0;
-    float ms = 0;
-    HIPCHK(hipEventSynchronize(c->enc_ev[b]));
-    HIPCHK(hipEventElapsedTime(&ms, c->enc_ev[a], c->enc_ev[b]));
-    return ms;
+    return keep ? keep->adopt(sc.release(top)) : nullptr;
 }
 
 void vocab_destroy(mrg_vocab *v) {
@@ -2558,11 +2481,9 @@ mrg_vocab *job_vocab(mrg_ctx *c, uint64_t max_words, uint64_t min_count) {
     Pool &p = c->pool;
     hipStream_t s = c->stream;
     Scratch sc(p);
-    enc_events(c);
-    enc_rec(c, 4);
-    SortRec *top = nullptr;
-    job_topk(c, max_words ? max_words : ~0ull, &top);
-    if (top) sc.adopt(top);
+    ev_make(c, c->enc_ev);
+    ev_rec(c, c->enc_ev, 4);
+    SortRec *top = job_topk(c, max_words ? max_words : ~0ull, &sc);
     const uint64_t m = top ? c->top_lines : 0;
     uint64_t n = 0, text_bytes = 0;
     uint64_t *loff = nullptr;
@@ -2588,9 +2509,9 @@ mrg_vocab *job_vocab(mrg_ctx *c, uint64_t max_words, uint64_t min_count) {
     if (n) HIPCHK(hipMemcpyAsync((void *)v->T.line_off, loff, 8 * (n + 1), hipMemcpyDeviceToDevice, s));
     if (n) HIPCHK(hipMemcpyAsync(v->W.wlen, wlen, 4 * n, hipMemcpyDeviceToDevice, s));
     vocab_build(c, v.get(), sc);
-    enc_rec(c, 5);
+    ev_rec(c, c->enc_ev, 5);
     sync(c);
-    c->enc_ms[3] = enc_ms(c, 4, 5);
+    c->enc_ms[3] = ev_ms(c, c->enc_ev, 4, 5);
     return v.release();
 }
 
@@ -2619,7 +2540,7 @@ void vocab_encode(mrg_ctx *c, const mrg_vocab *v, const uint8_t *d_bytes, const 
     Pool &p = c->pool;
     hipStream_t s = c->stream;
     Scratch sc(p);
-    enc_events(c);
+    ev_make(c, c->enc_ev);
     // positions relative to the 1 KiB boundary at or below the first document
     const uint64_t shift = lo0 & ~1023ull;
     std::vector<uint64_t> rel(h_doc_off, h_doc_off + n_docs + 1);
@@ -2648,19 +2569,19 @@ void vocab_encode(mrg_ctx *c, const mrg_vocab *v, const uint8_t *d_bytes, const 
     HIPCHK(hipMemsetAsync(P.err, 0xFF, 8, s));
     HIPCHK(hipMemsetAsync(P.info, 0, 64, s));
     mrg_enc_launch_bounds(P, s);
-    enc_rec(c, 0);
+    ev_rec(c, c->enc_ev, 0);
     mrg_enc_launch_count(P, v->T, s);
-    enc_rec(c, 1);
+    ev_rec(c, c->enc_ev, 1);
     mrg_scan_u64(P.cnt, P.cnt, P.ntiles + 1, stmp, s);
     mrg_enc_launch_offsets(P, v->T, s);
-    enc_rec(c, 2);
+    ev_rec(c, c->enc_ev, 2);
     HIPCHK(hipGetLastError());
     unsigned long long herr = 0;
     HIPCHK(hipMemcpyAsync(h_tok_off, P.tok_off, 8 * ((uint64_t)n_docs + 1), hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(&herr, P.err, 8, hipMemcpyDeviceToHost, s));
     sync(c);  // (also: the pageable `rel` has been read)
-    c->enc_ms[0] = enc_ms(c, 0, 1);
-    c->enc_ms[1] = enc_ms(c, 1, 2);
+    c->enc_ms[0] = ev_ms(c, c->enc_ev, 0, 1);
+    c->enc_ms[1] = ev_ms(c, c->enc_ev, 1, 2);
     if (herr != ~0ull) {
         uint32_t d = 0;
         while (d + 1 < n_docs && rel[d + 1] <= herr) ++d;
@@ -2673,33 +2594,17 @@ void vocab_encode(mrg_ctx *c, const mrg_vocab *v, const uint8_t *d_bytes, const 
                                    (unsigned long long)total);
         P.out = d_ids;
         P.out_n = total;
-        enc_rec(c, 2);
+        ev_rec(c, c->enc_ev, 2);
         if (total) mrg_enc_launch_emit(P, v->T, s);
-        enc_rec(c, 3);
+        ev_rec(c, c->enc_ev, 3);
         HIPCHK(hipGetLastError());
     }
     unsigned long long hinfo[8] = {};
     HIPCHK(hipMemcpyAsync(hinfo, P.info, 64, hipMemcpyDeviceToHost, s));
     sync(c);
-    if (d_ids) c->enc_ms[2] = enc_ms(c, 2, 3);
+    if (d_ids) c->enc_ms[2] = ev_ms(c, c->enc_ev, 2, 3);
     for (int i = 0; i < 5; ++i) c->enc_info[i] = hinfo[i];
     if (!d_ids) c->enc_info[0] = total;
-}
-
-void dec_events(mrg_ctx *c) {
-    if (!c->timing) return;
-    for (auto &e : c->dec_ev)
-        if (!e) HIPCHK(hipEventCreate(&e));
-}
-void dec_rec(mrg_ctx *c, int i) {
-    if (c->timing) HIPCHK(hipEventRecord(c->dec_ev[i], c->stream));
-}
-double dec_ms(mrg_ctx *c, int a, int b) {
-    if (!c->timing) return 0.0;
-    float ms = 0;
-    HIPCHK(hipEventSynchronize(c->dec_ev[b]));
-    HIPCHK(hipEventElapsedTime(&ms, c->dec_ev[a], c->dec_ev[b]));
-    return ms;
 }
 
 // A vocabulary from its text: the host cuts the lines, the device checks every
@@ -2724,8 +2629,8 @@ mrg_vocab *vocab_from_text(mrg_ctx *c, const uint8_t *h_text, uint64_t bytes, ui
     const uint64_t n = loff.size() - 1;
     hipStream_t s = c->stream;
     Scratch sc(c->pool);
-    dec_events(c);
-    dec_rec(c, 4);
+    ev_make(c, c->dec_ev);
+    ev_rec(c, c->dec_ev, 4);
     VocPtr v = vocab_alloc(c, n, bytes, (flags >> 8) & 0xFFu);
     if (n) {
         HIPCHK(hipMemcpyAsync((void *)v->T.text, h_text, bytes, hipMemcpyHostToDevice, s));
@@ -2752,14 +2657,14 @@ mrg_vocab *vocab_from_text(mrg_ctx *c, const uint8_t *h_text, uint64_t bytes, ui
         mrg_voc_launch_verify(v->T, v->W.wlen, err + 1, s);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(&herr, err + 1, 8, hipMemcpyDeviceToHost, s));
-        dec_rec(c, 5);
+        ev_rec(c, c->dec_ev, 5);
         sync(c);
         if (herr != ~0ull) raise(MRG_EINVAL, "mrg_vocab_from_text: line %llu: duplicate word", herr);
     } else {
-        dec_rec(c, 5);
+        ev_rec(c, c->dec_ev, 5);
         sync(c);
     }
-    c->dec_ms[3] = dec_ms(c, 4, 5);
+    c->dec_ms[3] = ev_ms(c, c->dec_ev, 4, 5);
     return v.release();
 }
 
@@ -2790,7 +2695,7 @@ void vocab_decode(mrg_ctx *c, const mrg_vocab *v, const uint32_t *d_ids, const u
     Pool &p = c->pool;
     hipStream_t s = c->stream;
     Scratch sc(p);
-    dec_events(c);
+    ev_make(c, c->dec_ev);
     // positions relative to the 16-byte boundary at or below the first id
     const uint64_t shift = (uint64_t)(((uintptr_t)(d_ids + lo0) & 15u) >> 2);
     std::vector<uint64_t> rel(h_tok_off, h_tok_off + n_docs + 1);
@@ -2823,19 +2728,19 @@ void vocab_decode(mrg_ctx *c, const mrg_vocab *v, const uint32_t *d_ids, const u
     HIPCHK(hipMemsetAsync(P.cnt, 0, 8 * (P.nchunks + 1), s));
     HIPCHK(hipMemsetAsync(P.err, 0xFF, 8, s));
     mrg_dec_launch_bounds(P, s);
-    dec_rec(c, 0);
+    ev_rec(c, c->dec_ev, 0);
     mrg_dec_launch_count(P, v->T, v->W, s);
-    dec_rec(c, 1);
+    ev_rec(c, c->dec_ev, 1);
     mrg_scan_u64(P.cnt, P.cnt, P.nchunks + 1, stmp, s);
     mrg_dec_launch_offsets(P, v->T, v->W, s);
-    dec_rec(c, 2);
+    ev_rec(c, c->dec_ev, 2);
     HIPCHK(hipGetLastError());
     unsigned long long herr = 0;
     HIPCHK(hipMemcpyAsync(h_out_off, P.out_off, 8 * ((uint64_t)n_docs + 1), hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(&herr, P.err, 8, hipMemcpyDeviceToHost, s));
     sync(c);  // (also: the pageable `rel` and h_unk have been read)
-    c->dec_ms[0] = dec_ms(c, 0, 1);
-    c->dec_ms[1] = dec_ms(c, 1, 2);
+    c->dec_ms[0] = ev_ms(c, c->dec_ev, 0, 1);
+    c->dec_ms[1] = ev_ms(c, c->dec_ev, 1, 2);
     if (herr != ~0ull)
         raise(MRG_EINVAL, "mrg_vocab_decode: the id at index %llu is not in the vocabulary (%llu words%s)",
               (unsigned long long)(herr - shift + lo0), (unsigned long long)v->n,
@@ -2847,12 +2752,12 @@ void vocab_decode(mrg_ctx *c, const mrg_vocab *v, const uint32_t *d_ids, const u
                            (unsigned long long)total);
     P.out = d_out;
     P.out_n = total;
-    dec_rec(c, 2);
+    ev_rec(c, c->dec_ev, 2);
     if (total) mrg_dec_launch_emit(P, v->T, v->W, s);
-    dec_rec(c, 3);
+    ev_rec(c, c->dec_ev, 3);
     HIPCHK(hipGetLastError());
     sync(c);
-    c->dec_ms[2] = dec_ms(c, 2, 3);
+    c->dec_ms[2] = ev_ms(c, c->dec_ev, 2, 3);
 }
 
 void export_sizes(mrg_ctx *c, uint32_t n_owners, uint64_t *h_rec, uint64_t *h_heap) {
@@ -2861,16 +2766,15 @@ void export_sizes(mrg_ctx *c, uint32_t n_owners, uint64_t *h_rec, uint64_t *h_he
     if (n_owners == 0) raise(MRG_EINVAL, "n_owners must be > 0");
     acc_emit(c);
     wide_densify(c, 0);
-    Pool &p = c->pool;
+    Scratch sc(c->pool);
     hipStream_t s = c->stream;
-    unsigned long long *d = pget<unsigned long long>(p, 2ull * n_owners);
+    unsigned long long *d = sc.get<unsigned long long>(2ull * n_owners);
     HIPCHK(hipMemsetAsync(d, 0, 16ull * n_owners, s));
     c->xrec_vmax = std::max<uint64_t>(1, std::min<uint64_t>(MRG_XREC_VMAX, env_u64("MRG_TEST_XREC_VMAX", MRG_XREC_VMAX)));
     mrg_launch_export_count(c->keys.ks, c->keys.n, n_owners, d, d + n_owners, is_idx(c), c->xrec_vmax, s);
     std::vector<uint64_t> h(2ull * n_owners);
     HIPCHK(hipMemcpyAsync(h.data(), d, 16ull * n_owners, hipMemcpyDeviceToHost, s));
     sync(c);
-    p.put(d);
     c->n_owners = n_owners;
     c->exp_rec.assign(h.begin(), h.begin() + n_owners);
     c->exp_heap.assign(h.begin() + n_owners, h.end());
@@ -2883,7 +2787,7 @@ void export_sizes(mrg_ctx *c, uint32_t n_owners, uint64_t *h_rec, uint64_t *h_he
 void export_pack(mrg_ctx *c, void *d_rec, void *d_heap, bool wait = true) {
     need_job(c);
     if (!c->n_owners) raise(MRG_EINVAL, "call mrg_job_export_sizes first");
-    Pool &p = c->pool;
+    Scratch sc(c->pool);
     hipStream_t s = c->stream;
     const uint32_t G = c->n_owners;
     std::vector<uint64_t> base(2ull * G, 0);
@@ -2891,15 +2795,13 @@ void export_pack(mrg_ctx *c, void *d_rec, void *d_heap, bool wait = true) {
         base[o] = base[o - 1] + c->exp_rec[o - 1];
         base[G + o] = base[G + o - 1] + c->exp_heap[o - 1];
     }
-    uint64_t *d_base = pget<uint64_t>(p, 2ull * G);
-    unsigned long long *cur = pget<unsigned long long>(p, 2ull * G);
+    uint64_t *d_base = sc.get<uint64_t>(2ull * G);
+    unsigned long long *cur = sc.get<unsigned long long>(2ull * G);
     HIPCHK(hipMemcpyAsync(d_base, base.data(), 16ull * G, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemsetAsync(cur, 0, 16ull * G, s));
     mrg_launch_export_pack(c->keys.ks, c->keys.heap, c->keys.n, G, d_base, d_base + G, cur, cur + G, (XRec *)d_rec,
                            (uint8_t *)d_heap, is_idx(c), c->xrec_vmax, s);
     if (wait) sync(c);
-    p.put(d_base);  // later users of these blocks run after the pack on the same stream
-    p.put(cur);
 }
 
 // Received records -> the job's keys: exchange records (xr, include/mrgpu.h) or the text reduce's
@@ -2911,7 +2813,7 @@ void import_recs(mrg_ctx *c, const XRec *xr, const LRec *lr, uint64_t n_rec, con
     acc_release(c);            // (and the accumulator of mrg_job_map_add)
     c->keyed = false;
     c->st.map_batches = 0;
-    Pool &p = c->pool;
+    Scratch sc(c->pool);
     hipStream_t s = c->stream;
     std::vector<uint64_t> rec_end, heap_base;
     if (n_segs == 0) {
@@ -2928,15 +2830,15 @@ void import_recs(mrg_ctx *c, const XRec *xr, const LRec *lr, uint64_t n_rec, con
         }
         if (r != n_rec || h != heap_bytes) raise(MRG_EINVAL, "segment sizes do not add up to n_rec / heap_bytes");
     }
-    uint64_t *d_seg = pget<uint64_t>(p, 2ull * n_segs);
+    uint64_t *d_seg = sc.get<uint64_t>(2ull * n_segs);
     HIPCHK(hipMemcpyAsync(d_seg, rec_end.data(), 8ull * n_segs, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(d_seg + n_segs, heap_base.data(), 8ull * n_segs, hipMemcpyHostToDevice, s));
     LongItems li{};
     li.base = (const uint8_t *)d_heap;
-    li.start = pget<uint64_t>(p, n_rec);
-    li.rawlen = pget<uint32_t>(p, n_rec);
-    li.doc = pget<uint32_t>(p, n_rec);
-    li.cnt = pget<uint64_t>(p, n_rec);
+    li.start = sc.get<uint64_t>(n_rec);
+    li.rawlen = sc.get<uint32_t>(n_rec);
+    li.doc = sc.get<uint32_t>(n_rec);
+    li.cnt = sc.get<uint64_t>(n_rec);
     li.verbatim = 1;  // the exchange heap holds exact key bytes
     HIPCHK(hipMemsetAsync(&c->d_cnt[CNT_LONG], 0, 8, s));
     if (xr) mrg_launch_x_split_long(xr, n_rec, d_seg, d_seg + n_segs, n_segs, li, &c->d_cnt[CNT_LONG], is_idx(c), s);
@@ -2947,12 +2849,11 @@ void import_recs(mrg_ctx *c, const XRec *xr, const LRec *lr, uint64_t n_rec, con
     src.x = xr;
     src.lx = lr;
     src.n = n_rec;
-    ev_rec(c, 2);
+    ev_rec(c, c->ev, 2);
     aggregate(c, src, li);
-    ev_rec(c, 3);
+    ev_rec(c, c->ev, 3);
     sync(c);
-    p.put(d_seg); p.put(li.start); p.put(li.rawlen); p.put(li.doc); p.put(li.cnt);
-    c->st.ms_aggregate = ev_ms(c, 2, 3);
+    c->st.ms_aggregate = ev_ms(c, c->ev, 2, 3);
     c->mapped = c->keyed = true;
     c->reduced = false;
 }
@@ -3054,23 +2955,6 @@ int agree(mrg_ctx *c, mrg_comm *m, int flag) {
 // counts message carries it (the first collective), and one status all-reduce precedes the data
 // transfer; every rank then raises together (the failing rank its own error, the others MRG_ECOMM).
 // An RCCL error aborts the communicator.
-// Pool buffers of one exchange, returned to the pool on every exit (a failed collective or a watchdog
-// abort throws past the success path).
-struct PoolLease {
-    Pool &p;
-    uint8_t *b[4] = {nullptr, nullptr, nullptr, nullptr};
-    explicit PoolLease(Pool &pool) : p(pool) {}
-    PoolLease(const PoolLease &) = delete;
-    PoolLease &operator=(const PoolLease &) = delete;
-    uint8_t *get(int i, uint64_t bytes) { return b[i] = pget<uint8_t>(p, bytes); }
-    void put(int i) {
-        p.put(b[i]);
-        b[i] = nullptr;
-    }
-    ~PoolLease() {
-        for (int i = 0; i < 4; ++i) p.put(b[i]);
-    }
-};
 
 // A pair of timing events, destroyed on every exit.
 struct EventPair {
@@ -3103,13 +2987,14 @@ void job_shuffle(mrg_ctx *c, mrg_comm *m) {
     if (!c || !m || !m->comm) raise(MRG_EINVAL, "null context or communicator");
     if (m->device != c->device) raise(MRG_EINVAL, "communicator is on device %d, context on %d", m->device, c->device);
     check_not_aborted(m);
-    Pool &p = c->pool;
     hipStream_t s = c->stream;
     const uint32_t G = (uint32_t)m->n;
     const uint32_t me = (uint32_t)m->rank;
     const uint64_t X = MRG_XREC_BYTES;
-    enum { SREC, SHEAP, RREC, RHEAP };
-    PoolLease buf(p);  // send records / heap, receive records / heap: returned on every exit
+    // send records / heap, receive records / heap: returned on every exit (a failed collective or a
+    // watchdog abort throws past the success path)
+    Scratch buf(c->pool);
+    uint8_t *srec = nullptr, *sheap = nullptr, *rrec = nullptr, *rheap = nullptr;
     MrgError mine{MRG_OK, ""};
     // ---- local: export sizes and pack (the pack runs on the stream, no host wait)
     std::vector<uint64_t> sc(3ull * G, 0), rc(3ull * G, 0);  // per peer: records, heap bytes, status
@@ -3125,14 +3010,13 @@ void job_shuffle(mrg_ctx *c, mrg_comm *m) {
             sro[o + 1] = sro[o] + sc[3 * o];
             sho[o + 1] = sho[o] + sc[3 * o + 1];
         }
-        buf.get(SREC, sro[G] * X + 16);
-        buf.get(SHEAP, sho[G] + 16);
-        export_pack(c, buf.b[SREC], buf.b[SHEAP], false);
+        srec = buf.get<uint8_t>(sro[G] * X + 16);
+        sheap = buf.get<uint8_t>(sho[G] + 16);
+        export_pack(c, srec, sheap, false);
     } catch (const MrgError &e) {
         mine = e;
         std::fill(sc.begin(), sc.end(), 0);
     }
-    uint8_t *const srec = buf.b[SREC], *const sheap = buf.b[SHEAP];
     for (uint32_t o = 0; o < G; ++o) sc[3 * o + 2] = mine.code ? 1u : 0u;
     // ---- collective 1: the counts all-to-all (with every rank's status)
     HIPCHK(hipMemcpyAsync(m->d_counts, sc.data(), 24ull * G, hipMemcpyHostToDevice, s));
@@ -3158,8 +3042,8 @@ void job_shuffle(mrg_ctx *c, mrg_comm *m) {
     }
     try {
         test_fail("recv", (int)me);
-        buf.get(RREC, rro[G] * X + 16);
-        buf.get(RHEAP, rho[G] + 16);
+        rrec = buf.get<uint8_t>(rro[G] * X + 16);
+        rheap = buf.get<uint8_t>(rho[G] + 16);
     } catch (const MrgError &e) {
         mine = e;
     }
@@ -3168,7 +3052,6 @@ void job_shuffle(mrg_ctx *c, mrg_comm *m) {
         if (mine.code) throw mine;
         raise(MRG_ECOMM, "another rank of the exchange could not allocate its receive buffers");
     }
-    uint8_t *const rrec = buf.b[RREC], *const rheap = buf.b[RHEAP];
     // ---- collective 3: own slice by a device copy; peers by one send/recv group (each peer pair has
     // its own xGMI link)
     EventPair ev;
@@ -3201,8 +3084,8 @@ void job_shuffle(mrg_ctx *c, mrg_comm *m) {
     HIPCHK(hipEventRecord(ev.e1, s));
     HIPCHK(hipEventSynchronize(ev.e1));
     check_not_aborted(m);  // a watchdog abort ends a transfer early: its buffers are not to be used
-    buf.put(SREC);
-    buf.put(SHEAP);
+    buf.put(srec);
+    buf.put(sheap);
     // ---- local: re-aggregate what arrived (no collective after this point)
     const mrg_stats keep = c->st;
     job_import(c, rrec, rro[G], rheap, rho[G], seg_rec.data(), seg_heap.data(), G);  // ends with a host wait
@@ -3237,13 +3120,13 @@ void check_names(const char *const *names, uint32_t n) {
 // (worker.rs:117-140).  out = the R files' bytes concatenated, off[R + 1] their offsets.
 void text_map(mrg_ctx *c, const uint8_t *h, uint64_t n, uint32_t R, std::vector<uint8_t> &out,
               std::vector<uint64_t> &off) {
-    Pool &p = c->pool;
+    Scratch sc(c->pool);
     hipStream_t s = c->stream;
-    uint8_t *d = pget<uint8_t>(p, n + 64);
+    uint8_t *d = sc.get<uint8_t>(n + 64);
     if (n) HIPCHK(hipMemcpyAsync(d, h, n, hipMemcpyHostToDevice, s));
     const uint64_t nseg = mrg_text_segments(n);
-    uint64_t *cnt = pget<uint64_t>(p, nseg + 1), *base = pget<uint64_t>(p, nseg + 1);
-    uint64_t *stmp = pget<uint64_t>(p, mrg_scan_tmp_elems(nseg + 1));
+    uint64_t *cnt = sc.get<uint64_t>(nseg + 1), *base = sc.get<uint64_t>(nseg + 1);
+    uint64_t *stmp = sc.get<uint64_t>(mrg_scan_tmp_elems(nseg + 1));
     HIPCHK(hipMemsetAsync(cnt, 0, 8 * (nseg + 1), s));
     HIPCHK(hipMemsetAsync(&c->d_cnt[CNT_ERRPOS], 0xFF, 8, s));
     mrg_launch_text_tok(d, n, R, nullptr, cnt, nullptr, &c->d_cnt[CNT_ERRPOS], s);
@@ -3251,24 +3134,21 @@ void text_map(mrg_ctx *c, const uint8_t *h, uint64_t n, uint32_t R, std::vector<
     uint64_t T = 0;
     HIPCHK(hipMemcpyAsync(&T, base + nseg, 8, hipMemcpyDeviceToHost, s));
     read_counters(c);
-    auto done = [&]() { p.put(d); p.put(cnt); p.put(base); p.put(stmp); };
-    if (c->h_cnt[CNT_ERRPOS] != ~0ull) {
-        done();
+    if (c->h_cnt[CNT_ERRPOS] != ~0ull)
         raise(MRG_EUTF8, "stream did not contain valid UTF-8: byte offset %llu", (unsigned long long)c->h_cnt[CNT_ERRPOS]);
-    }
     off.assign(R + 1, 0);
     out.clear();
     if (T) {
-        TextTok *tok = pget<TextTok>(p, T);
+        TextTok *tok = sc.get<TextTok>(T);
         mrg_launch_text_tok(d, n, R, base, cnt, tok, &c->d_cnt[CNT_ERRPOS], s);
-        uint64_t *part = pget<uint64_t>(p, T), *kv = pget<uint64_t>(p, 4 * T);
-        uint32_t *idx = pget<uint32_t>(p, T);
-        void *stmp2 = p.get(mrg_sort_tmp_bytes(T));
+        uint64_t *part = sc.get<uint64_t>(T), *kv = sc.get<uint64_t>(4 * T);
+        uint32_t *idx = sc.get<uint32_t>(T);
+        void *stmp2 = sc.get<uint8_t>(mrg_sort_tmp_bytes(T));
         mrg_launch_text_keys(tok, T, part, idx, s);
         check_sort_n(T, "text partition sort");
         mrg_radix_sort_u64(part, idx, kv, T, stmp2, s);  // stable: input order inside a partition
-        uint64_t *L = pget<uint64_t>(p, T + 1), *O = pget<uint64_t>(p, T + 1);
-        uint64_t *stmp3 = pget<uint64_t>(p, mrg_scan_tmp_elems(T + 1));
+        uint64_t *L = sc.get<uint64_t>(T + 1), *O = sc.get<uint64_t>(T + 1);
+        uint64_t *stmp3 = sc.get<uint64_t>(mrg_scan_tmp_elems(T + 1));
         mrg_launch_text_len(tok, idx, T, L, s);
         mrg_scan_u64(L, O, T, stmp3, s);
         uint64_t last[2];
@@ -3276,25 +3156,22 @@ void text_map(mrg_ctx *c, const uint8_t *h, uint64_t n, uint32_t R, std::vector<
         HIPCHK(hipMemcpyAsync(&last[1], L + (T - 1), 8, hipMemcpyDeviceToHost, s));
         sync(c);
         const uint64_t total = last[0] + last[1];
-        uint8_t *ob = pget<uint8_t>(p, total + 16);
-        uint64_t *doff = pget<uint64_t>(p, R + 1);
+        uint8_t *ob = sc.get<uint8_t>(total + 16);
+        uint64_t *doff = sc.get<uint64_t>(R + 1);
         mrg_launch_text_write(d, tok, idx, T, O, ob, s);
         mrg_launch_text_part_off(part, O, T, R, total, doff, s);
         out.resize(total);
         HIPCHK(hipMemcpyAsync(out.data(), ob, total, hipMemcpyDeviceToHost, s));
         HIPCHK(hipMemcpyAsync(off.data(), doff, 8ull * (R + 1), hipMemcpyDeviceToHost, s));
         sync(c);
-        p.put(tok); p.put(part); p.put(kv); p.put(idx); p.put(stmp2); p.put(L); p.put(O); p.put(stmp3);
-        p.put(ob); p.put(doff);
     }
-    done();
 }
 
 // One reduce task from text intermediates (worker.rs:79-109, 157-193): returns mr-{r}.txt.
 void text_reduce(mrg_ctx *c, const uint8_t *const *files, const uint64_t *sizes, size_t k, uint32_t flags,
                  std::vector<uint8_t> &out) {
     job_begin(c, MRG_APP_WC, 1, flags);  // every key read goes to the one output file
-    Pool &p = c->pool;
+    Scratch sc(c->pool);
     hipStream_t s = c->stream;
     std::vector<uint64_t> fo(k + 1, 0), fe(k);
     for (size_t i = 0; i < k; ++i) {
@@ -3302,23 +3179,23 @@ void text_reduce(mrg_ctx *c, const uint8_t *const *files, const uint64_t *sizes,
         fo[i + 1] = (fe[i] + 63) & ~63ull;  // files on 64-byte boundaries (one file per segment)
     }
     const uint64_t total = fo[k];
-    uint8_t *d = pget<uint8_t>(p, total + 64);
+    uint8_t *d = sc.get<uint8_t>(total + 64);
     HIPCHK(hipMemsetAsync(d, 0, total + 64, s));
     for (size_t i = 0; i < k; ++i)
         if (sizes[i]) HIPCHK(hipMemcpyAsync(d + fo[i], files[i], sizes[i], hipMemcpyHostToDevice, s));
     const uint32_t nf = (uint32_t)std::max<size_t>(k, 1);
-    uint64_t *dfo = pget<uint64_t>(p, nf + 1), *dfe = pget<uint64_t>(p, nf);
+    uint64_t *dfo = sc.get<uint64_t>(nf + 1), *dfe = sc.get<uint64_t>(nf);
     if (k) {
         HIPCHK(hipMemcpyAsync(dfo, fo.data(), 8 * k, hipMemcpyHostToDevice, s));
         HIPCHK(hipMemcpyAsync(dfe, fe.data(), 8 * k, hipMemcpyHostToDevice, s));
     }
-    unsigned long long *err = pget<unsigned long long>(p, 3);  // [utf8 pos, format pos, empty-key lines]
+    unsigned long long *err = sc.get<unsigned long long>(3);  // [utf8 pos, format pos, empty-key lines]
     HIPCHK(hipMemsetAsync(err, 0xFF, 16, s));
     HIPCHK(hipMemsetAsync(err + 2, 0, 8, s));
     mrg_launch_utf8_check(d, total, err, s);  // read_to_string (worker.rs:93); zero padding is valid
     const uint64_t nseg = total / 64;
-    uint64_t *cnt = pget<uint64_t>(p, nseg + 1), *base = pget<uint64_t>(p, nseg + 1);
-    uint64_t *stmp = pget<uint64_t>(p, mrg_scan_tmp_elems(nseg + 1));
+    uint64_t *cnt = sc.get<uint64_t>(nseg + 1), *base = sc.get<uint64_t>(nseg + 1);
+    uint64_t *stmp = sc.get<uint64_t>(mrg_scan_tmp_elems(nseg + 1));
     HIPCHK(hipMemsetAsync(cnt, 0, 8 * (nseg + 1), s));
     if (k) mrg_launch_text_lines(d, dfo, dfe, nf, nseg, nullptr, cnt, nullptr, err, err + 2, s);
     mrg_scan_u64(cnt, base, nseg + 1, stmp, s);
@@ -3327,7 +3204,6 @@ void text_reduce(mrg_ctx *c, const uint8_t *const *files, const uint64_t *sizes,
     unsigned long long herr[3];
     HIPCHK(hipMemcpyAsync(herr, err, sizeof herr, hipMemcpyDeviceToHost, s));
     sync(c);
-    auto done = [&]() { p.put(d); p.put(dfo); p.put(dfe); p.put(err); p.put(cnt); p.put(base); p.put(stmp); };
     auto where = [&](uint64_t pos, uint64_t &f) {
         f = 0;
         while (f + 1 < k && fo[f + 1] <= pos) ++f;
@@ -3336,20 +3212,18 @@ void text_reduce(mrg_ctx *c, const uint8_t *const *files, const uint64_t *sizes,
     if (herr[0] != ~0ull) {
         uint64_t f;
         const uint64_t at = where(herr[0], f);
-        done();
         raise(MRG_EUTF8, "intermediate file %llu is not valid UTF-8 (byte offset %llu)", (unsigned long long)f,
               (unsigned long long)at);
     }
     if (herr[1] != ~0ull) {
         uint64_t f;
         const uint64_t at = where(herr[1], f);
-        done();
         raise(MRG_EINVAL, "intermediate file %llu: the line at byte %llu does not split into `key value` "
               "(worker.rs:100 asserts two space-separated fields; keys hold no NUL)", (unsigned long long)f,
               (unsigned long long)at);
     }
     const uint64_t N = fb[k];
-    LRec *x = pget<LRec>(p, std::max<uint64_t>(N, 1));
+    LRec *x = sc.get<LRec>(std::max<uint64_t>(N, 1));
     if (k) mrg_launch_text_lines(d, dfo, dfe, nf, nseg, base, cnt, x, err, err + 2, s);  // also counts empty keys
     HIPCHK(hipMemcpyAsync(&herr[2], err + 2, 8, hipMemcpyDeviceToHost, s));
     sync(c);
@@ -3368,8 +3242,6 @@ void text_reduce(mrg_ctx *c, const uint8_t *const *files, const uint64_t *sizes,
         const std::string line = " " + std::to_string(herr[2]) + "\n";
         out.assign(line.begin(), line.end());
     }
-    p.put(x);
-    done();
 }
 
 extern "C" {
@@ -3688,20 +3560,16 @@ int mrg_map(mrg_ctx *c, int app, const uint8_t *h_bytes, size_t n, const char *d
         (void)doc;
         HIPCHK(hipSetDevice(c->device));
         job_begin(c, app, n_reduce, flags);
-        uint8_t *d = pget<uint8_t>(c->pool, n + 64);
+        Scratch sc(c->pool);
+        uint8_t *d = sc.get<uint8_t>(n + 64);
         if (n) HIPCHK(hipMemcpyAsync(d, h_bytes, n, hipMemcpyHostToDevice, c->stream));
         const uint64_t off[2] = {0, n};
         c->d_in = d;
         c->doc_off.assign(off, off + 2);
         c->doc_ids.assign(1, doc_id);
-        try {
-            job_map(c);
-        } catch (...) {
-            c->pool.put(d);
-            throw;
-        }
+        job_map(c);
         export_sizes(c, n_reduce, nullptr, nullptr);
-        mrg_parts *P = new mrg_parts();
+        std::unique_ptr<mrg_parts> P(new mrg_parts());
         P->R = n_reduce;
         P->rec_off.assign(n_reduce + 1, 0);
         P->heap_off.assign(n_reduce + 1, 0);
@@ -3709,8 +3577,8 @@ int mrg_map(mrg_ctx *c, int app, const uint8_t *h_bytes, size_t n, const char *d
             P->rec_off[r + 1] = P->rec_off[r] + c->exp_rec[r];
             P->heap_off[r + 1] = P->heap_off[r] + c->exp_heap[r];
         }
-        XRec *dx = pget<XRec>(c->pool, P->rec_off[n_reduce]);
-        uint8_t *dh = pget<uint8_t>(c->pool, P->heap_off[n_reduce] + 1);
+        XRec *dx = sc.get<XRec>(P->rec_off[n_reduce]);
+        uint8_t *dh = sc.get<uint8_t>(P->heap_off[n_reduce] + 1);
         export_pack(c, dx, dh);
         P->recs.resize(P->rec_off[n_reduce] * sizeof(XRec));
         P->heap.resize(P->heap_off[n_reduce]);
@@ -3719,10 +3587,7 @@ int mrg_map(mrg_ctx *c, int app, const uint8_t *h_bytes, size_t n, const char *d
         if (!P->heap.empty())
             HIPCHK(hipMemcpyAsync(P->heap.data(), dh, P->heap.size(), hipMemcpyDeviceToHost, c->stream));
         sync(c);
-        c->pool.put(dx);
-        c->pool.put(dh);
-        c->pool.put(d);
-        *out = P;
+        *out = P.release();
     });
 }
 
@@ -3763,8 +3628,9 @@ int mrg_reduce(mrg_ctx *c, int app, uint32_t r, const mrg_parts *const *in, size
             seg_heap.push_back(hb - ha);
         }
         const uint64_t nrec = recs.size() / sizeof(XRec);
-        uint8_t *dr = pget<uint8_t>(c->pool, recs.size() + 16);
-        uint8_t *dh = pget<uint8_t>(c->pool, heap.size() + 16);
+        Scratch sc(c->pool);
+        uint8_t *dr = sc.get<uint8_t>(recs.size() + 16);
+        uint8_t *dh = sc.get<uint8_t>(heap.size() + 16);
         if (!recs.empty()) HIPCHK(hipMemcpyAsync(dr, recs.data(), recs.size(), hipMemcpyHostToDevice, c->stream));
         if (!heap.empty()) HIPCHK(hipMemcpyAsync(dh, heap.data(), heap.size(), hipMemcpyHostToDevice, c->stream));
         job_import(c, dr, nrec, dh, heap.size(), seg_rec.data(), seg_heap.data(), (uint32_t)seg_rec.size());
@@ -3774,8 +3640,6 @@ int mrg_reduce(mrg_ctx *c, int app, uint32_t r, const mrg_parts *const *in, size
         if (!o) raise(MRG_ENOMEM, "host allocation failed");
         if (b > a) HIPCHK(hipMemcpyAsync(o, c->d_out + a, b - a, hipMemcpyDeviceToHost, c->stream));
         sync(c);
-        c->pool.put(dr);
-        c->pool.put(dh);
         *h_out = o;
         *h_out_len = b - a;
     });
