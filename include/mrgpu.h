@@ -248,9 +248,11 @@ int mrg_vocab_encode(mrg_ctx *ctx, const mrg_vocab *v, const uint8_t *d_bytes, c
  * Validation -- MRG_EINVAL unless stated, mrg_last_error names the 0-based line ("line N"), *out is
  * NULL, nothing is leaked, the context and every other vocabulary stay usable:
  *   - the text is empty or ends in '\n';
+ *   - every line is valid UTF-8 (else MRG_EUTF8, with the line named, as the map reports it): checked
+ *     first, over the whole line, so a line that strict UTF-8 decoding rejects is MRG_EUTF8 whatever
+ *     else is wrong with it;
  *   - every line is `word`, one ' ', then 1 to 20 ASCII digits (the count is not interpreted further):
  *     an empty line, a missing count or a second space is an error; the word is not empty;
- *   - the word is valid UTF-8 (else MRG_EUTF8, with the line named, as the map reports it);
  *   - every codepoint of the word is \w by the map's tables, i.e. the word is accepted exactly when
  *     wc::map over it produces that word as its single key (don't, a-dash-b and "a b" are rejected);
  *   - no word stands on two lines ("duplicate", naming a line whose word also stands on another one);

@@ -596,34 +596,38 @@ __global__ __launch_bounds__(ENC_WG) void k_enc(EncArgs A, VocTable T) {
 
 // ---------------------------------------------------------------- vocabulary from text
 // Line i = text[line_off[i], line_off[i + 1]), the last byte its '\n' (the host cut the lines there):
-// `word`, one ' ', 1 to 20 ASCII digits; the word non-empty, valid UTF-8, every codepoint \w.  One lane
-// per line; the first bad line wins by atomicMin on line * 4 + reason.
+// valid UTF-8 (checked first, over the whole line: MRG_EUTF8 whatever else is wrong with it), then
+// `word`, one ' ', 1 to 20 ASCII digits; the word non-empty, every codepoint \w.  One lane per line; the
+// first bad line wins by atomicMin on line * 4 + reason.
 __global__ __launch_bounds__(ENC_WG) void k_voc_check(VocTable T, uint32_t *wlen, unsigned long long *err) {
     const uint64_t i = (uint64_t)blockIdx.x * ENC_WG + threadIdx.x;
     if (i >= T.n) return;
     const uint64_t lo = T.line_off[i], hi = T.line_off[i + 1] - 1u;  // [lo, hi): the line without its '\n'
     const uint8_t *t = T.text;
-    uint64_t sp = lo;
-    while (sp < hi && t[sp] != 0x20u) ++sp;
-    const uint64_t nd = hi > sp ? hi - sp - 1u : 0u;  // bytes after the space
-    bool form = sp > lo && sp < hi && nd >= 1u && nd <= 20u;
-    for (uint64_t q = sp + 1u; form && q < hi; ++q) form = (uint32_t)t[q] - '0' < 10u;
-    uint32_t bad = form ? 3u : MRG_VOC_BAD_FORM;
-    if (form) {
-        auto rd = [&](uint64_t x) -> uint32_t { return t[x]; };
-        for (uint64_t p = lo; p < sp;) {
-            uint32_t cp, raw;
-            const int l = mrg_utf8_decode(rd, p, sp, &cp, &raw);
-            if (!l) {
-                bad = MRG_VOC_BAD_UTF8;
-                break;
-            }
-            if (mrg_uclass(cp) != MRG_CLS_W) {
-                bad = MRG_VOC_BAD_CLASS;
-                break;
-            }
-            p += (uint64_t)l;
+    auto rd = [&](uint64_t x) -> uint32_t { return t[x]; };
+    // one pass over the line: its UTF-8, the first space (hi: none) and whether every codepoint before it is \w
+    uint32_t bad = 3u;
+    uint64_t sp = hi;
+    bool word = true;
+    for (uint64_t p = lo; p < hi;) {
+        uint32_t cp = 0, raw;
+        const int l = mrg_utf8_decode(rd, p, hi, &cp, &raw);
+        if (!l) {
+            bad = MRG_VOC_BAD_UTF8;
+            break;
         }
+        if (sp == hi) {
+            if (cp == 0x20u) sp = p;
+            else if (mrg_uclass(cp) != MRG_CLS_W) word = false;
+        }
+        p += (uint64_t)l;
+    }
+    if (bad == 3u) {
+        const uint64_t nd = hi > sp ? hi - sp - 1u : 0u;  // bytes after the space
+        bool form = sp > lo && sp < hi && nd >= 1u && nd <= 20u;
+        for (uint64_t q = sp + 1u; form && q < hi; ++q) form = (uint32_t)t[q] - '0' < 10u;
+        if (!form) bad = MRG_VOC_BAD_FORM;
+        else if (!word) bad = MRG_VOC_BAD_CLASS;
     }
     wlen[i] = bad == 3u ? (uint32_t)(sp - lo) : 0u;
     if (bad != 3u) atomicMin(err, (unsigned long long)(i * 4u + bad));

@@ -739,23 +739,30 @@ __device__ __forceinline__ uint32_t generic_tile(const MapArgs &A, LdsTable<CAP,
         uint64_t p = s0;
         bool prevS = true;
         if (!done && s0 > doc_lo) {
-            uint32_t j = 0;  // continuation bytes belong to a codepoint that starts before s0
-            while (s0 + j < s1 && mrg_is_cont(rd(s0 + j))) ++j;
-            p = s0 + j;
-            uint32_t k = 1;  // lead of the codepoint ending at p - 1 (at most 3 continuation bytes back)
-            while (k <= 3 && p - k >= doc_lo && mrg_is_cont(rd(p - k))) ++k;
-            const uint64_t q = p - k;
-            if (q < doc_lo || mrg_is_cont(rd(q))) {
-                report_error(A.counters, s0);  // orphan continuation bytes
+            // q: the last byte before s0 that is no continuation byte (at most 4 back): the lead of the
+            // codepoint that ends at s0 - 1 or reaches into the segment.  The walk starts where that
+            // codepoint ends, exactly as a decoder coming from the document's start would arrive there,
+            // so a position reported from here on is the first invalid byte unless an earlier lane
+            // reports a smaller one (never a byte before it: atomicMin keeps the true first).
+            uint32_t k = 1;
+            while (k < 4 && s0 - k > doc_lo && mrg_is_cont(rd(s0 - k))) ++k;
+            const uint64_t q = s0 - k;
+            uint32_t cp = 0, raw;
+            const int l = mrg_is_cont(rd(q)) ? -1 : mrg_utf8_decode(rd, q, doc_hi, &cp, &raw);
+            if (l < 0) {
+                // four continuation bytes in a row, or the document starts with one: the first invalid byte
+                // lies before s0 and the lane that owns it reports it -- in this tile or in an earlier one,
+                // which is walked here too: a tile or block holding a continuation byte that no codepoint
+                // covers is never tokenized by the fast path (the class fix defers it, C != nam).  s0 is
+                // only this lane's upper bound for the atomicMin.
+                report_error(A.counters, s0);
+                done = true;
+            } else if (l == 0 || q + (uint64_t)l < s0) {  // a bad lead, or s0 - 1 is an orphan continuation byte
+                report_error(A.counters, l == 0 ? q : q + (uint64_t)l);
                 done = true;
             } else {
-                uint32_t cp, raw;
-                const int l = mrg_utf8_decode(rd, q, doc_hi, &cp, &raw);
-                if (j > 0 && (l == 0 || q + (uint64_t)l != p)) {
-                    report_error(A.counters, s0);
-                    done = true;
-                }
-                prevS = (l > 0 && q + (uint64_t)l == p) ? (mrg_uclass(cp) == MRG_CLS_S) : false;
+                p = q + (uint64_t)l;  // >= s0: an orphan continuation byte at p fails the decode below
+                prevS = mrg_uclass(cp) == MRG_CLS_S;
             }
             if (p >= s1) done = true;
         }

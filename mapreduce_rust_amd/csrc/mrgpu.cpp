@@ -2608,7 +2608,7 @@ void vocab_encode(mrg_ctx *c, const mrg_vocab *v, const uint8_t *d_bytes, const 
 }
 
 // A vocabulary from its text: the host cuts the lines, the device checks every
-// line's form and its word's codepoints (k_voc_check), builds the table as mrg_job_vocab does, and looks
+// line's UTF-8, its form and its word's codepoints (k_voc_check), builds the table as mrg_job_vocab does, and looks
 // every word up again to find a word that stands on two lines (k_voc_verify).  No job state is touched.
 mrg_vocab *vocab_from_text(mrg_ctx *c, const uint8_t *h_text, uint64_t bytes, uint32_t flags) {
     if (!c) raise(MRG_EINVAL, "null context");
@@ -2646,7 +2646,7 @@ mrg_vocab *vocab_from_text(mrg_ctx *c, const uint8_t *h_text, uint64_t bytes, ui
             const unsigned long long line = herr >> 2;
             switch ((uint32_t)(herr & 3u)) {
                 case MRG_VOC_BAD_UTF8:
-                    raise(MRG_EUTF8, "mrg_vocab_from_text: line %llu: the word is not valid UTF-8", line);
+                    raise(MRG_EUTF8, "mrg_vocab_from_text: line %llu: not valid UTF-8", line);
                 case MRG_VOC_BAD_CLASS:
                     raise(MRG_EINVAL, "mrg_vocab_from_text: line %llu: the word holds a codepoint that is not \\w", line);
                 default:
