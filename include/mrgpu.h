@@ -120,7 +120,8 @@ typedef struct {
  * map_batches (same size and offset)
  * (6, additive): mrg_job_vocab, mrg_vocab_size, mrg_vocab_copy_text, mrg_vocab_free, mrg_vocab_encode,
  * MRG_ID_UNK
- * (6, additive): mrg_vocab_from_text, mrg_vocab_decode */
+ * (6, additive): mrg_vocab_from_text, mrg_vocab_decode
+ * (6, additive): mrg_vocab_term_counts */
 #define MRG_ABI_VERSION 6
 
 const char *mrg_last_error(void);
@@ -279,6 +280,33 @@ int mrg_vocab_from_text(mrg_ctx *ctx, const uint8_t *h_text, uint64_t bytes, uin
 int mrg_vocab_decode(mrg_ctx *ctx, const mrg_vocab *v, const uint32_t *d_ids, const uint64_t *h_tok_off,
                      uint32_t n_docs, const uint8_t *h_unk, uint32_t unk_len, uint8_t *d_out, uint64_t cap,
                      uint64_t *h_out_off);
+/* Ids -> per-document term counts: the document-term matrix in CSR form.  The input layout is that of
+ * mrg_vocab_decode: document i's ids are d_ids[h_tok_off[i] .. h_tok_off[i+1]) (d_ids: device memory,
+ * 4-byte aligned; h_tok_off: n_docs + 1 non-decreasing entries, h_tok_off[0] may be greater than 0).
+ * Row i is d_terms[h_row_off[i] .. h_row_off[i+1]): the distinct ids of document i other than MRG_ID_UNK,
+ * in ascending order (a vocabulary of mrg_job_vocab is ranked, so that is most frequent in the vocabulary
+ * first); d_counts at the same positions holds the occurrences of each id in that document.  h_row_off
+ * has n_docs + 1 entries and h_row_off[0] = 0.  The output is fully determined by the input: no order
+ * depends on scheduling.
+ * MRG_ID_UNK never appears in a row.  h_unk may be NULL; otherwise h_unk[i] (n_docs entries) is the
+ * number of MRG_ID_UNK in document i, so sum(counts of row i) + h_unk[i] = h_tok_off[i+1] - h_tok_off[i].
+ * Any other id >= the vocabulary's words: MRG_EINVAL, mrg_last_error names the smallest index in d_ids
+ * of such an id ("index N"), the outputs are then unspecified, the context and the vocabulary stay
+ * usable.  An empty vocabulary is valid: every id must then be MRG_ID_UNK.
+ * A document of more than 0xFFFFFFFF ids: MRG_EINVAL before any device work, so every count fits 32 bits.
+ * d_terms = NULL and d_counts = NULL: sizes only -- h_row_off and h_unk are filled, nothing else is
+ * written; exactly one of the two NULL: MRG_EINVAL.  Otherwise cap (entries of each buffer) <
+ * h_row_off[n_docs] returns MRG_EINVAL with both buffers untouched.  cap >= the number of ids always
+ * suffices, so a caller may skip the sizing call.  n_docs = 0 or no ids: all-zero offsets, MRG_OK.  A
+ * vocabulary of another device: MRG_EINVAL.
+ * The call needs no job and touches no job state (it is legal between mrg_job_map_add batches).  It
+ * runs on the context's stream with scratch from the context's pool, all returned before the call ends,
+ * on error exits too; on return the outputs are complete.  Scratch: 24 bytes per document, 4 bytes per
+ * non-empty document, and for the documents of more than 4096 ids, which are processed in slices of at
+ * most 2^25 ids together (a longer document alone), about 16.5 bytes per id of the largest slice. */
+int mrg_vocab_term_counts(mrg_ctx *ctx, const mrg_vocab *v, const uint32_t *d_ids, const uint64_t *h_tok_off,
+                          uint32_t n_docs, uint32_t *d_terms, uint32_t *d_counts, uint64_t cap,
+                          uint64_t *h_row_off, uint64_t *h_unk);
 
 /* ---- multi-GPU: one rank per GPU, the shuffle as an RCCL all-to-all over xGMI ----
  * The reference moves map output to the reduce workers through mr-{m}-{r}.txt files in a shared

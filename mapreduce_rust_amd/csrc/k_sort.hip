@@ -124,6 +124,11 @@ struct KVTraits {
     static constexpr int NPASS = 8;
     __device__ static __forceinline__ uint32_t digit(const R &r, int q) { return (uint32_t)(r.key >> (8 * q)) & 0xFFu; }
 };
+struct K64Traits {  // bare u64 keys (mrg_radix_sort_u64_keys)
+    using R = uint64_t;
+    static constexpr int NPASS = 8;
+    __device__ static __forceinline__ uint32_t digit(const R &r, int q) { return (uint32_t)(r >> (8 * q)) & 0xFFu; }
+};
 
 // all-pass histograms in one read: hist[q * 256 + d], for the passes in qmask only.  A digit that
 // is the same on every active lane (constant bytes: zero padding of short keys, the partition's
@@ -540,4 +545,18 @@ void mrg_radix_sort_u64(uint64_t *keys, uint32_t *vals, uint64_t *kv_tmp, uint64
     for (int q = 0; q < 8; ++q) want[q] = true;
     KV64 *r = radix_sort_t<KVTraits>(a, b, n, want, tmp, s, nullptr);
     hipLaunchKernelGGL(k_unpack_kv, dim3(g), dim3(256), 0, s, r, n, keys, vals);
+}
+
+uint64_t mrg_sort_u64_keys_tmp_bytes(uint64_t n) {
+    const uint64_t ntiles = (n + TILE - 1) / TILE;
+    return sizeof(unsigned long long) * 8 * 256 + sizeof(uint32_t) * (256 * ntiles + scan_tmp(256 * ntiles)) + 256;
+}
+
+// Bare u64 keys, ascending, between keys and alt (n each): only the byte passes in byte_mask run (bit q =
+// key bits [8 q, 8 q + 8); the other bytes must be equal in all keys).  Returns the buffer with the result.
+uint64_t *mrg_radix_sort_u64_keys(uint64_t *keys, uint64_t *alt, uint64_t n, uint32_t byte_mask, void *tmp,
+                                  hipStream_t s, int *passes_run) {
+    bool want[8];
+    for (int q = 0; q < 8; ++q) want[q] = (byte_mask >> q) & 1u;
+    return radix_sort_t<K64Traits>(keys, alt, n, want, tmp, s, passes_run);
 }

@@ -321,6 +321,12 @@ SortRec *mrg_msd_sort_finish(SortRec *recs, SortRec *alt, uint64_t n, const Sort
                              uint32_t nb);
 // Stable sort of (u64 key, u32 val) pairs by key, in place in (keys, vals); kv_tmp holds 4n u64.
 void mrg_radix_sort_u64(uint64_t *keys, uint32_t *vals, uint64_t *kv_tmp, uint64_t n, void *tmp, hipStream_t s);
+// Bare u64 keys ascending, between keys and alt (n each); only the byte passes in byte_mask run (bit q =
+// key bits [8 q, 8 q + 8); every other byte must be the same in all keys).  n < 2^32.  Returns the buffer
+// (keys or alt) with the result; tmp holds mrg_sort_u64_keys_tmp_bytes(n) bytes.
+uint64_t mrg_sort_u64_keys_tmp_bytes(uint64_t n);
+uint64_t *mrg_radix_sort_u64_keys(uint64_t *keys, uint64_t *alt, uint64_t n, uint32_t byte_mask, void *tmp,
+                                  hipStream_t s, int *passes_run);
 
 // ---- k_format.hip
 struct FormatArgs {
@@ -600,6 +606,38 @@ void mrg_dec_launch_bounds(const DecPlan &p, hipStream_t s);
 void mrg_dec_launch_count(const DecPlan &p, const VocTable &t, const VocWords &w, hipStream_t s);    // fills cnt, err
 void mrg_dec_launch_offsets(const DecPlan &p, const VocTable &t, const VocWords &w, hipStream_t s);  // after the scan of cnt
 void mrg_dec_launch_emit(const DecPlan &p, const VocTable &t, const VocWords &w, hipStream_t s);
+
+// ---- k_terms.hip: per-document term counts of id sequences
+// One mrg_vocab_term_counts call.  Positions are id indices from `in`; lists hold document indices.
+struct TermsPlan {
+    const uint32_t *in;
+    const uint64_t *tok_off;     // [n_docs + 1] device copy of the offsets
+    uint64_t n_words;            // ids >= n_words other than MRG_ID_UNK are reported in *err
+    uint64_t *len;               // [n_docs + 1] zeroed: distinct ids per document, then (scanned in place) row offsets
+    uint64_t *unk;               // [n_docs] zeroed: MRG_ID_UNK per document
+    uint32_t *terms, *counts;    // the rows (emit only)
+    unsigned long long *err;     // all ones: smallest index of an id that is not in the vocabulary (atomicMin)
+};
+// The documents list[0, n) of at most MRG_TERMS_WAVE_MAX (wg: MRG_TERMS_WG_MAX) ids each, one wave (one
+// workgroup) per document; emit: write the rows (len holds the row offsets), else count into len / unk.
+void mrg_terms_launch_lds(const TermsPlan &p, const uint32_t *list, uint32_t n, bool wg, bool emit, hipStream_t s);
+// A slice of the large path: documents ldoc[0, nd), whose ids stand concatenated at soff[j] (soff[nd] = m).
+struct TermsSlice {
+    const uint32_t *ldoc;        // [nd] document indices
+    const uint64_t *soff;        // [nd + 1]
+    uint32_t nd;
+    uint64_t m;                  // ids of the slice (< 2^32)
+};
+// keys[i] = (rank j of the document in the slice) << 32 | min(id, n_words) (MRG_ID_UNK becomes n_words)
+void mrg_terms_launch_keys(const TermsPlan &p, const TermsSlice &sl, uint64_t *keys, hipStream_t s);
+// over the sorted keys: flag[i] = 1 where a run of a vocabulary id starts (flag[m] = 0)
+void mrg_terms_launch_flags(const uint64_t *keys, uint64_t m, uint64_t n_words, uint32_t *flag, hipStream_t s);
+// E = the exclusive scan of flag: len / unk of every document of the slice
+void mrg_terms_launch_rows(const TermsPlan &p, const TermsSlice &sl, const uint64_t *keys, const uint32_t *E,
+                           hipStream_t s);
+// pos[E[i]] = i for every run start, then the rows from (keys, E, pos); p.len holds the row offsets
+void mrg_terms_launch_write(const TermsPlan &p, const TermsSlice &sl, const uint64_t *keys, const uint32_t *E,
+                            uint32_t *pos, hipStream_t s);
 
 // ---- k_gen.hip
 int mrg_gen_zipf_impl(uint8_t *dst, uint64_t n, uint64_t seed, uint64_t file_index, uint32_t vocab, double s, uint32_t style,

@@ -30,6 +30,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "mrg_device.h"
 #include "mrg_internal.h"
 #include "mrgpu.h"
 
@@ -447,6 +448,12 @@ struct mrg_ctx {
     uint64_t dec_info[8] = {};
     double dec_ms[4] = {};
     hipEvent_t dec_ev[6] = {};      // created on first use
+    // last mrg_vocab_term_counts (mrg_terms_info): ids, row entries, UNK, documents of the wave / workgroup /
+    // large path, large-path slices, scratch bytes; ms of the LDS paths' count, the large path's count and
+    // the row scan, the LDS paths' emit, the large path's emit (with mrg_set_timing)
+    uint64_t terms_info[8] = {};
+    double terms_ms[4] = {};
+    hipEvent_t terms_ev[6] = {};    // created on first use
 };
 
 // A vocabulary (mrg_job_vocab, mrg_vocab_from_text): one device allocation of its own -- the "word count\n"
@@ -558,7 +565,7 @@ void read_counters(mrg_ctx *c) {
 }
 
 // Timing events (mrg_set_timing) of one of the context's event arrays: c->ev (made by mrg_open), or
-// c->enc_ev / c->dec_ev, which ev_make creates on first use.
+// c->enc_ev / c->dec_ev / c->terms_ev, which ev_make creates on first use.
 template <size_t N>
 void ev_make(mrg_ctx *c, hipEvent_t (&ev)[N]) {
     if (!c->timing) return;
@@ -2760,6 +2767,187 @@ void vocab_decode(mrg_ctx *c, const mrg_vocab *v, const uint32_t *d_ids, const u
     c->dec_ms[2] = ev_ms(c, c->dec_ev, 2, 3);
 }
 
+// Ids -> per-document term counts in CSR form (k_terms.hip): the documents are
+// listed by path on the host; a count pass (LDS sort per document, radix sort per large slice) gives every
+// row's length and UNK count, the scan the row offsets, an emit pass the rows.  Touches no job state;
+// scratch comes from the pool and goes back on every exit.
+void vocab_term_counts(mrg_ctx *c, const mrg_vocab *v, const uint32_t *d_ids, const uint64_t *h_tok_off, uint32_t n_docs,
+                       uint32_t *d_terms, uint32_t *d_counts, uint64_t cap, uint64_t *h_row_off, uint64_t *h_unk) {
+    if (!c) raise(MRG_EINVAL, "null context");
+    if (!v) raise(MRG_EINVAL, "null vocabulary");
+    if (!h_tok_off || !h_row_off) raise(MRG_EINVAL, "null offsets (h_tok_off and h_row_off need n_docs + 1 entries)");
+    if (v->device != c->device) raise(MRG_EINVAL, "the vocabulary lives on device %d, the context on device %d", v->device,
+                                      c->device);
+    if (n_docs == 0xFFFFFFFFu) raise(MRG_EINVAL, "n_docs out of range");
+    if ((uintptr_t)d_ids & 3u) raise(MRG_EINVAL, "the ids must be 4-byte aligned");
+    if (!d_terms != !d_counts) raise(MRG_EINVAL, "d_terms and d_counts must both be given, or both be NULL (sizes only)");
+    if (((uintptr_t)d_terms | (uintptr_t)d_counts) & 3u) raise(MRG_EINVAL, "d_terms and d_counts must be 4-byte aligned");
+    // the documents by path (an empty document takes none: its row length stays 0)
+    std::vector<uint32_t> list[3];
+    for (uint32_t i = 0; i < n_docs; ++i) {
+        if (h_tok_off[i + 1] < h_tok_off[i]) raise(MRG_EINVAL, "token offsets must be non-decreasing");
+        const uint64_t T = h_tok_off[i + 1] - h_tok_off[i];
+        if (T > 0xFFFFFFFFull)
+            raise(MRG_EINVAL, "mrg_vocab_term_counts: document %u has %llu ids: at most 4294967295 (counts are 32 bits)", i,
+                  (unsigned long long)T);
+        if (T) list[T <= MRG_TERMS_WAVE_MAX ? 0 : T <= MRG_TERMS_WG_MAX ? 1 : 2].push_back(i);
+    }
+    HIPCHK(hipSetDevice(c->device));
+    memset(c->terms_info, 0, sizeof c->terms_info);
+    memset(c->terms_ms, 0, sizeof c->terms_ms);
+    const uint64_t n_ids = h_tok_off[n_docs] - h_tok_off[0];
+    if (n_ids == 0) {  // no ids: empty rows
+        for (uint32_t i = 0; i <= n_docs; ++i) h_row_off[i] = 0;
+        if (h_unk)
+            for (uint32_t i = 0; i < n_docs; ++i) h_unk[i] = 0;
+        return;
+    }
+    if (!d_ids) raise(MRG_EINVAL, "null ids");
+    // the large documents in slices: maximal runs of at most `budget` ids together, a longer document alone
+    uint64_t budget = 1ull << 25;
+    if (const char *e = getenv("MRG_TEST_TERMS_SLICE_IDS")) budget = std::max<long long>(1, atoll(e));
+    struct Slice {
+        uint32_t first, nd;  // list[2][first, first + nd)
+        uint64_t m, soff_at; // ids; its nd + 1 offsets in `soff`
+    };
+    std::vector<Slice> slices;
+    std::vector<uint64_t> soff;
+    for (uint32_t x = 0; x < list[2].size(); ++x) {
+        const uint64_t T = h_tok_off[list[2][x] + 1] - h_tok_off[list[2][x]];
+        if (slices.empty() || slices.back().m + T > budget) {
+            if (!slices.empty()) soff.push_back(slices.back().m);
+            slices.push_back(Slice{x, 0, 0, soff.size()});
+        }
+        soff.push_back(slices.back().m);
+        slices.back().m += T;
+        slices.back().nd += 1;
+    }
+    if (!slices.empty()) soff.push_back(slices.back().m);
+    for (const Slice &S : slices)
+        if (S.m > 0xFFFFFFFFull) raise(MRG_EINVAL, "MRG_TEST_TERMS_SLICE_IDS: a slice of %llu ids", (unsigned long long)S.m);
+
+    Pool &p = c->pool;
+    hipStream_t s = c->stream;
+    Scratch sc(p);
+    ev_make(c, c->terms_ev);
+    const uint64_t nl[3] = {list[0].size(), list[1].size(), list[2].size()};
+    TermsPlan P{};
+    P.in = d_ids;
+    P.n_words = v->n;
+    uint64_t *d_off = sc.get<uint64_t>((uint64_t)n_docs + 1);
+    P.tok_off = d_off;
+    P.len = sc.get<uint64_t>((uint64_t)n_docs + 1);
+    P.unk = sc.get<uint64_t>(n_docs);
+    uint32_t *d_list = sc.get<uint32_t>(nl[0] + nl[1] + nl[2]);
+    const uint32_t *d_lp[3] = {d_list, d_list + nl[0], d_list + nl[0] + nl[1]};
+    uint64_t *d_soff = sc.get<uint64_t>(soff.size());
+    uint64_t *stmp = sc.get<uint64_t>(mrg_scan_tmp_elems((uint64_t)n_docs + 1));
+    P.err = sc.get<unsigned long long>(1);
+    uint64_t scratch = 8 * (3 * (uint64_t)n_docs + 2) + 4 * (nl[0] + nl[1] + nl[2]) + 8 * soff.size() +
+                       8 * mrg_scan_tmp_elems((uint64_t)n_docs + 1) + 8, slice_max = 0;
+    for (const Slice &S : slices)
+        slice_max = std::max(slice_max, 16 * (S.m + 1) + mrg_sort_u64_keys_tmp_bytes(S.m) + 4 * mrg_scan_tmp_elems(S.m + 1));
+    c->terms_info[0] = n_ids;
+    for (int k = 0; k < 3; ++k) c->terms_info[3 + k] = nl[k];
+    c->terms_info[6] = slices.size();
+    c->terms_info[7] = scratch + slice_max;
+    HIPCHK(hipMemcpyAsync(d_off, h_tok_off, 8 * ((uint64_t)n_docs + 1), hipMemcpyHostToDevice, s));
+    for (int k = 0; k < 3; ++k)
+        if (nl[k]) HIPCHK(hipMemcpyAsync((void *)d_lp[k], list[k].data(), 4 * nl[k], hipMemcpyHostToDevice, s));
+    if (!soff.empty()) HIPCHK(hipMemcpyAsync(d_soff, soff.data(), 8 * soff.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(P.len, 0, 8 * ((uint64_t)n_docs + 1), s));
+    HIPCHK(hipMemsetAsync(P.unk, 0, 8 * (uint64_t)n_docs, s));
+    HIPCHK(hipMemsetAsync(P.err, 0xFF, 8, s));
+
+    // One slice, sorted and run-flagged: K = the sorted keys, E = the scanned run starts, pos = room for
+    // the run positions (E and pos lie in the key buffer the sort left free).
+    struct Sorted {
+        TermsSlice sl;
+        const uint64_t *K;
+        uint32_t *E, *pos;
+    };
+    auto nbytes = [](uint64_t x) {
+        uint32_t b = 0;
+        for (; x; x >>= 8) ++b;
+        return b;
+    };
+    auto sort_slice = [&](const Slice &S, Scratch &ss) {
+        Sorted r{};
+        r.sl = TermsSlice{d_lp[2] + S.first, d_soff + S.soff_at, S.nd, S.m};
+        uint64_t *a = ss.get<uint64_t>(S.m + 1), *b = ss.get<uint64_t>(S.m + 1);
+        void *sort_tmp = ss.get<uint8_t>(mrg_sort_u64_keys_tmp_bytes(S.m));
+        uint32_t *scan_tmp = ss.get<uint32_t>(mrg_scan_tmp_elems(S.m + 1));
+        mrg_terms_launch_keys(P, r.sl, a, s);
+        // the key bytes that can differ: those of an id <= n_words, and of a rank < nd
+        const uint32_t mask = ((1u << nbytes(v->n)) - 1u) | (((1u << nbytes((uint64_t)S.nd - 1u)) - 1u) << 4);
+        uint64_t *K = mrg_radix_sort_u64_keys(a, b, S.m, mask, sort_tmp, s, nullptr);
+        r.K = K;
+        r.E = (uint32_t *)(K == a ? b : a);
+        r.pos = r.E + S.m + 1;
+        mrg_terms_launch_flags(K, S.m, v->n, r.E, s);
+        mrg_scan_u32(r.E, r.E, S.m + 1, scan_tmp, s);
+        HIPCHK(hipGetLastError());
+        return r;
+    };
+
+    // ---- count: row lengths and UNKs of every document, then the row offsets
+    ev_rec(c, c->terms_ev, 0);
+    mrg_terms_launch_lds(P, d_lp[0], (uint32_t)nl[0], false, false, s);
+    mrg_terms_launch_lds(P, d_lp[1], (uint32_t)nl[1], true, false, s);
+    ev_rec(c, c->terms_ev, 1);
+    Scratch kept(p);  // a single slice stays sorted for the emit pass
+    Sorted one{};
+    for (const Slice &S : slices) {
+        Scratch ss(p);
+        const Sorted r = sort_slice(S, ss);
+        mrg_terms_launch_rows(P, r.sl, r.K, r.E, s);
+        if (slices.size() == 1 && d_terms) {
+            one = r;
+            kept = std::move(ss);
+        }
+    }
+    mrg_scan_u64(P.len, P.len, (uint64_t)n_docs + 1, stmp, s);
+    ev_rec(c, c->terms_ev, 2);
+    HIPCHK(hipGetLastError());
+    unsigned long long herr = 0;
+    std::vector<uint64_t> hu(n_docs);
+    HIPCHK(hipMemcpyAsync(h_row_off, P.len, 8 * ((uint64_t)n_docs + 1), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(hu.data(), P.unk, 8 * (uint64_t)n_docs, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&herr, P.err, 8, hipMemcpyDeviceToHost, s));
+    sync(c);  // (also: the pageable offsets and lists have been read)
+    c->terms_ms[0] = ev_ms(c, c->terms_ev, 0, 1);
+    c->terms_ms[1] = ev_ms(c, c->terms_ev, 1, 2);
+    if (herr != ~0ull)
+        raise(MRG_EINVAL, "mrg_vocab_term_counts: the id at index %llu is not in the vocabulary (%llu words)", herr,
+              (unsigned long long)v->n);
+    uint64_t n_unk = 0;
+    for (uint32_t i = 0; i < n_docs; ++i) n_unk += hu[i];
+    if (h_unk) memcpy(h_unk, hu.data(), 8 * (uint64_t)n_docs);
+    const uint64_t total = h_row_off[n_docs];
+    c->terms_info[1] = total;
+    c->terms_info[2] = n_unk;
+    if (!d_terms) return;
+    if (cap < total) raise(MRG_EINVAL, "destination too small (%llu entries < %llu row entries)", (unsigned long long)cap,
+                           (unsigned long long)total);
+    // ---- emit
+    P.terms = d_terms;
+    P.counts = d_counts;
+    ev_rec(c, c->terms_ev, 3);
+    mrg_terms_launch_lds(P, d_lp[0], (uint32_t)nl[0], false, true, s);
+    mrg_terms_launch_lds(P, d_lp[1], (uint32_t)nl[1], true, true, s);
+    ev_rec(c, c->terms_ev, 4);
+    for (const Slice &S : slices) {
+        Scratch ss(p);
+        const Sorted r = slices.size() == 1 ? one : sort_slice(S, ss);
+        mrg_terms_launch_write(P, r.sl, r.K, r.E, r.pos, s);
+    }
+    ev_rec(c, c->terms_ev, 5);
+    HIPCHK(hipGetLastError());
+    sync(c);
+    c->terms_ms[2] = ev_ms(c, c->terms_ev, 3, 4);
+    c->terms_ms[3] = ev_ms(c, c->terms_ev, 4, 5);
+}
+
 void export_sizes(mrg_ctx *c, uint32_t n_owners, uint64_t *h_rec, uint64_t *h_heap) {
     need_job(c);
     if (!c->mapped) raise(MRG_EINVAL, "export before map");
@@ -3283,6 +3471,8 @@ int mrg_close(mrg_ctx *c) {
             if (e) (void)hipEventDestroy(e);
         for (auto &e : c->dec_ev)
             if (e) (void)hipEventDestroy(e);
+        for (auto &e : c->terms_ev)
+            if (e) (void)hipEventDestroy(e);
         (void)hipFree(c->d_cnt);
         (void)hipHostFree(c->h_cnt);
         if (c->h_stage) (void)hipHostFree(c->h_stage);
@@ -3491,6 +3681,24 @@ int mrg_vocab_from_text(mrg_ctx *c, const uint8_t *h_text, uint64_t bytes, uint3
 int mrg_vocab_decode(mrg_ctx *c, const mrg_vocab *v, const uint32_t *d_ids, const uint64_t *h_tok_off, uint32_t n_docs,
                      const uint8_t *h_unk, uint32_t unk_len, uint8_t *d_out, uint64_t cap, uint64_t *h_out_off) {
     return guard([&] { vocab_decode(c, v, d_ids, h_tok_off, n_docs, h_unk, unk_len, d_out, cap, h_out_off); });
+}
+
+int mrg_vocab_term_counts(mrg_ctx *c, const mrg_vocab *v, const uint32_t *d_ids, const uint64_t *h_tok_off,
+                          uint32_t n_docs, uint32_t *d_terms, uint32_t *d_counts, uint64_t cap, uint64_t *h_row_off,
+                          uint64_t *h_unk) {
+    return guard([&] { vocab_term_counts(c, v, d_ids, h_tok_off, n_docs, d_terms, d_counts, cap, h_row_off, h_unk); });
+}
+
+// Diagnostics of the last mrg_vocab_term_counts (not in include/mrgpu.h; tools/time_terms.py): h_info[0..8) =
+// ids, row entries, UNK ids, documents of the wave, workgroup and large path, large-path slices, scratch
+// bytes; h_ms[0..4) = the LDS paths' count pass, the large path's count pass with the row scan, the LDS
+// paths' emit pass, the large path's emit pass (HIP events, with mrg_set_timing).
+int mrg_terms_info(mrg_ctx *c, uint64_t *h_info, double *h_ms) {
+    return guard([&] {
+        if (!c) raise(MRG_EINVAL, "null context");
+        if (h_info) memcpy(h_info, c->terms_info, sizeof c->terms_info);
+        if (h_ms) memcpy(h_ms, c->terms_ms, sizeof c->terms_ms);
+    });
 }
 
 // Diagnostics of the last mrg_vocab_decode (not in include/mrgpu.h; tools/time_decode.py): h_info[0..4) =

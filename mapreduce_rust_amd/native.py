@@ -21,6 +21,10 @@ ID_UNK = 0xFFFFFFFF  # MRG_ID_UNK: mrg_vocab_encode's id of a word that is not i
 OK, EINVAL, EUTF8, EHIP, ENOMEM, EIO, ECOMM = 0, -1, -2, -3, -4, -5, -6
 _CODES = {EINVAL: "EINVAL", EUTF8: "EUTF8", EHIP: "EHIP", ENOMEM: "ENOMEM", EIO: "EIO", ECOMM: "ECOMM"}
 COMM_ID_BYTES = 128
+# term_counts: the longest document (in ids) sorted by one wave / by one workgroup (MRG_TERMS_WAVE_MAX,
+# MRG_TERMS_WG_MAX of csrc/mrg_device.h); longer ones take the radix-sort path
+TERMS_WAVE_MAX = 256
+TERMS_WG_MAX = 4096
 
 
 def debug_hash_bits(n):
@@ -117,6 +121,7 @@ _SIGS = {
     "mrg_vocab_encode": (C.c_int, [_vp, _vp, _vp, _u64p, C.c_uint32, _vp, C.c_uint64, _u64p]),
     "mrg_vocab_from_text": (C.c_int, [_vp, C.c_char_p, C.c_uint64, C.c_uint32, C.POINTER(_vp)]),
     "mrg_vocab_decode": (C.c_int, [_vp, _vp, _vp, _u64p, C.c_uint32, C.c_char_p, C.c_uint32, _vp, C.c_uint64, _u64p]),
+    "mrg_vocab_term_counts": (C.c_int, [_vp, _vp, _vp, _u64p, C.c_uint32, _vp, _vp, C.c_uint64, _u64p, _u64p]),
     "mrg_map": (C.c_int, [_vp, C.c_int, C.c_char_p, C.c_size_t, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32,
                           C.POINTER(_vp)]),
     "mrg_parts_get": (C.c_int, [_vp, C.c_uint32, C.POINTER(_vp), _u64p, C.POINTER(_vp), _u64p]),
@@ -469,6 +474,32 @@ class Context:
         _check(f(self.h, info, ms))
         return {"ids": info[0], "output_bytes": info[1], "chunks": info[2], "scratch_bytes": info[3],
                 "ms_count": ms[0], "ms_offsets": ms[1], "ms_emit": ms[2], "ms_from_text": ms[3]}
+
+    def term_counts(self, vocab, ids_ptr, tok_off, terms_ptr=None, counts_ptr=None, cap=0):
+        """mrg_vocab_term_counts: per-document term counts of the ids of every document (layout of decode's
+        input) in CSR form: row i = the distinct ids of document i other than ID_UNK, ascending, in the device
+        buffer terms_ptr, and their occurrences in counts_ptr (cap uint32 each; both None: sizes only).
+        Returns (row_off, unk): row i is [row_off[i], row_off[i + 1]) of both buffers, unk[i] the ID_UNK of
+        document i."""
+        if len(tok_off) < 1:
+            raise ValueError("tok_off needs n_docs + 1 entries (at least [0])")
+        n = len(tok_off) - 1
+        off, unk = (C.c_uint64 * (n + 1))(), (C.c_uint64 * max(n, 1))()
+        _check(load().mrg_vocab_term_counts(self.h, vocab.h, ids_ptr, _u64arr(tok_off), n, terms_ptr, counts_ptr, cap,
+                                            off, unk))
+        return list(off), list(unk)[:n]
+
+    def terms_info(self):
+        """Diagnostics of the last term_counts(): ids, row entries, ID_UNK ids, documents taken by the wave,
+        workgroup and large path, large-path slices, scratch bytes; HIP-event ms per phase (with set_timing)."""
+        f = load().mrg_terms_info
+        f.restype = C.c_int
+        f.argtypes = [_vp, _u64p, C.POINTER(C.c_double)]
+        info, ms = (C.c_uint64 * 8)(), (C.c_double * 4)()
+        _check(f(self.h, info, ms))
+        return {"ids": info[0], "entries": info[1], "unk": info[2], "wave_docs": info[3], "wg_docs": info[4],
+                "large_docs": info[5], "slices": info[6], "scratch_bytes": info[7], "ms_count_lds": ms[0],
+                "ms_count_large": ms[1], "ms_emit_lds": ms[2], "ms_emit_large": ms[3]}
 
     def encode_info(self):
         """Diagnostics of the last encode(): tokens, UNK and long tokens, non-ASCII 1 KiB chunks, table
