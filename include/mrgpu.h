@@ -121,7 +121,8 @@ typedef struct {
  * (6, additive): mrg_job_vocab, mrg_vocab_size, mrg_vocab_copy_text, mrg_vocab_free, mrg_vocab_encode,
  * MRG_ID_UNK
  * (6, additive): mrg_vocab_from_text, mrg_vocab_decode
- * (6, additive): mrg_vocab_term_counts */
+ * (6, additive): mrg_vocab_term_counts
+ * (6, additive): mrg_vocab_postings */
 #define MRG_ABI_VERSION 6
 
 const char *mrg_last_error(void);
@@ -307,6 +308,39 @@ int mrg_vocab_decode(mrg_ctx *ctx, const mrg_vocab *v, const uint32_t *d_ids, co
 int mrg_vocab_term_counts(mrg_ctx *ctx, const mrg_vocab *v, const uint32_t *d_ids, const uint64_t *h_tok_off,
                           uint32_t n_docs, uint32_t *d_terms, uint32_t *d_counts, uint64_t cap,
                           uint64_t *h_row_off, uint64_t *h_unk);
+/* Term counts -> the inverted index over ids: the transpose (CSC form) of the document-term matrix.  The
+ * input is a CSR in the layout mrg_vocab_term_counts writes: row i is d_terms[h_row_off[i] .. h_row_off[i+1])
+ * with d_counts at the same positions (device memory, 4-byte aligned; h_row_off: n_docs + 1 non-decreasing
+ * entries).  h_row_off[0] may be greater than 0, so rows [a, b) of a bigger CSR are indexed by passing
+ * h_row_off + a, n_docs = b - a and doc_base = a: the document of row i is doc_base + i.  E =
+ * h_row_off[n_docs] - h_row_off[0] is the number of entries; only those entries are read.
+ * d_post_off (device memory, 8-byte aligned) receives the vocabulary's words + 1 offsets, d_post_off[0] = 0
+ * and d_post_off[words] = E.  The postings of word w are d_docs[d_post_off[w] .. d_post_off[w+1]) with the
+ * term frequencies in d_tf at the same positions; the document frequency of w is d_post_off[w+1] -
+ * d_post_off[w].  The call is a stable transpose: the postings of a word stand in the input order of its
+ * entries, so its documents ascend; a term that stands twice in a row gives two postings of that document,
+ * in entry order; nothing is required of the order inside a row; a count is copied as it is, 0 included.
+ * The output is fully determined by the input: no order depends on scheduling, two calls give identical
+ * bytes.
+ * d_docs = NULL and d_tf = NULL: document frequencies only -- only d_post_off is written, d_counts is not
+ * read and may be NULL.  d_tf = NULL: documents only, d_counts is not read.  d_tf without d_docs, or d_tf
+ * without d_counts: MRG_EINVAL.  h_entries may be NULL; otherwise it receives E.
+ * Checked before any device work, MRG_EINVAL with every output untouched: a NULL context, a vocabulary of
+ * another device, offsets that are not non-decreasing, doc_base + n_docs > 2^32, E >= 2^32, d_post_off =
+ * NULL, the NULL combinations above, and d_docs != NULL with cap (entries of d_docs and of d_tf) < E
+ * ("too small").  Checked on the device: a term >= the vocabulary's words (MRG_ID_UNK included, which never
+ * stands in a row) is MRG_EINVAL, mrg_last_error names the smallest index in d_terms of such a term
+ * ("index N"), the outputs are then unspecified.  After every error the context and the vocabulary stay
+ * usable.  An empty vocabulary is valid: E must then be 0 and d_post_off gets its one 0.  n_docs = 0 or
+ * E = 0: all-zero offsets, MRG_OK.
+ * The call needs no job and touches no job state (it is legal between mrg_job_map_add batches).  It runs
+ * on the context's stream with scratch from the context's pool, all returned before the call ends, on
+ * error exits too; on return the outputs are complete.  Scratch: nothing per word beyond the scan's 8
+ * bytes per 2048 words (the frequencies are counted in d_post_off itself); for the postings 24.5 bytes
+ * per entry (two 12-byte records and the sort's tile counts) and 8 bytes per row. */
+int mrg_vocab_postings(mrg_ctx *ctx, const mrg_vocab *v, const uint32_t *d_terms, const uint32_t *d_counts,
+                       const uint64_t *h_row_off, uint32_t n_docs, uint32_t doc_base, uint64_t *d_post_off,
+                       uint32_t *d_docs, uint32_t *d_tf, uint64_t cap, uint64_t *h_entries);
 
 /* ---- multi-GPU: one rank per GPU, the shuffle as an RCCL all-to-all over xGMI ----
  * The reference moves map output to the reduce workers through mr-{m}-{r}.txt files in a shared

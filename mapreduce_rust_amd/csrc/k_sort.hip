@@ -129,6 +129,11 @@ struct K64Traits {  // bare u64 keys (mrg_radix_sort_u64_keys)
     static constexpr int NPASS = 8;
     __device__ static __forceinline__ uint32_t digit(const R &r, int q) { return (uint32_t)(r >> (8 * q)) & 0xFFu; }
 };
+struct PostTraits {  // (term, doc, tf) by the term's bytes (mrg_radix_sort_post)
+    using R = PostRec;
+    static constexpr int NPASS = 4;
+    __device__ static __forceinline__ uint32_t digit(const R &r, int q) { return (r.term >> (8 * q)) & 0xFFu; }
+};
 
 // all-pass histograms in one read: hist[q * 256 + d], for the passes in qmask only.  A digit that
 // is the same on every active lane (constant bytes: zero padding of short keys, the partition's
@@ -559,4 +564,19 @@ uint64_t *mrg_radix_sort_u64_keys(uint64_t *keys, uint64_t *alt, uint64_t n, uin
     bool want[8];
     for (int q = 0; q < 8; ++q) want[q] = (byte_mask >> q) & 1u;
     return radix_sort_t<K64Traits>(keys, alt, n, want, tmp, s, passes_run);
+}
+
+uint64_t mrg_sort_post_tmp_bytes(uint64_t n) {
+    const uint64_t ntiles = (n + TILE - 1) / TILE;
+    return sizeof(unsigned long long) * PostTraits::NPASS * 256 + sizeof(uint32_t) * (256 * ntiles + scan_tmp(256 * ntiles)) +
+           256;
+}
+
+// PostRecs by term, ascending and stable, between recs and alt (n each): only the byte passes of the term
+// in byte_mask run (the other bytes must be equal in all records).  Returns the buffer with the result.
+PostRec *mrg_radix_sort_post(PostRec *recs, PostRec *alt, uint64_t n, uint32_t byte_mask, void *tmp, hipStream_t s,
+                             int *passes_run) {
+    bool want[PostTraits::NPASS];
+    for (int q = 0; q < PostTraits::NPASS; ++q) want[q] = (byte_mask >> q) & 1u;
+    return radix_sort_t<PostTraits>(recs, alt, n, want, tmp, s, passes_run);
 }

@@ -327,6 +327,17 @@ void mrg_radix_sort_u64(uint64_t *keys, uint32_t *vals, uint64_t *kv_tmp, uint64
 uint64_t mrg_sort_u64_keys_tmp_bytes(uint64_t n);
 uint64_t *mrg_radix_sort_u64_keys(uint64_t *keys, uint64_t *alt, uint64_t n, uint32_t byte_mask, void *tmp,
                                   hipStream_t s, int *passes_run);
+// One entry of the document-term matrix on its way to the inverted index (k_postings.hip).
+struct PostRec {  // 12 bytes
+    uint32_t term, doc, tf;
+};
+// Stable sort of PostRecs by term ascending, between recs and alt (n each); only the byte passes in
+// byte_mask run (bit q = term bits [8 q, 8 q + 8); every other byte of the term must be the same in all
+// records).  n < 2^32.  Returns the buffer (recs or alt) with the result; tmp holds
+// mrg_sort_post_tmp_bytes(n) bytes.
+uint64_t mrg_sort_post_tmp_bytes(uint64_t n);
+PostRec *mrg_radix_sort_post(PostRec *recs, PostRec *alt, uint64_t n, uint32_t byte_mask, void *tmp, hipStream_t s,
+                             int *passes_run);
 
 // ---- k_format.hip
 struct FormatArgs {
@@ -638,6 +649,25 @@ void mrg_terms_launch_rows(const TermsPlan &p, const TermsSlice &sl, const uint6
 // pos[E[i]] = i for every run start, then the rows from (keys, E, pos); p.len holds the row offsets
 void mrg_terms_launch_write(const TermsPlan &p, const TermsSlice &sl, const uint64_t *keys, const uint32_t *E,
                             uint32_t *pos, hipStream_t s);
+
+// ---- k_postings.hip: the inverted index over ids
+// One mrg_vocab_postings call.  Positions are indices into `terms`; the entries are [lo, hi).
+struct PostPlan {
+    const uint32_t *terms, *counts;  // the CSR (counts may be null: tf = 0)
+    const uint64_t *row_off;         // [n_docs + 1] device copy of the row offsets (pack only)
+    uint32_t n_docs, doc_base;
+    uint64_t lo, hi;                 // row_off[0], row_off[n_docs]
+    uint64_t n_words;                // terms >= n_words are reported in stat[0]
+    unsigned long long *df;          // [n_words + 1] zeroed: document frequencies, then (scanned in place) offsets
+    // [4]: all ones, then the smallest index of a term that is not in the vocabulary (atomicMin); zero, then
+    // the entries counted in LDS; those counted with global atomics; the largest document frequency
+    unsigned long long *stat;
+};
+void mrg_post_launch_count(const PostPlan &p, hipStream_t s);  // fills df and stat[0..3)
+void mrg_post_launch_max(const PostPlan &p, hipStream_t s);    // stat[3], before df is scanned
+// out[i] = (term, doc_base + row, count) of entry lo + i; needs row_off
+void mrg_post_launch_pack(const PostPlan &p, PostRec *out, hipStream_t s);
+void mrg_post_launch_unpack(const PostRec *in, uint64_t n, uint32_t *docs, uint32_t *tf, hipStream_t s);  // tf may be null
 
 // ---- k_gen.hip
 int mrg_gen_zipf_impl(uint8_t *dst, uint64_t n, uint64_t seed, uint64_t file_index, uint32_t vocab, double s, uint32_t style,

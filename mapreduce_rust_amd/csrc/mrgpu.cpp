@@ -454,6 +454,12 @@ struct mrg_ctx {
     uint64_t terms_info[8] = {};
     double terms_ms[4] = {};
     hipEvent_t terms_ev[6] = {};    // created on first use
+    // last mrg_vocab_postings (mrg_postings_info): entries, words, the largest document frequency, radix
+    // passes run, entries counted in LDS / with global atomics, scratch bytes; ms of the count, the scan
+    // (with the largest df), the pack, the sort and the unpack (with mrg_set_timing)
+    uint64_t post_info[8] = {};
+    double post_ms[5] = {};
+    hipEvent_t post_ev[6] = {};     // created on first use
 };
 
 // A vocabulary (mrg_job_vocab, mrg_vocab_from_text): one device allocation of its own -- the "word count\n"
@@ -565,7 +571,7 @@ void read_counters(mrg_ctx *c) {
 }
 
 // Timing events (mrg_set_timing) of one of the context's event arrays: c->ev (made by mrg_open), or
-// c->enc_ev / c->dec_ev / c->terms_ev, which ev_make creates on first use.
+// c->enc_ev / c->dec_ev / c->terms_ev / c->post_ev, which ev_make creates on first use.
 template <size_t N>
 void ev_make(mrg_ctx *c, hipEvent_t (&ev)[N]) {
     if (!c->timing) return;
@@ -2948,6 +2954,111 @@ void vocab_term_counts(mrg_ctx *c, const mrg_vocab *v, const uint32_t *d_ids, co
     c->terms_ms[3] = ev_ms(c, c->terms_ev, 4, 5);
 }
 
+// The CSR of mrg_vocab_term_counts -> the inverted index over ids (k_postings.hip):
+// one pass over the terms checks them and counts the document frequencies into d_post_off, a scan turns
+// them into the offsets; then (term, doc, tf) records are packed, sorted by the term's bytes with the
+// stable LSD radix sort and unpacked.  Touches no job state; scratch comes from the pool and goes back on
+// every exit.
+void vocab_postings(mrg_ctx *c, const mrg_vocab *v, const uint32_t *d_terms, const uint32_t *d_counts,
+                    const uint64_t *h_row_off, uint32_t n_docs, uint32_t doc_base, uint64_t *d_post_off, uint32_t *d_docs,
+                    uint32_t *d_tf, uint64_t cap, uint64_t *h_entries) {
+    if (!c) raise(MRG_EINVAL, "null context");
+    if (!v) raise(MRG_EINVAL, "null vocabulary");
+    if (v->device != c->device) raise(MRG_EINVAL, "the vocabulary lives on device %d, the context on device %d", v->device,
+                                      c->device);
+    if (!h_row_off) raise(MRG_EINVAL, "null offsets (h_row_off needs n_docs + 1 entries)");
+    for (uint32_t i = 0; i < n_docs; ++i)
+        if (h_row_off[i + 1] < h_row_off[i]) raise(MRG_EINVAL, "row offsets must be non-decreasing (row %u)", i);
+    if ((uint64_t)doc_base + n_docs > (1ull << 32))
+        raise(MRG_EINVAL, "doc_base + n_docs = %llu: documents are 32 bits", (unsigned long long)doc_base + n_docs);
+    const uint64_t lo = h_row_off[0], E = h_row_off[n_docs] - lo;
+    if (E > 0xFFFFFFFFull) raise(MRG_EINVAL, "mrg_vocab_postings: %llu entries: at most 4294967295", (unsigned long long)E);
+    if (!d_post_off) raise(MRG_EINVAL, "null d_post_off (it receives the vocabulary's words + 1 offsets)");
+    if (d_tf && !d_docs) raise(MRG_EINVAL, "d_tf without d_docs");
+    if (d_tf && !d_counts) raise(MRG_EINVAL, "d_tf without d_counts");
+    if (((uintptr_t)d_terms | (uintptr_t)d_counts | (uintptr_t)d_docs | (uintptr_t)d_tf) & 3u)
+        raise(MRG_EINVAL, "d_terms, d_counts, d_docs and d_tf must be 4-byte aligned");
+    if ((uintptr_t)d_post_off & 7u) raise(MRG_EINVAL, "d_post_off must be 8-byte aligned");
+    if (d_docs && cap < E) raise(MRG_EINVAL, "destination too small (%llu entries < %llu postings)", (unsigned long long)cap,
+                                 (unsigned long long)E);
+    if (E && !d_terms) raise(MRG_EINVAL, "null terms");
+    HIPCHK(hipSetDevice(c->device));
+    memset(c->post_info, 0, sizeof c->post_info);
+    memset(c->post_ms, 0, sizeof c->post_ms);
+    const uint64_t n_words = v->n;
+    c->post_info[0] = E;
+    c->post_info[1] = n_words;
+    hipStream_t s = c->stream;
+    HIPCHK(hipMemsetAsync(d_post_off, 0, 8 * (n_words + 1), s));
+    if (E == 0) {  // no entries: all-zero offsets
+        sync(c);
+        if (h_entries) *h_entries = 0;
+        return;
+    }
+    Pool &p = c->pool;
+    Scratch sc(p);
+    ev_make(c, c->post_ev);
+    PostPlan P{};
+    P.terms = d_terms;
+    P.counts = d_tf ? d_counts : nullptr;
+    P.n_docs = n_docs;
+    P.doc_base = doc_base;
+    P.lo = lo;
+    P.hi = lo + E;
+    P.n_words = n_words;
+    P.df = (unsigned long long *)d_post_off;
+    P.stat = sc.get<unsigned long long>(4);
+    uint64_t *stmp = sc.get<uint64_t>(mrg_scan_tmp_elems(n_words + 1));
+    uint64_t scratch = 32 + 8 * mrg_scan_tmp_elems(n_words + 1);
+    HIPCHK(hipMemsetAsync(P.stat, 0xFF, 8, s));
+    HIPCHK(hipMemsetAsync(P.stat + 1, 0, 24, s));
+    // ---- count and validate, then the offsets
+    ev_rec(c, c->post_ev, 0);
+    mrg_post_launch_count(P, s);
+    ev_rec(c, c->post_ev, 1);
+    mrg_post_launch_max(P, s);
+    mrg_scan_u64(d_post_off, d_post_off, n_words + 1, stmp, s);  // d_post_off[n_words] = E
+    ev_rec(c, c->post_ev, 2);
+    HIPCHK(hipGetLastError());
+    unsigned long long hstat[4] = {};
+    HIPCHK(hipMemcpyAsync(hstat, P.stat, sizeof hstat, hipMemcpyDeviceToHost, s));
+    sync(c);
+    c->post_ms[0] = ev_ms(c, c->post_ev, 0, 1);
+    c->post_ms[1] = ev_ms(c, c->post_ev, 1, 2);
+    c->post_info[6] = scratch;
+    if (hstat[0] != ~0ull)
+        raise(MRG_EINVAL, "mrg_vocab_postings: the term at index %llu is not in the vocabulary (%llu words)", hstat[0],
+              (unsigned long long)n_words);
+    c->post_info[2] = hstat[3];
+    c->post_info[4] = hstat[1];
+    c->post_info[5] = hstat[2];
+    if (h_entries) *h_entries = E;
+    if (!d_docs) return;
+    // ---- pack, stable sort by the term's bytes, unpack
+    uint64_t *d_off = sc.get<uint64_t>((uint64_t)n_docs + 1);
+    PostRec *a = sc.get<PostRec>(E), *b = sc.get<PostRec>(E);
+    void *sort_tmp = sc.get<uint8_t>(mrg_sort_post_tmp_bytes(E));
+    c->post_info[6] = scratch + 8 * ((uint64_t)n_docs + 1) + 2 * sizeof(PostRec) * E + mrg_sort_post_tmp_bytes(E);
+    P.row_off = d_off;
+    HIPCHK(hipMemcpyAsync(d_off, h_row_off, 8 * ((uint64_t)n_docs + 1), hipMemcpyHostToDevice, s));
+    ev_rec(c, c->post_ev, 2);
+    mrg_post_launch_pack(P, a, s);
+    ev_rec(c, c->post_ev, 3);
+    uint32_t nb = 0;  // the bytes that n_words - 1 can set
+    for (uint64_t x = n_words - 1; x; x >>= 8) ++nb;
+    int passes = 0;
+    const PostRec *r = mrg_radix_sort_post(a, b, E, (1u << nb) - 1u, sort_tmp, s, &passes);
+    ev_rec(c, c->post_ev, 4);
+    mrg_post_launch_unpack(r, E, d_docs, d_tf, s);
+    ev_rec(c, c->post_ev, 5);
+    HIPCHK(hipGetLastError());
+    sync(c);  // (also: the pageable offsets have been read)
+    c->post_info[3] = (uint64_t)passes;
+    c->post_ms[2] = ev_ms(c, c->post_ev, 2, 3);
+    c->post_ms[3] = ev_ms(c, c->post_ev, 3, 4);
+    c->post_ms[4] = ev_ms(c, c->post_ev, 4, 5);
+}
+
 void export_sizes(mrg_ctx *c, uint32_t n_owners, uint64_t *h_rec, uint64_t *h_heap) {
     need_job(c);
     if (!c->mapped) raise(MRG_EINVAL, "export before map");
@@ -3473,6 +3584,8 @@ int mrg_close(mrg_ctx *c) {
             if (e) (void)hipEventDestroy(e);
         for (auto &e : c->terms_ev)
             if (e) (void)hipEventDestroy(e);
+        for (auto &e : c->post_ev)
+            if (e) (void)hipEventDestroy(e);
         (void)hipFree(c->d_cnt);
         (void)hipHostFree(c->h_cnt);
         if (c->h_stage) (void)hipHostFree(c->h_stage);
@@ -3698,6 +3811,26 @@ int mrg_terms_info(mrg_ctx *c, uint64_t *h_info, double *h_ms) {
         if (!c) raise(MRG_EINVAL, "null context");
         if (h_info) memcpy(h_info, c->terms_info, sizeof c->terms_info);
         if (h_ms) memcpy(h_ms, c->terms_ms, sizeof c->terms_ms);
+    });
+}
+
+int mrg_vocab_postings(mrg_ctx *c, const mrg_vocab *v, const uint32_t *d_terms, const uint32_t *d_counts,
+                       const uint64_t *h_row_off, uint32_t n_docs, uint32_t doc_base, uint64_t *d_post_off, uint32_t *d_docs,
+                       uint32_t *d_tf, uint64_t cap, uint64_t *h_entries) {
+    return guard([&] {
+        vocab_postings(c, v, d_terms, d_counts, h_row_off, n_docs, doc_base, d_post_off, d_docs, d_tf, cap, h_entries);
+    });
+}
+
+// Diagnostics of the last mrg_vocab_postings (not in include/mrgpu.h; tools/time_postings.py): h_info[0..7) =
+// entries, words, the largest document frequency, radix passes run, entries counted in LDS, entries counted
+// with global atomics, scratch bytes; h_ms[0..5) = count, scan (with the largest df), pack, sort, unpack
+// (HIP events, with mrg_set_timing).
+int mrg_postings_info(mrg_ctx *c, uint64_t *h_info, double *h_ms) {
+    return guard([&] {
+        if (!c) raise(MRG_EINVAL, "null context");
+        if (h_info) memcpy(h_info, c->post_info, sizeof c->post_info);
+        if (h_ms) memcpy(h_ms, c->post_ms, sizeof c->post_ms);
     });
 }
 

@@ -25,6 +25,10 @@ COMM_ID_BYTES = 128
 # MRG_TERMS_WG_MAX of csrc/mrg_device.h); longer ones take the radix-sort path
 TERMS_WAVE_MAX = 256
 TERMS_WG_MAX = 4096
+# postings: terms below POST_LDS_WORDS are counted in LDS, the others with global atomics; one workgroup
+# finds the rows of POST_TILE consecutive entries (MRG_POST_LDS_WORDS, MRG_POST_TILE of csrc/mrg_device.h)
+POST_LDS_WORDS = 8192
+POST_TILE = 2048
 
 
 def debug_hash_bits(n):
@@ -122,6 +126,7 @@ _SIGS = {
     "mrg_vocab_from_text": (C.c_int, [_vp, C.c_char_p, C.c_uint64, C.c_uint32, C.POINTER(_vp)]),
     "mrg_vocab_decode": (C.c_int, [_vp, _vp, _vp, _u64p, C.c_uint32, C.c_char_p, C.c_uint32, _vp, C.c_uint64, _u64p]),
     "mrg_vocab_term_counts": (C.c_int, [_vp, _vp, _vp, _u64p, C.c_uint32, _vp, _vp, C.c_uint64, _u64p, _u64p]),
+    "mrg_vocab_postings": (C.c_int, [_vp, _vp, _vp, _vp, _u64p, C.c_uint32, C.c_uint32, _vp, _vp, _vp, C.c_uint64, _u64p]),
     "mrg_map": (C.c_int, [_vp, C.c_int, C.c_char_p, C.c_size_t, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32,
                           C.POINTER(_vp)]),
     "mrg_parts_get": (C.c_int, [_vp, C.c_uint32, C.POINTER(_vp), _u64p, C.POINTER(_vp), _u64p]),
@@ -500,6 +505,34 @@ class Context:
         return {"ids": info[0], "entries": info[1], "unk": info[2], "wave_docs": info[3], "wg_docs": info[4],
                 "large_docs": info[5], "slices": info[6], "scratch_bytes": info[7], "ms_count_lds": ms[0],
                 "ms_count_large": ms[1], "ms_emit_lds": ms[2], "ms_emit_large": ms[3]}
+
+    def postings(self, vocab, terms_ptr, counts_ptr, row_off, post_off_ptr, docs_ptr=None, tf_ptr=None, cap=0, doc_base=0):
+        """mrg_vocab_postings: the inverted index of a CSR in term_counts' layout (uint32 terms and counts at
+        the device pointers, row i = [row_off[i], row_off[i + 1]), its document doc_base + i): post_off_ptr
+        (uint64, the vocabulary's words + 1) receives the offsets, whose differences are the document
+        frequencies; docs_ptr and tf_ptr (cap uint32 each) the documents of every word, ascending, and the
+        term frequencies.  docs_ptr and tf_ptr None: document frequencies only; tf_ptr None: documents only.
+        Returns the number of entries."""
+        if len(row_off) < 1:
+            raise ValueError("row_off needs n_docs + 1 entries (at least [0])")
+        n = len(row_off) - 1
+        e = C.c_uint64()
+        _check(load().mrg_vocab_postings(self.h, vocab.h, terms_ptr, counts_ptr, _u64arr(row_off), n, doc_base,
+                                         post_off_ptr, docs_ptr, tf_ptr, cap, C.byref(e)))
+        return e.value
+
+    def postings_info(self):
+        """Diagnostics of the last postings(): entries, words, the largest document frequency, radix passes
+        run, entries counted in LDS and with global atomics, scratch bytes; HIP-event ms per phase (with
+        set_timing)."""
+        f = load().mrg_postings_info
+        f.restype = C.c_int
+        f.argtypes = [_vp, _u64p, C.POINTER(C.c_double)]
+        info, ms = (C.c_uint64 * 8)(), (C.c_double * 5)()
+        _check(f(self.h, info, ms))
+        return {"entries": info[0], "words": info[1], "max_df": info[2], "passes": info[3], "lds_entries": info[4],
+                "global_entries": info[5], "scratch_bytes": info[6], "ms_count": ms[0], "ms_scan": ms[1],
+                "ms_pack": ms[2], "ms_sort": ms[3], "ms_unpack": ms[4]}
 
     def encode_info(self):
         """Diagnostics of the last encode(): tokens, UNK and long tokens, non-ASCII 1 KiB chunks, table

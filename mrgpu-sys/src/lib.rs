@@ -136,6 +136,7 @@ extern "C" {
     pub fn mrg_vocab_from_text(ctx: *mut mrg_ctx, h_text: *const u8, bytes: u64, flags: u32, out: *mut *mut mrg_vocab) -> c_int;
     pub fn mrg_vocab_decode(ctx: *mut mrg_ctx, v: *const mrg_vocab, d_ids: *const u32, h_tok_off: *const u64, n_docs: u32, h_unk: *const u8, unk_len: u32, d_out: *mut u8, cap: u64, h_out_off: *mut u64) -> c_int;
     pub fn mrg_vocab_term_counts(ctx: *mut mrg_ctx, v: *const mrg_vocab, d_ids: *const u32, h_tok_off: *const u64, n_docs: u32, d_terms: *mut u32, d_counts: *mut u32, cap: u64, h_row_off: *mut u64, h_unk: *mut u64) -> c_int;
+    pub fn mrg_vocab_postings(ctx: *mut mrg_ctx, v: *const mrg_vocab, d_terms: *const u32, d_counts: *const u32, h_row_off: *const u64, n_docs: u32, doc_base: u32, d_post_off: *mut u64, d_docs: *mut u32, d_tf: *mut u32, cap: u64, h_entries: *mut u64) -> c_int;
 
     pub fn mrg_comm_get_id(id: *mut u8) -> c_int;
     pub fn mrg_comm_init(ctx: *mut mrg_ctx, id: *const u8, n_ranks: c_int, rank: c_int,
