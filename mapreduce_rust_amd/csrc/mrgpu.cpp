@@ -1,4 +1,5 @@
-// mrgpu.cpp -- C ABI (include/mrgpu.h) and host orchestration of libmrgpu.so.
+// mrgpu.cpp -- C ABI (include/mrgpu.h) and host orchestration of libmrgpu.so: the context, the job pipeline, the
+// exchange, mrg_run_job.  The vocabulary calls are mrg_vocab.cpp; what both units share is mrg_host.h.
 //
 // Pipeline of one job, all on one HIP stream of the context:
 //   map     k_map (tokenize + LDS combine)                         wc.rs:6-13, worker.rs:117-131
@@ -7,9 +8,6 @@
 //   [shuffle: export by owner = r % G, exchange by the caller (RCCL all-to-all), import]
 //   reduce  radix sort by (r, key bytes[, doc]) + format lines     worker.rs:162-184, wc.rs:15-17
 // Errors never cross the ABI as exceptions or aborts: every entry point returns a status code.
-#include <stdarg.h>
-#include <stdio.h>
-#include <string.h>
 #include <sys/stat.h>
 
 #include <rccl/rccl.h>
@@ -17,48 +15,26 @@
 #include <fcntl.h>
 #include <unistd.h>
 
-#include <algorithm>
 #include <atomic>
-#include <chrono>
 #include <condition_variable>
 #include <exception>
-#include <map>
 #include <memory>
-#include <mutex>
-#include <string>
 #include <thread>
-#include <unordered_map>
-#include <vector>
 
-#include "mrg_device.h"
-#include "mrg_internal.h"
-#include "mrgpu.h"
+#include "mrg_host.h"
+
+using namespace mrg_host;
 
 static_assert(sizeof(XRec) == MRG_XREC_BYTES, "exchange record layout (include/mrgpu.h)");
 
-namespace {
+thread_local std::string mrg_host::g_err;
 
-thread_local std::string g_err;
-
-struct MrgError {
-    int code;
-    std::string msg;
-};
-
-[[noreturn]] void raise(int code, const char *fmt, ...) {
-    char buf[1024];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    throw MrgError{code, buf};
+DeviceCache &DeviceCache::get() {
+    static DeviceCache *c = new DeviceCache();
+    return *c;
 }
 
-#define HIPCHK(x)                                                                      \
-    do {                                                                               \
-        hipError_t e_ = (x);                                                           \
-        if (e_ != hipSuccess) raise(MRG_EHIP, "%s: %s", #x, hipGetErrorString(e_));    \
-    } while (0)
+namespace {
 
 #define NCCLCHK(x)                                                                     \
     do {                                                                               \
@@ -89,389 +65,7 @@ bool wide_forced_off() {
     return v && *v && atoi(v) == 0;
 }
 
-template <class F>
-int guard(F &&f) {
-    try {
-        f();
-        return MRG_OK;
-    } catch (const MrgError &e) {
-        g_err = e.msg;
-        return e.code;
-    } catch (const std::bad_alloc &) {
-        g_err = "host out of memory";
-        return MRG_ENOMEM;
-    } catch (...) {
-        g_err = "unexpected internal error";
-        return MRG_EINVAL;
-    }
-}
-
-// ---------------------------------------------------------------- caching device allocator
-// Process-wide cache of the device blocks of closed contexts, per device (r06).  A worker process runs
-// one task after another (src/bin/mrworker.rs:43-149); every mrg_run_job opens fresh contexts, and
-// without this each call re-allocated -- and the GPU re-touched -- its multi-GiB workspaces (the first
-// job's map ran 1.2x its steady time).  Capped at MRG_POOL_KEEP_GIB per device (default: half the
-// device's memory; 0 = off); blocks beyond the cap are freed.  Never destroyed: no hipFree may run
-// after the HIP runtime's own teardown at process exit.
-class DeviceCache {
-   public:
-    static DeviceCache &get() {
-        static DeviceCache *c = new DeviceCache();
-        return *c;
-    }
-    // a cached block of `dev` of at least c bytes and at most c + c / 4 (any size >= c when `any`: the
-    // device is full) -- its size in *got -- else null
-    void *take(int dev, size_t c, size_t *got, bool any = false) {
-        std::lock_guard<std::mutex> lk(mu_);
-        auto &f = free_[dev];
-        auto it = f.lower_bound(c);
-        if (it == f.end() || (!any && it->first > c + (c >> 2))) return nullptr;
-        void *p = it->second;
-        *got = it->first;
-        bytes_[dev] -= it->first;
-        f.erase(it);
-        return p;
-    }
-    // a block of a closing context (its work on the device finished); the current device is `dev`
-    void give(int dev, void *p, size_t c) {
-        {
-            std::lock_guard<std::mutex> lk(mu_);
-            if (bytes_[dev] + c <= keep(dev)) {
-                free_[dev].insert({c, p});
-                bytes_[dev] += c;
-                return;
-            }
-        }
-        (void)hipFree(p);
-    }
-    void trim(int dev) {  // the device is full: give the cached blocks back to the driver
-        std::multimap<size_t, void *> f;
-        {
-            std::lock_guard<std::mutex> lk(mu_);
-            f.swap(free_[dev]);
-            bytes_[dev] = 0;
-        }
-        for (auto &kv : f) (void)hipFree(kv.second);
-    }
-
-   private:
-    DeviceCache() {
-        if (const char *v = getenv("MRG_POOL_KEEP_GIB")) keep_env_ = (long long)(atof(v) * (double)((size_t)1 << 30));
-    }
-    // bytes of `dev` (the current device) kept: MRG_POOL_KEEP_GIB, else half the device's memory.  A
-    // block handed back to the driver is wiped before any allocation can reuse it (a fresh context
-    // after one that freed ~100 GiB waited 4.6 s in hipMalloc: profiles/r06/v13), so one C5-sized
-    // job's blocks (67-83 GiB at 13.4 GB of input) are worth keeping
-    size_t keep(int dev) {
-        if (keep_env_ >= 0) return (size_t)keep_env_;
-        auto it = keep_dev_.find(dev);
-        if (it != keep_dev_.end()) return it->second;
-        size_t fr = 0, tot = 0;
-        if (hipMemGetInfo(&fr, &tot) != hipSuccess) {
-            (void)hipGetLastError();
-            tot = (size_t)128 << 30;
-        }
-        return keep_dev_[dev] = tot / 2;
-    }
-    std::mutex mu_;
-    std::map<int, std::multimap<size_t, void *>> free_;
-    std::map<int, size_t> bytes_;
-    std::map<int, size_t> keep_dev_;
-    long long keep_env_ = -1;
-};
-
-class Pool : public DevPool {
-   public:
-    void set_device(int dev) { dev_ = dev; }
-    void *get(size_t bytes) override {
-        const size_t c = cls(bytes ? bytes : 1);
-        // smallest free block of this class or up to two classes above (record counts drift by a few
-        // between jobs over the same input: an exact-class pool would then miss, run out of device
-        // memory and trim everything)
-        auto it = free_.lower_bound(c);
-        if (it != free_.end() && it->first <= c + (c >> 2)) {
-            void *p = it->second;
-            free_.erase(it);
-            return p;
-        }
-        if (dev_ >= 0) {  // a block a closed context of this device left behind
-            size_t got = 0;
-            if (void *q = DeviceCache::get().take(dev_, c, &got)) {
-                size_[q] = got;
-                ++reused_;
-                return q;
-            }
-        }
-        void *p = nullptr;
-        if (debug_) fprintf(stderr, "[mrgpu] pool: allocating %zu bytes\n", c);
-        const auto t0 = std::chrono::steady_clock::now();
-        if (hipMalloc(&p, c) != hipSuccess) {
-            (void)hipGetLastError();
-            // the device is full: a larger cached block first (memory handed back to the driver is
-            // wiped before it can be allocated again: a trim costs seconds)
-            if (dev_ >= 0) {
-                size_t got = 0;
-                if (void *q = DeviceCache::get().take(dev_, c, &got, true)) {
-                    alloc_ms_ += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-                    size_[q] = got;
-                    ++reused_;
-                    return q;
-                }
-            }
-            if (debug_) fprintf(stderr, "[mrgpu] pool: device full, trimming %zu free blocks\n", free_.size());
-            trim();
-            if (hipMalloc(&p, c) != hipSuccess) {
-                (void)hipGetLastError();
-                raise(MRG_ENOMEM, "device allocation of %zu bytes failed", c);
-            }
-        }
-        alloc_ms_ += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        ++allocs_;
-        alloc_bytes_ += c;
-        size_[p] = c;
-        return p;
-    }
-    void put(void *p) override {
-        if (!p) return;
-        auto it = size_.find(p);
-        if (it != size_.end()) free_.insert({it->second, p});
-    }
-    void trim() {
-        (void)hipDeviceSynchronize();
-        for (auto &kv : free_) {
-            (void)hipFree(kv.second);
-            size_.erase(kv.second);
-        }
-        free_.clear();
-        if (dev_ >= 0) DeviceCache::get().trim(dev_);
-    }
-    // blocks handed out and not returned; bytes held by the pool (handed out or cached)
-    uint64_t outstanding() const { return size_.size() - free_.size(); }
-    uint64_t held_bytes() const {
-        uint64_t b = 0;
-        for (auto &kv : size_) b += kv.second;
-        return b;
-    }
-    // device allocations made so far (hipMalloc calls, bytes, host milliseconds inside them): a fresh
-    // context's first job pays them, later jobs reuse the cached blocks
-    void alloc_stats(uint64_t *n, uint64_t *bytes, double *ms) const {
-        if (n) *n = allocs_;
-        if (bytes) *bytes = alloc_bytes_;
-        if (ms) *ms = alloc_ms_;
-    }
-    uint64_t reused() const { return reused_; }  // blocks taken from the process-wide device cache
-    ~Pool() override {  // (the caller has made dev_ current)
-        (void)hipDeviceSynchronize();
-        for (auto &kv : size_) {
-            if (dev_ >= 0) DeviceCache::get().give(dev_, kv.first, kv.second);
-            else (void)hipFree(kv.first);
-        }
-    }
-
-   private:
-    static size_t cls(size_t b) {
-        if (b <= 4096) return (b + 255) & ~(size_t)255;
-        size_t p = 4096;
-        while (p < b) p <<= 1;
-        const size_t step = p >> 3;  // 8 classes per octave: <= 12.5% slack
-        return ((b + step - 1) / step) * step;
-    }
-    std::multimap<size_t, void *> free_;
-    std::unordered_map<void *, size_t> size_;
-    bool debug_ = getenv("MRG_DEBUG") != nullptr;
-    uint64_t allocs_ = 0, alloc_bytes_ = 0, reused_ = 0;
-    int dev_ = -1;
-    double alloc_ms_ = 0.0;
-};
-
-template <class T>
-T *pget(Pool &p, uint64_t n) {
-    return (T *)p.get(sizeof(T) * (n ? n : 1));
-}
-
-// The pool blocks of one scope, returned on every exit from it, an exception included.  A block goes
-// back at the point the host reaches, while kernels that use it may still be queued on the context's
-// stream: every later user of the block runs on that same stream, behind them.  put() returns one block
-// early, so the allocations that follow can reuse it; release() hands one to an owner that outlives
-// the scope (c->keys, c->wide, c->d_out, another Scratch).
-struct Scratch {
-    Pool &p;
-    std::vector<void *> b;
-    explicit Scratch(Pool &pool) : p(pool) {}
-    Scratch(const Scratch &) = delete;
-    Scratch &operator=(const Scratch &) = delete;
-    Scratch(Scratch &&o) : p(o.p), b(std::move(o.b)) { o.b.clear(); }
-    Scratch &operator=(Scratch &&o) {  // (of the same pool)
-        put_all();
-        b = std::move(o.b);
-        o.b.clear();
-        return *this;
-    }
-    template <class T>
-    T *get(uint64_t n) {
-        b.push_back(nullptr);
-        return (T *)(b.back() = pget<T>(p, n));
-    }
-    template <class T>
-    T *adopt(T *q) {
-        if (q) b.push_back((void *)q);
-        return q;
-    }
-    template <class T>
-    T *release(T *q) {
-        auto it = std::find(b.begin(), b.end(), (void *)q);
-        if (it != b.end()) b.erase(it);
-        return q;
-    }
-    template <class T>
-    void put(T *q) {
-        if (q) p.put((void *)release(q));
-    }
-    void put_all() {
-        for (void *q : b) p.put(q);
-        b.clear();
-    }
-    void keep() { b.clear(); }  // every block has found its longer-lived owner
-    ~Scratch() { put_all(); }
-};
-
-struct KeysBuf {
-    KeySet ks{};
-    uint64_t n = 0, cap = 0;
-    uint8_t *heap = nullptr;
-    uint64_t heap_bytes = 0;
-    bool any_long = false;
-    bool sorted = false;  // keys already in (partition, key) order (wide aggregation, no long keys)
-};
-
-// Result of the wide (sample-sort) aggregation, k_wide.hip: distinct keys in output order, per leaf,
-// with gaps between leaves; formatted directly, or made a dense KeySet for the other consumers.
-struct WideRes {
-    bool ready = false;
-    uint32_t B1 = 0, B1r = 0;
-    uint64_t *kout = nullptr, *ocnt = nullptr;
-    uint32_t *nleaf = nullptr, *leaf_nd = nullptr, *leaf_last = nullptr, *leaf_pk = nullptr;
-    uint64_t *leaf_out = nullptr, *leaf_bytes = nullptr;
-    uint64_t distinct = 0;
-    void release(Pool &p) {
-        p.put(kout); p.put(ocnt); p.put(nleaf); p.put(leaf_nd); p.put(leaf_last); p.put(leaf_out); p.put(leaf_bytes);
-        p.put(leaf_pk);
-        *this = WideRes{};
-    }
-};
-
-// The accumulator of mrg_job_map_add (k_acc.hip): the job's keys over all its
-// batches.  Short keys live in a persistent open-addressing table, long keys (rare) beside it as rows
-// of a KeysBuf with their heap; c->keys is then only a view, emitted on demand for the consumers.
-struct Acc {
-    bool on = false;      // the job's keys live here
-    bool dirty = false;   // c->keys does not show them (a fold, or a failed batch, since the last emit)
-    bool seeded = false;  // started from keys the job already held (mrg_job_map / mrg_job_import)
-    AccTable T{};
-    uint64_t n = 0;       // short keys in the table (exact: the fold counts the slots it claims)
-    KeysBuf lng;          // long keys: dense rows (k0, k1 = prefix, cnt, hoff, doc, len, part) + heap
-    uint64_t in_bytes = 0, tokens = 0, long_tokens = 0;  // totals over the batches (mrg_stats)
-    uint32_t batches = 0, rehashes = 0;
-    double ms_fold = 0.0;  // last batch, HIP events (mrg_set_timing): end of the aggregation .. end of the fold
-};
-
 }  // namespace
-
-struct mrg_ctx {
-    int device = 0;
-    hipStream_t own = nullptr, stream = nullptr;
-    Pool pool;
-    unsigned long long *d_cnt = nullptr;  // CNT_N counters
-    unsigned long long *h_cnt = nullptr;  // pinned mirror
-    // pinned staging of the small per-job host tables (document offsets, region bases, map args): one
-    // bump region, reset by job_begin (after its sync), so their copies are plain async DMA
-    uint8_t *h_stage = nullptr;
-    size_t stage_used = 0;
-    // batched small writes (stage_h2d / stage_fill): their device copy of the staging buffer, the ops
-    // not yet issued, and the first staging byte they use
-    uint8_t *d_stage = nullptr;
-    std::vector<StageOp> pend;
-    size_t pend_lo = 0;
-    bool timing = false;
-    hipEvent_t ev[8] = {};
-    int lds_cap = 4096;
-    int map_grid = 0;
-    uint64_t long_hint = 0, ovf_hint = 0;
-    uint64_t lper_hint = 0;  // long-token records per map workgroup region (grown on a rerun)
-    uint32_t agg_nsub = 1;  // bucket-aggregation workgroups per bucket (grown when the tables overflow)
-    std::vector<double> bcap_rate;  // tail records per (bucket, map workgroup) per input byte of the workgroup
-    std::vector<double> bcap16_rate;  // the same for the 16-byte regions (wc keys of 13..16 bytes)
-    uint64_t ocap_hint = 0;         // records per bucket overflow list
-    bool spec_agg = false, spec_c32 = false;  // last wc job took the bucket path (with 32-bit counts)
-    bool wide_hint = false;   // last wc job took the wide aggregation (the next one may take the wide map)
-    bool wc_sized = false;    // a wc job of >= 64 MiB has run on this context (its path is a measured hint)
-    uint64_t wcap_hint = 0;   // wide map: records per (L1 bucket, workgroup) region the last run needed
-    bool w12_off = false;     // wide map: a job overflowed the 16-byte lists of the 12-byte regions
-    // job
-    bool job = false;
-    int app = 0;
-    uint32_t R = 0, flags = 0;
-    const uint8_t *d_in = nullptr;
-    std::vector<uint64_t> doc_off;
-    std::vector<uint32_t> doc_ids;
-    std::vector<std::string> names;
-    KeysBuf keys;
-    WideRes wide;
-    Acc acc;
-    bool keyed = false;   // keys / wide hold the complete result of a map or an import
-    bool mapped = false;
-    uint32_t n_owners = 0;
-    std::vector<uint64_t> exp_rec, exp_heap;
-    uint64_t xrec_vmax = MRG_XREC_VMAX;  // count per short export record (test knob MRG_TEST_XREC_VMAX)
-    uint8_t *d_out = nullptr;
-    uint64_t out_cap = 0, out_bytes = 0;
-    std::vector<uint64_t> part_off;
-    bool reduced = false;
-    uint8_t *d_final = nullptr;     // final.txt (mrg_job_final)
-    uint64_t final_cap = 0, final_bytes = 0;
-    bool finalized = false;
-    uint8_t *d_top = nullptr;       // the K most frequent lines (mrg_job_topk)
-    uint64_t top_cap = 0, top_bytes = 0, top_lines = 0;
-    bool topped = false;
-    uint64_t top_info[8] = {};      // last mrg_job_topk: keys, candidates, select passes, dropped candidates
-    uint64_t top_pass_bytes[MRG_TOPK_DIGITS] = {};  // bytes each of its select passes read (0: pass not run)
-    uint64_t extra_first = 0;       // text reduce: values of empty-key lines, folded into the first group
-    mrg_stats st{};
-    // last mrg_vocab_encode (mrg_encode_info): tokens, UNK, long tokens, non-ASCII chunks, table probes,
-    // input bytes, scratch bytes; ms of the count, offsets (scan + boundaries) and emit passes, and of
-    // the last mrg_job_vocab (with mrg_set_timing)
-    uint64_t enc_info[8] = {};
-    double enc_ms[4] = {};
-    hipEvent_t enc_ev[6] = {};      // created on first use
-    // last mrg_vocab_decode (mrg_decode_info): ids, output bytes, chunks, scratch bytes; ms of the count,
-    // offsets (scan + boundaries) and emit passes, and of the last mrg_vocab_from_text (with mrg_set_timing)
-    uint64_t dec_info[8] = {};
-    double dec_ms[4] = {};
-    hipEvent_t dec_ev[6] = {};      // created on first use
-    // last mrg_vocab_term_counts (mrg_terms_info): ids, row entries, UNK, documents of the wave / workgroup /
-    // large path, large-path slices, scratch bytes; ms of the LDS paths' count, the large path's count and
-    // the row scan, the LDS paths' emit, the large path's emit (with mrg_set_timing)
-    uint64_t terms_info[8] = {};
-    double terms_ms[4] = {};
-    hipEvent_t terms_ev[6] = {};    // created on first use
-    // last mrg_vocab_postings (mrg_postings_info): entries, words, the largest document frequency, radix
-    // passes run, entries counted in LDS / with global atomics, scratch bytes; ms of the count, the scan
-    // (with the largest df), the pack, the sort and the unpack (with mrg_set_timing)
-    uint64_t post_info[8] = {};
-    double post_ms[5] = {};
-    hipEvent_t post_ev[6] = {};     // created on first use
-};
-
-// A vocabulary (mrg_job_vocab, mrg_vocab_from_text): one device allocation of its own -- the "word count\n"
-// lines in id order, the byte offset of every line, the word -> id table over them (k_encode.hip), and
-// the id-indexed word lengths and packed words of the decoder (k_decode.hip).  Read-only once built.
-struct mrg_vocab {
-    int device = 0;
-    uint64_t n = 0, text_bytes = 0;
-    void *block = nullptr;
-    VocTable T{};
-    VocWords W{};
-};
 
 struct mrg_comm {
     ncclComm_t comm = nullptr;
@@ -494,11 +88,6 @@ struct mrg_parts {
 };
 
 namespace {
-
-uint32_t hash_bits(const mrg_ctx *c) { return (c->flags >> 8) & 0xFFu; }
-bool is_idx(const mrg_ctx *c) { return c->app == MRG_APP_INDEXER; }
-
-void sync(mrg_ctx *c) { HIPCHK(hipStreamSynchronize(c->stream)); }
 
 constexpr size_t MRG_STAGE_BYTES = 256u << 10;
 // Host -> device copy of a small table through the pinned staging region (falls back to a pageable
@@ -570,25 +159,6 @@ void read_counters(mrg_ctx *c) {
     sync(c);
 }
 
-// Timing events (mrg_set_timing) of one of the context's event arrays: c->ev (made by mrg_open), or
-// c->enc_ev / c->dec_ev / c->terms_ev / c->post_ev, which ev_make creates on first use.
-template <size_t N>
-void ev_make(mrg_ctx *c, hipEvent_t (&ev)[N]) {
-    if (!c->timing) return;
-    for (auto &e : ev)
-        if (!e) HIPCHK(hipEventCreate(&e));
-}
-void ev_rec(mrg_ctx *c, hipEvent_t *ev, int i) {
-    if (c->timing) HIPCHK(hipEventRecord(ev[i], c->stream));
-}
-double ev_ms(mrg_ctx *c, hipEvent_t *ev, int a, int b) {
-    if (!c->timing) return 0.0;
-    float ms = 0;
-    HIPCHK(hipEventSynchronize(ev[b]));
-    HIPCHK(hipEventElapsedTime(&ms, ev[a], ev[b]));
-    return ms;
-}
-
 // Drops the staged writes (stage_h2d / stage_fill) that are still pending when its scope ends by an
 // exception: their destinations are scratch blocks the same exit returns to the pool, and the next
 // flush_stage -- the next job's, at the latest -- would write them into memory that another call owns
@@ -640,12 +210,6 @@ void keys_reserve(mrg_ctx *c, uint64_t cap) {
     sc.keep();
     c->keys.ks = ks;
     c->keys.cap = cap;
-}
-
-uint64_t pow2_at_least(uint64_t x) {
-    uint64_t p = 1024;
-    while (p < x) p <<= 1;
-    return p;
 }
 
 struct ShortSrc {
@@ -894,12 +458,6 @@ bool bucket_aggregate(mrg_ctx *c, const MapArgs &A, uint32_t nreg, uint32_t regc
     long_aggregate(c, li);
     finish_keys(c, fresh, parted);
     return true;
-}
-
-uint32_t bytes_for(uint64_t maxval) {
-    uint32_t b = 0;
-    while (maxval) { ++b; maxval >>= 8; }
-    return b;
 }
 
 // radix sort by (partition < R, the 16 key bytes of a short key)
@@ -1253,11 +811,6 @@ void wide_aggregate(mrg_ctx *c, const MapArgs &A, uint32_t nreg, uint32_t regcap
     sc.put_all();
     mark();  // 3: L1
     wide_finish(c, fin, li, n, nw, B1, B1r, K1, bstart, spl1, bid, wk0, wk1, wcnt, wpart, dbg, pe, npe, WmapIn{});
-}
-
-void need_job(mrg_ctx *c) {
-    if (!c) raise(MRG_EINVAL, "null context");
-    if (!c->job) raise(MRG_EINVAL, "no job: call mrg_job_begin first");
 }
 
 void job_begin(mrg_ctx *c, int app, uint32_t R, uint32_t flags) {
@@ -2338,7 +1891,9 @@ void job_final(mrg_ctx *c) {
 // Reads the key set only: reduce, final and export afterwards give what they give without it.
 // keep: the ranked records of the lines written (idx = key index in c->keys) become a block of *keep and
 // are returned; null when no line was written (mrg_job_vocab).
-SortRec *job_topk(mrg_ctx *c, uint64_t k, Scratch *keep = nullptr) {
+}  // namespace
+
+SortRec *mrg_host::job_topk(mrg_ctx *c, uint64_t k, Scratch *keep) {
     need_job(c);
     if (is_idx(c)) raise(MRG_EINVAL, "mrg_job_topk: word count only (the indexer has no counts to rank)");
     if (!c->mapped) raise(MRG_EINVAL, "no keys: call mrg_job_map or mrg_job_import first");
@@ -2418,646 +1973,7 @@ SortRec *job_topk(mrg_ctx *c, uint64_t k, Scratch *keep = nullptr) {
     return keep ? keep->adopt(sc.release(top)) : nullptr;
 }
 
-void vocab_destroy(mrg_vocab *v) {
-    if (!v) return;
-    if (v->block) {
-        int cur = -1;
-        (void)hipGetDevice(&cur);
-        (void)hipSetDevice(v->device);
-        (void)hipFree(v->block);
-        if (cur >= 0 && cur != v->device) (void)hipSetDevice(cur);
-    }
-    delete v;
-}
-
-struct VocDel {
-    void operator()(mrg_vocab *v) const { vocab_destroy(v); }
-};
-using VocPtr = std::unique_ptr<mrg_vocab, VocDel>;
-
-// The block of a vocabulary of n words over text_bytes of text, laid out and allocated; nothing in it is
-// written yet except line_off[0] of the empty vocabulary.  Layout: text | line_off | table k0, k1, id |
-// wlen | packed words (the last two are the decoder's: the encoder's part is as it was).
-VocPtr vocab_alloc(mrg_ctx *c, uint64_t n, uint64_t text_bytes, uint32_t hbits) {
-    if (n > 0xFFFFFFFEull) raise(MRG_EINVAL, "vocabulary of %llu words: ids are 32 bits", (unsigned long long)n);
-    VocPtr v(new mrg_vocab());
-    v->device = c->device;
-    v->n = n;
-    v->text_bytes = text_bytes;
-    const uint64_t cap = pow2_at_least(2 * n);
-    auto up = [](uint64_t x) { return (x + 255) & ~255ull; };
-    const uint64_t o_text = 0, o_loff = o_text + up(text_bytes + 16), o_k0 = o_loff + up(8 * (n + 1)),
-                   o_k1 = o_k0 + 8 * cap, o_id = o_k1 + 8 * cap, o_wlen = o_id + 4 * cap, o_pk = o_wlen + up(4 * n),
-                   total = o_pk + up(16 * n);
-    if (hipMalloc(&v->block, total) != hipSuccess) {
-        (void)hipGetLastError();
-        v->block = nullptr;
-        raise(MRG_ENOMEM, "vocabulary: device allocation of %llu bytes failed", (unsigned long long)total);
-    }
-    uint8_t *blk = (uint8_t *)v->block;
-    VocTable &T = v->T;
-    T.k0 = (uint64_t *)(blk + o_k0);
-    T.k1 = (uint64_t *)(blk + o_k1);
-    T.id = (uint32_t *)(blk + o_id);
-    T.cap = cap;
-    T.hash_bits = hbits;
-    T.text = blk + o_text;
-    T.line_off = (const uint64_t *)(blk + o_loff);
-    T.n = n;
-    v->W.wlen = (uint32_t *)(blk + o_wlen);
-    v->W.pk = (uint64_t *)(blk + o_pk);
-    if (!n) HIPCHK(hipMemsetAsync(blk + o_loff, 0, 8, c->stream));
-    return v;
-}
-
-// The table and the packed words over the block's text, line offsets and word lengths (enqueued before);
-// waits for the build.
-void vocab_build(mrg_ctx *c, mrg_vocab *v, Scratch &sc) {
-    hipStream_t s = c->stream;
-    unsigned long long *fail = sc.get<unsigned long long>(1);
-    HIPCHK(hipMemsetAsync(fail, 0, 8, s));
-    mrg_voc_launch_build(v->T, v->W.wlen, fail, s);
-    mrg_voc_launch_words(v->T, v->W, s);
-    HIPCHK(hipGetLastError());
-    unsigned long long hfail = 0;
-    HIPCHK(hipMemcpyAsync(&hfail, fail, 8, hipMemcpyDeviceToHost, s));
-    sync(c);
-    if (hfail) raise(MRG_EHIP, "vocabulary: %llu words found no table slot", hfail);
-}
-
-// The vocabulary of the job's keys: mrg_job_topk's ranked lines, cut at
-// min_count, copied with their line offsets into one allocation of the vocabulary's own, and the
-// word -> id table over that copy.
-mrg_vocab *job_vocab(mrg_ctx *c, uint64_t max_words, uint64_t min_count) {
-    need_job(c);
-    if (is_idx(c)) raise(MRG_EINVAL, "mrg_job_vocab: word count only (the indexer has no counts to rank)");
-    Pool &p = c->pool;
-    hipStream_t s = c->stream;
-    Scratch sc(p);
-    ev_make(c, c->enc_ev);
-    ev_rec(c, c->enc_ev, 4);
-    SortRec *top = job_topk(c, max_words ? max_words : ~0ull, &sc);
-    const uint64_t m = top ? c->top_lines : 0;
-    uint64_t n = 0, text_bytes = 0;
-    uint64_t *loff = nullptr;
-    uint32_t *wlen = nullptr;
-    if (m) {
-        loff = sc.get<uint64_t>(m + 1);
-        wlen = sc.get<uint32_t>(m);
-        uint64_t *stmp = sc.get<uint64_t>(mrg_scan_tmp_elems(m + 1));
-        unsigned long long *nk = sc.get<unsigned long long>(1);
-        HIPCHK(hipMemsetAsync(nk, 0, 8, s));
-        mrg_voc_launch_lines(top, m, c->keys.ks, min_count, loff, wlen, nk, s);
-        mrg_scan_u64(loff, loff, m + 1, stmp, s);
-        HIPCHK(hipMemcpyAsync(&n, nk, 8, hipMemcpyDeviceToHost, s));
-        sync(c);
-        if (n > m) raise(MRG_EHIP, "vocabulary: %llu of %llu lines kept", (unsigned long long)n, (unsigned long long)m);
-        HIPCHK(hipMemcpyAsync(&text_bytes, loff + n, 8, hipMemcpyDeviceToHost, s));
-        sync(c);
-        if (text_bytes > c->top_bytes) raise(MRG_EHIP, "vocabulary: line offsets exceed the ranked text");
-    }
-    VocPtr v = vocab_alloc(c, n, text_bytes, hash_bits(c));
-    uint8_t *blk = (uint8_t *)v->block;
-    if (text_bytes) HIPCHK(hipMemcpyAsync(blk, c->d_top, text_bytes, hipMemcpyDeviceToDevice, s));
-    if (n) HIPCHK(hipMemcpyAsync((void *)v->T.line_off, loff, 8 * (n + 1), hipMemcpyDeviceToDevice, s));
-    if (n) HIPCHK(hipMemcpyAsync(v->W.wlen, wlen, 4 * n, hipMemcpyDeviceToDevice, s));
-    vocab_build(c, v.get(), sc);
-    ev_rec(c, c->enc_ev, 5);
-    sync(c);
-    c->enc_ms[3] = ev_ms(c, c->enc_ev, 4, 5);
-    return v.release();
-}
-
-// Text -> ids (k_encode.hip): boundary bitmap, count pass, scan, per-document offsets, emit pass.
-// Touches no job state; scratch comes from the pool and goes back on every exit.
-void vocab_encode(mrg_ctx *c, const mrg_vocab *v, const uint8_t *d_bytes, const uint64_t *h_doc_off, uint32_t n_docs,
-                  uint32_t *d_ids, uint64_t cap_ids, uint64_t *h_tok_off) {
-    if (!c) raise(MRG_EINVAL, "null context");
-    if (!v) raise(MRG_EINVAL, "null vocabulary");
-    if (!h_doc_off || !h_tok_off) raise(MRG_EINVAL, "null offsets (h_doc_off and h_tok_off need n_docs + 1 entries)");
-    if (v->device != c->device) raise(MRG_EINVAL, "the vocabulary lives on device %d, the context on device %d", v->device,
-                                      c->device);
-    if (n_docs == 0xFFFFFFFFu) raise(MRG_EINVAL, "n_docs out of range");
-    if ((uintptr_t)d_bytes & 15u) raise(MRG_EINVAL, "input buffer must be 16-byte aligned");
-    for (uint32_t i = 0; i < n_docs; ++i)
-        if (h_doc_off[i + 1] < h_doc_off[i]) raise(MRG_EINVAL, "document offsets must be non-decreasing");
-    HIPCHK(hipSetDevice(c->device));
-    memset(c->enc_info, 0, sizeof c->enc_info);
-    c->enc_ms[0] = c->enc_ms[1] = c->enc_ms[2] = 0.0;
-    const uint64_t lo0 = h_doc_off[0], hi0 = h_doc_off[n_docs];
-    if (hi0 == lo0) {  // no bytes: no tokens
-        for (uint32_t i = 0; i <= n_docs; ++i) h_tok_off[i] = 0;
-        return;
-    }
-    if (!d_bytes) raise(MRG_EINVAL, "null input");
-    Pool &p = c->pool;
-    hipStream_t s = c->stream;
-    Scratch sc(p);
-    ev_make(c, c->enc_ev);
-    // positions relative to the 1 KiB boundary at or below the first document
-    const uint64_t shift = lo0 & ~1023ull;
-    std::vector<uint64_t> rel(h_doc_off, h_doc_off + n_docs + 1);
-    for (auto &x : rel) x -= shift;
-    EncPlan P{};
-    P.in = d_bytes + shift;
-    P.lo = lo0 - shift;
-    P.hi = hi0 - shift;
-    P.ntiles = (P.hi + 1023) >> 10;
-    P.n_docs = n_docs;
-    const uint64_t bw = mrg_enc_bitmap_words(P.ntiles);
-    P.bnd = sc.get<uint32_t>(bw);
-    uint64_t *d_off = sc.get<uint64_t>((uint64_t)n_docs + 1);
-    P.doc_off = d_off;
-    P.cnt = sc.get<uint64_t>(P.ntiles + 1);
-    P.tok_off = sc.get<uint64_t>((uint64_t)n_docs + 1);
-    uint64_t *stmp = sc.get<uint64_t>(mrg_scan_tmp_elems(P.ntiles + 1));
-    unsigned long long *small = sc.get<unsigned long long>(9);  // err, info[8]
-    P.err = small;
-    P.info = small + 1;
-    c->enc_info[5] = hi0 - lo0;
-    c->enc_info[6] = 4 * bw + 8 * (P.ntiles + 1) + 16 * ((uint64_t)n_docs + 1) + 8 * mrg_scan_tmp_elems(P.ntiles + 1) + 72;
-    HIPCHK(hipMemcpyAsync(d_off, rel.data(), 8 * ((uint64_t)n_docs + 1), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemsetAsync(P.bnd, 0, 4 * bw, s));
-    HIPCHK(hipMemsetAsync(P.cnt, 0, 8 * (P.ntiles + 1), s));
-    HIPCHK(hipMemsetAsync(P.err, 0xFF, 8, s));
-    HIPCHK(hipMemsetAsync(P.info, 0, 64, s));
-    mrg_enc_launch_bounds(P, s);
-    ev_rec(c, c->enc_ev, 0);
-    mrg_enc_launch_count(P, v->T, s);
-    ev_rec(c, c->enc_ev, 1);
-    mrg_scan_u64(P.cnt, P.cnt, P.ntiles + 1, stmp, s);
-    mrg_enc_launch_offsets(P, v->T, s);
-    ev_rec(c, c->enc_ev, 2);
-    HIPCHK(hipGetLastError());
-    unsigned long long herr = 0;
-    HIPCHK(hipMemcpyAsync(h_tok_off, P.tok_off, 8 * ((uint64_t)n_docs + 1), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(&herr, P.err, 8, hipMemcpyDeviceToHost, s));
-    sync(c);  // (also: the pageable `rel` has been read)
-    c->enc_ms[0] = ev_ms(c, c->enc_ev, 0, 1);
-    c->enc_ms[1] = ev_ms(c, c->enc_ev, 1, 2);
-    if (herr != ~0ull) {
-        uint32_t d = 0;
-        while (d + 1 < n_docs && rel[d + 1] <= herr) ++d;
-        raise(MRG_EUTF8, "stream did not contain valid UTF-8: document %u, byte offset %llu", d,
-              (unsigned long long)(herr - rel[d]));
-    }
-    const uint64_t total = h_tok_off[n_docs];
-    if (d_ids) {
-        if (cap_ids < total) raise(MRG_EINVAL, "destination too small (%llu ids < %llu tokens)", (unsigned long long)cap_ids,
-                                   (unsigned long long)total);
-        P.out = d_ids;
-        P.out_n = total;
-        ev_rec(c, c->enc_ev, 2);
-        if (total) mrg_enc_launch_emit(P, v->T, s);
-        ev_rec(c, c->enc_ev, 3);
-        HIPCHK(hipGetLastError());
-    }
-    unsigned long long hinfo[8] = {};
-    HIPCHK(hipMemcpyAsync(hinfo, P.info, 64, hipMemcpyDeviceToHost, s));
-    sync(c);
-    if (d_ids) c->enc_ms[2] = ev_ms(c, c->enc_ev, 2, 3);
-    for (int i = 0; i < 5; ++i) c->enc_info[i] = hinfo[i];
-    if (!d_ids) c->enc_info[0] = total;
-}
-
-// A vocabulary from its text: the host cuts the lines, the device checks every
-// line's UTF-8, its form and its word's codepoints (k_voc_check), builds the table as mrg_job_vocab does, and looks
-// every word up again to find a word that stands on two lines (k_voc_verify).  No job state is touched.
-mrg_vocab *vocab_from_text(mrg_ctx *c, const uint8_t *h_text, uint64_t bytes, uint32_t flags) {
-    if (!c) raise(MRG_EINVAL, "null context");
-    if (bytes && !h_text) raise(MRG_EINVAL, "mrg_vocab_from_text: null text");
-    if (flags & ~MRG_FLAG_DEBUG_HASH_BITS(0xFFu))
-        raise(MRG_EINVAL, "mrg_vocab_from_text: flags 0x%x: only MRG_FLAG_DEBUG_HASH_BITS is accepted", flags);
-    HIPCHK(hipSetDevice(c->device));
-    std::vector<uint64_t> loff(1, 0);
-    for (const uint8_t *p = h_text, *e = h_text + bytes; p < e;) {
-        const uint8_t *q = (const uint8_t *)memchr(p, '\n', (size_t)(e - p));
-        if (!q) raise(MRG_EINVAL, "mrg_vocab_from_text: line %llu: the text does not end in a newline",
-                      (unsigned long long)(loff.size() - 1));
-        p = q + 1;
-        loff.push_back((uint64_t)(p - h_text));
-        if (loff.size() - 1 > 0xFFFFFFFEull)
-            raise(MRG_EINVAL, "mrg_vocab_from_text: more than %llu lines: ids are 32 bits", 0xFFFFFFFEull);
-    }
-    const uint64_t n = loff.size() - 1;
-    hipStream_t s = c->stream;
-    Scratch sc(c->pool);
-    ev_make(c, c->dec_ev);
-    ev_rec(c, c->dec_ev, 4);
-    VocPtr v = vocab_alloc(c, n, bytes, (flags >> 8) & 0xFFu);
-    if (n) {
-        HIPCHK(hipMemcpyAsync((void *)v->T.text, h_text, bytes, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync((void *)v->T.line_off, loff.data(), 8 * (n + 1), hipMemcpyHostToDevice, s));
-        unsigned long long *err = sc.get<unsigned long long>(2);  // first bad line, first duplicate
-        HIPCHK(hipMemsetAsync(err, 0xFF, 16, s));
-        mrg_voc_launch_check(v->T, v->W.wlen, err, s);
-        HIPCHK(hipGetLastError());
-        unsigned long long herr = 0;
-        HIPCHK(hipMemcpyAsync(&herr, err, 8, hipMemcpyDeviceToHost, s));
-        sync(c);  // (also: the pageable text and offsets have been read)
-        if (herr != ~0ull) {
-            const unsigned long long line = herr >> 2;
-            switch ((uint32_t)(herr & 3u)) {
-                case MRG_VOC_BAD_UTF8:
-                    raise(MRG_EUTF8, "mrg_vocab_from_text: line %llu: not valid UTF-8", line);
-                case MRG_VOC_BAD_CLASS:
-                    raise(MRG_EINVAL, "mrg_vocab_from_text: line %llu: the word holds a codepoint that is not \\w", line);
-                default:
-                    raise(MRG_EINVAL, "mrg_vocab_from_text: line %llu: not `word`, one space, 1 to 20 digits", line);
-            }
-        }
-        vocab_build(c, v.get(), sc);
-        mrg_voc_launch_verify(v->T, v->W.wlen, err + 1, s);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(&herr, err + 1, 8, hipMemcpyDeviceToHost, s));
-        ev_rec(c, c->dec_ev, 5);
-        sync(c);
-        if (herr != ~0ull) raise(MRG_EINVAL, "mrg_vocab_from_text: line %llu: duplicate word", herr);
-    } else {
-        ev_rec(c, c->dec_ev, 5);
-        sync(c);
-    }
-    c->dec_ms[3] = ev_ms(c, c->dec_ev, 4, 5);
-    return v.release();
-}
-
-// Ids -> text (k_decode.hip): boundary bitmap, count pass, scan, per-document offsets, emit pass.
-// Touches no job state; scratch comes from the pool and goes back on every exit.
-void vocab_decode(mrg_ctx *c, const mrg_vocab *v, const uint32_t *d_ids, const uint64_t *h_tok_off, uint32_t n_docs,
-                  const uint8_t *h_unk, uint32_t unk_len, uint8_t *d_out, uint64_t cap, uint64_t *h_out_off) {
-    if (!c) raise(MRG_EINVAL, "null context");
-    if (!v) raise(MRG_EINVAL, "null vocabulary");
-    if (!h_tok_off || !h_out_off) raise(MRG_EINVAL, "null offsets (h_tok_off and h_out_off need n_docs + 1 entries)");
-    if (v->device != c->device) raise(MRG_EINVAL, "the vocabulary lives on device %d, the context on device %d", v->device,
-                                      c->device);
-    if (n_docs == 0xFFFFFFFFu) raise(MRG_EINVAL, "n_docs out of range");
-    if ((uintptr_t)d_ids & 3u) raise(MRG_EINVAL, "the ids must be 4-byte aligned");
-    if (unk_len > 255u) raise(MRG_EINVAL, "unk_len %u: at most 255 bytes", unk_len);
-    if (unk_len && !h_unk) raise(MRG_EINVAL, "null h_unk with unk_len %u", unk_len);
-    for (uint32_t i = 0; i < n_docs; ++i)
-        if (h_tok_off[i + 1] < h_tok_off[i]) raise(MRG_EINVAL, "token offsets must be non-decreasing");
-    HIPCHK(hipSetDevice(c->device));
-    memset(c->dec_info, 0, sizeof c->dec_info);
-    c->dec_ms[0] = c->dec_ms[1] = c->dec_ms[2] = 0.0;
-    const uint64_t lo0 = h_tok_off[0], hi0 = h_tok_off[n_docs];
-    if (hi0 == lo0) {  // no ids: no bytes
-        for (uint32_t i = 0; i <= n_docs; ++i) h_out_off[i] = 0;
-        return;
-    }
-    if (!d_ids) raise(MRG_EINVAL, "null ids");
-    Pool &p = c->pool;
-    hipStream_t s = c->stream;
-    Scratch sc(p);
-    ev_make(c, c->dec_ev);
-    // positions relative to the 16-byte boundary at or below the first id
-    const uint64_t shift = (uint64_t)(((uintptr_t)(d_ids + lo0) & 15u) >> 2);
-    std::vector<uint64_t> rel(h_tok_off, h_tok_off + n_docs + 1);
-    for (auto &x : rel) x = x - lo0 + shift;
-    DecPlan P{};
-    P.in = d_ids + lo0 - shift;
-    P.lo = shift;
-    P.hi = shift + (hi0 - lo0);
-    P.nchunks = (P.hi + MRG_DEC_CHUNK - 1) / MRG_DEC_CHUNK;
-    P.n_docs = n_docs;
-    const uint64_t bw = mrg_dec_bitmap_words(P.nchunks);
-    P.bnd = sc.get<uint32_t>(bw);
-    uint64_t *d_off = sc.get<uint64_t>((uint64_t)n_docs + 1);
-    P.tok_off = d_off;
-    P.cnt = sc.get<uint64_t>(P.nchunks + 1);
-    P.out_off = sc.get<uint64_t>((uint64_t)n_docs + 1);
-    uint64_t *stmp = sc.get<uint64_t>(mrg_scan_tmp_elems(P.nchunks + 1));
-    unsigned long long *small = sc.get<unsigned long long>(1 + 32);  // err, the UNK bytes
-    P.err = small;
-    P.unk_len = unk_len;
-    P.unk = (const uint8_t *)(small + 1);
-    for (uint32_t i = 0; i < unk_len && i < 16u; ++i)
-        (i < 8u ? P.unk_k0 : P.unk_k1) |= (uint64_t)h_unk[i] << (56u - 8u * (i & 7u));
-    c->dec_info[0] = hi0 - lo0;
-    c->dec_info[2] = P.nchunks;
-    c->dec_info[3] = 4 * bw + 8 * (P.nchunks + 1) + 16 * ((uint64_t)n_docs + 1) + 8 * mrg_scan_tmp_elems(P.nchunks + 1) + 264;
-    HIPCHK(hipMemcpyAsync(d_off, rel.data(), 8 * ((uint64_t)n_docs + 1), hipMemcpyHostToDevice, s));
-    if (unk_len) HIPCHK(hipMemcpyAsync(small + 1, h_unk, unk_len, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemsetAsync(P.bnd, 0, 4 * bw, s));
-    HIPCHK(hipMemsetAsync(P.cnt, 0, 8 * (P.nchunks + 1), s));
-    HIPCHK(hipMemsetAsync(P.err, 0xFF, 8, s));
-    mrg_dec_launch_bounds(P, s);
-    ev_rec(c, c->dec_ev, 0);
-    mrg_dec_launch_count(P, v->T, v->W, s);
-    ev_rec(c, c->dec_ev, 1);
-    mrg_scan_u64(P.cnt, P.cnt, P.nchunks + 1, stmp, s);
-    mrg_dec_launch_offsets(P, v->T, v->W, s);
-    ev_rec(c, c->dec_ev, 2);
-    HIPCHK(hipGetLastError());
-    unsigned long long herr = 0;
-    HIPCHK(hipMemcpyAsync(h_out_off, P.out_off, 8 * ((uint64_t)n_docs + 1), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(&herr, P.err, 8, hipMemcpyDeviceToHost, s));
-    sync(c);  // (also: the pageable `rel` and h_unk have been read)
-    c->dec_ms[0] = ev_ms(c, c->dec_ev, 0, 1);
-    c->dec_ms[1] = ev_ms(c, c->dec_ev, 1, 2);
-    if (herr != ~0ull)
-        raise(MRG_EINVAL, "mrg_vocab_decode: the id at index %llu is not in the vocabulary (%llu words%s)",
-              (unsigned long long)(herr - shift + lo0), (unsigned long long)v->n,
-              unk_len ? "" : "; MRG_ID_UNK needs unk_len > 0");
-    const uint64_t total = h_out_off[n_docs];
-    c->dec_info[1] = total;
-    if (!d_out) return;
-    if (cap < total) raise(MRG_EINVAL, "destination too small (%llu bytes < %llu bytes of text)", (unsigned long long)cap,
-                           (unsigned long long)total);
-    P.out = d_out;
-    P.out_n = total;
-    ev_rec(c, c->dec_ev, 2);
-    if (total) mrg_dec_launch_emit(P, v->T, v->W, s);
-    ev_rec(c, c->dec_ev, 3);
-    HIPCHK(hipGetLastError());
-    sync(c);
-    c->dec_ms[2] = ev_ms(c, c->dec_ev, 2, 3);
-}
-
-// Ids -> per-document term counts in CSR form (k_terms.hip): the documents are
-// listed by path on the host; a count pass (LDS sort per document, radix sort per large slice) gives every
-// row's length and UNK count, the scan the row offsets, an emit pass the rows.  Touches no job state;
-// scratch comes from the pool and goes back on every exit.
-void vocab_term_counts(mrg_ctx *c, const mrg_vocab *v, const uint32_t *d_ids, const uint64_t *h_tok_off, uint32_t n_docs,
-                       uint32_t *d_terms, uint32_t *d_counts, uint64_t cap, uint64_t *h_row_off, uint64_t *h_unk) {
-    if (!c) raise(MRG_EINVAL, "null context");
-    if (!v) raise(MRG_EINVAL, "null vocabulary");
-    if (!h_tok_off || !h_row_off) raise(MRG_EINVAL, "null offsets (h_tok_off and h_row_off need n_docs + 1 entries)");
-    if (v->device != c->device) raise(MRG_EINVAL, "the vocabulary lives on device %d, the context on device %d", v->device,
-                                      c->device);
-    if (n_docs == 0xFFFFFFFFu) raise(MRG_EINVAL, "n_docs out of range");
-    if ((uintptr_t)d_ids & 3u) raise(MRG_EINVAL, "the ids must be 4-byte aligned");
-    if (!d_terms != !d_counts) raise(MRG_EINVAL, "d_terms and d_counts must both be given, or both be NULL (sizes only)");
-    if (((uintptr_t)d_terms | (uintptr_t)d_counts) & 3u) raise(MRG_EINVAL, "d_terms and d_counts must be 4-byte aligned");
-    // the documents by path (an empty document takes none: its row length stays 0)
-    std::vector<uint32_t> list[3];
-    for (uint32_t i = 0; i < n_docs; ++i) {
-        if (h_tok_off[i + 1] < h_tok_off[i]) raise(MRG_EINVAL, "token offsets must be non-decreasing");
-        const uint64_t T = h_tok_off[i + 1] - h_tok_off[i];
-        if (T > 0xFFFFFFFFull)
-            raise(MRG_EINVAL, "mrg_vocab_term_counts: document %u has %llu ids: at most 4294967295 (counts are 32 bits)", i,
-                  (unsigned long long)T);
-        if (T) list[T <= MRG_TERMS_WAVE_MAX ? 0 : T <= MRG_TERMS_WG_MAX ? 1 : 2].push_back(i);
-    }
-    HIPCHK(hipSetDevice(c->device));
-    memset(c->terms_info, 0, sizeof c->terms_info);
-    memset(c->terms_ms, 0, sizeof c->terms_ms);
-    const uint64_t n_ids = h_tok_off[n_docs] - h_tok_off[0];
-    if (n_ids == 0) {  // no ids: empty rows
-        for (uint32_t i = 0; i <= n_docs; ++i) h_row_off[i] = 0;
-        if (h_unk)
-            for (uint32_t i = 0; i < n_docs; ++i) h_unk[i] = 0;
-        return;
-    }
-    if (!d_ids) raise(MRG_EINVAL, "null ids");
-    // the large documents in slices: maximal runs of at most `budget` ids together, a longer document alone
-    uint64_t budget = 1ull << 25;
-    if (const char *e = getenv("MRG_TEST_TERMS_SLICE_IDS")) budget = std::max<long long>(1, atoll(e));
-    struct Slice {
-        uint32_t first, nd;  // list[2][first, first + nd)
-        uint64_t m, soff_at; // ids; its nd + 1 offsets in `soff`
-    };
-    std::vector<Slice> slices;
-    std::vector<uint64_t> soff;
-    for (uint32_t x = 0; x < list[2].size(); ++x) {
-        const uint64_t T = h_tok_off[list[2][x] + 1] - h_tok_off[list[2][x]];
-        if (slices.empty() || slices.back().m + T > budget) {
-            if (!slices.empty()) soff.push_back(slices.back().m);
-            slices.push_back(Slice{x, 0, 0, soff.size()});
-        }
-        soff.push_back(slices.back().m);
-        slices.back().m += T;
-        slices.back().nd += 1;
-    }
-    if (!slices.empty()) soff.push_back(slices.back().m);
-    for (const Slice &S : slices)
-        if (S.m > 0xFFFFFFFFull) raise(MRG_EINVAL, "MRG_TEST_TERMS_SLICE_IDS: a slice of %llu ids", (unsigned long long)S.m);
-
-    Pool &p = c->pool;
-    hipStream_t s = c->stream;
-    Scratch sc(p);
-    ev_make(c, c->terms_ev);
-    const uint64_t nl[3] = {list[0].size(), list[1].size(), list[2].size()};
-    TermsPlan P{};
-    P.in = d_ids;
-    P.n_words = v->n;
-    uint64_t *d_off = sc.get<uint64_t>((uint64_t)n_docs + 1);
-    P.tok_off = d_off;
-    P.len = sc.get<uint64_t>((uint64_t)n_docs + 1);
-    P.unk = sc.get<uint64_t>(n_docs);
-    uint32_t *d_list = sc.get<uint32_t>(nl[0] + nl[1] + nl[2]);
-    const uint32_t *d_lp[3] = {d_list, d_list + nl[0], d_list + nl[0] + nl[1]};
-    uint64_t *d_soff = sc.get<uint64_t>(soff.size());
-    uint64_t *stmp = sc.get<uint64_t>(mrg_scan_tmp_elems((uint64_t)n_docs + 1));
-    P.err = sc.get<unsigned long long>(1);
-    uint64_t scratch = 8 * (3 * (uint64_t)n_docs + 2) + 4 * (nl[0] + nl[1] + nl[2]) + 8 * soff.size() +
-                       8 * mrg_scan_tmp_elems((uint64_t)n_docs + 1) + 8, slice_max = 0;
-    for (const Slice &S : slices)
-        slice_max = std::max(slice_max, 16 * (S.m + 1) + mrg_sort_u64_keys_tmp_bytes(S.m) + 4 * mrg_scan_tmp_elems(S.m + 1));
-    c->terms_info[0] = n_ids;
-    for (int k = 0; k < 3; ++k) c->terms_info[3 + k] = nl[k];
-    c->terms_info[6] = slices.size();
-    c->terms_info[7] = scratch + slice_max;
-    HIPCHK(hipMemcpyAsync(d_off, h_tok_off, 8 * ((uint64_t)n_docs + 1), hipMemcpyHostToDevice, s));
-    for (int k = 0; k < 3; ++k)
-        if (nl[k]) HIPCHK(hipMemcpyAsync((void *)d_lp[k], list[k].data(), 4 * nl[k], hipMemcpyHostToDevice, s));
-    if (!soff.empty()) HIPCHK(hipMemcpyAsync(d_soff, soff.data(), 8 * soff.size(), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemsetAsync(P.len, 0, 8 * ((uint64_t)n_docs + 1), s));
-    HIPCHK(hipMemsetAsync(P.unk, 0, 8 * (uint64_t)n_docs, s));
-    HIPCHK(hipMemsetAsync(P.err, 0xFF, 8, s));
-
-    // One slice, sorted and run-flagged: K = the sorted keys, E = the scanned run starts, pos = room for
-    // the run positions (E and pos lie in the key buffer the sort left free).
-    struct Sorted {
-        TermsSlice sl;
-        const uint64_t *K;
-        uint32_t *E, *pos;
-    };
-    auto nbytes = [](uint64_t x) {
-        uint32_t b = 0;
-        for (; x; x >>= 8) ++b;
-        return b;
-    };
-    auto sort_slice = [&](const Slice &S, Scratch &ss) {
-        Sorted r{};
-        r.sl = TermsSlice{d_lp[2] + S.first, d_soff + S.soff_at, S.nd, S.m};
-        uint64_t *a = ss.get<uint64_t>(S.m + 1), *b = ss.get<uint64_t>(S.m + 1);
-        void *sort_tmp = ss.get<uint8_t>(mrg_sort_u64_keys_tmp_bytes(S.m));
-        uint32_t *scan_tmp = ss.get<uint32_t>(mrg_scan_tmp_elems(S.m + 1));
-        mrg_terms_launch_keys(P, r.sl, a, s);
-        // the key bytes that can differ: those of an id <= n_words, and of a rank < nd
-        const uint32_t mask = ((1u << nbytes(v->n)) - 1u) | (((1u << nbytes((uint64_t)S.nd - 1u)) - 1u) << 4);
-        uint64_t *K = mrg_radix_sort_u64_keys(a, b, S.m, mask, sort_tmp, s, nullptr);
-        r.K = K;
-        r.E = (uint32_t *)(K == a ? b : a);
-        r.pos = r.E + S.m + 1;
-        mrg_terms_launch_flags(K, S.m, v->n, r.E, s);
-        mrg_scan_u32(r.E, r.E, S.m + 1, scan_tmp, s);
-        HIPCHK(hipGetLastError());
-        return r;
-    };
-
-    // ---- count: row lengths and UNKs of every document, then the row offsets
-    ev_rec(c, c->terms_ev, 0);
-    mrg_terms_launch_lds(P, d_lp[0], (uint32_t)nl[0], false, false, s);
-    mrg_terms_launch_lds(P, d_lp[1], (uint32_t)nl[1], true, false, s);
-    ev_rec(c, c->terms_ev, 1);
-    Scratch kept(p);  // a single slice stays sorted for the emit pass
-    Sorted one{};
-    for (const Slice &S : slices) {
-        Scratch ss(p);
-        const Sorted r = sort_slice(S, ss);
-        mrg_terms_launch_rows(P, r.sl, r.K, r.E, s);
-        if (slices.size() == 1 && d_terms) {
-            one = r;
-            kept = std::move(ss);
-        }
-    }
-    mrg_scan_u64(P.len, P.len, (uint64_t)n_docs + 1, stmp, s);
-    ev_rec(c, c->terms_ev, 2);
-    HIPCHK(hipGetLastError());
-    unsigned long long herr = 0;
-    std::vector<uint64_t> hu(n_docs);
-    HIPCHK(hipMemcpyAsync(h_row_off, P.len, 8 * ((uint64_t)n_docs + 1), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(hu.data(), P.unk, 8 * (uint64_t)n_docs, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(&herr, P.err, 8, hipMemcpyDeviceToHost, s));
-    sync(c);  // (also: the pageable offsets and lists have been read)
-    c->terms_ms[0] = ev_ms(c, c->terms_ev, 0, 1);
-    c->terms_ms[1] = ev_ms(c, c->terms_ev, 1, 2);
-    if (herr != ~0ull)
-        raise(MRG_EINVAL, "mrg_vocab_term_counts: the id at index %llu is not in the vocabulary (%llu words)", herr,
-              (unsigned long long)v->n);
-    uint64_t n_unk = 0;
-    for (uint32_t i = 0; i < n_docs; ++i) n_unk += hu[i];
-    if (h_unk) memcpy(h_unk, hu.data(), 8 * (uint64_t)n_docs);
-    const uint64_t total = h_row_off[n_docs];
-    c->terms_info[1] = total;
-    c->terms_info[2] = n_unk;
-    if (!d_terms) return;
-    if (cap < total) raise(MRG_EINVAL, "destination too small (%llu entries < %llu row entries)", (unsigned long long)cap,
-                           (unsigned long long)total);
-    // ---- emit
-    P.terms = d_terms;
-    P.counts = d_counts;
-    ev_rec(c, c->terms_ev, 3);
-    mrg_terms_launch_lds(P, d_lp[0], (uint32_t)nl[0], false, true, s);
-    mrg_terms_launch_lds(P, d_lp[1], (uint32_t)nl[1], true, true, s);
-    ev_rec(c, c->terms_ev, 4);
-    for (const Slice &S : slices) {
-        Scratch ss(p);
-        const Sorted r = slices.size() == 1 ? one : sort_slice(S, ss);
-        mrg_terms_launch_write(P, r.sl, r.K, r.E, r.pos, s);
-    }
-    ev_rec(c, c->terms_ev, 5);
-    HIPCHK(hipGetLastError());
-    sync(c);
-    c->terms_ms[2] = ev_ms(c, c->terms_ev, 3, 4);
-    c->terms_ms[3] = ev_ms(c, c->terms_ev, 4, 5);
-}
-
-// The CSR of mrg_vocab_term_counts -> the inverted index over ids (k_postings.hip):
-// one pass over the terms checks them and counts the document frequencies into d_post_off, a scan turns
-// them into the offsets; then (term, doc, tf) records are packed, sorted by the term's bytes with the
-// stable LSD radix sort and unpacked.  Touches no job state; scratch comes from the pool and goes back on
-// every exit.
-void vocab_postings(mrg_ctx *c, const mrg_vocab *v, const uint32_t *d_terms, const uint32_t *d_counts,
-                    const uint64_t *h_row_off, uint32_t n_docs, uint32_t doc_base, uint64_t *d_post_off, uint32_t *d_docs,
-                    uint32_t *d_tf, uint64_t cap, uint64_t *h_entries) {
-    if (!c) raise(MRG_EINVAL, "null context");
-    if (!v) raise(MRG_EINVAL, "null vocabulary");
-    if (v->device != c->device) raise(MRG_EINVAL, "the vocabulary lives on device %d, the context on device %d", v->device,
-                                      c->device);
-    if (!h_row_off) raise(MRG_EINVAL, "null offsets (h_row_off needs n_docs + 1 entries)");
-    for (uint32_t i = 0; i < n_docs; ++i)
-        if (h_row_off[i + 1] < h_row_off[i]) raise(MRG_EINVAL, "row offsets must be non-decreasing (row %u)", i);
-    if ((uint64_t)doc_base + n_docs > (1ull << 32))
-        raise(MRG_EINVAL, "doc_base + n_docs = %llu: documents are 32 bits", (unsigned long long)doc_base + n_docs);
-    const uint64_t lo = h_row_off[0], E = h_row_off[n_docs] - lo;
-    if (E > 0xFFFFFFFFull) raise(MRG_EINVAL, "mrg_vocab_postings: %llu entries: at most 4294967295", (unsigned long long)E);
-    if (!d_post_off) raise(MRG_EINVAL, "null d_post_off (it receives the vocabulary's words + 1 offsets)");
-    if (d_tf && !d_docs) raise(MRG_EINVAL, "d_tf without d_docs");
-    if (d_tf && !d_counts) raise(MRG_EINVAL, "d_tf without d_counts");
-    if (((uintptr_t)d_terms | (uintptr_t)d_counts | (uintptr_t)d_docs | (uintptr_t)d_tf) & 3u)
-        raise(MRG_EINVAL, "d_terms, d_counts, d_docs and d_tf must be 4-byte aligned");
-    if ((uintptr_t)d_post_off & 7u) raise(MRG_EINVAL, "d_post_off must be 8-byte aligned");
-    if (d_docs && cap < E) raise(MRG_EINVAL, "destination too small (%llu entries < %llu postings)", (unsigned long long)cap,
-                                 (unsigned long long)E);
-    if (E && !d_terms) raise(MRG_EINVAL, "null terms");
-    HIPCHK(hipSetDevice(c->device));
-    memset(c->post_info, 0, sizeof c->post_info);
-    memset(c->post_ms, 0, sizeof c->post_ms);
-    const uint64_t n_words = v->n;
-    c->post_info[0] = E;
-    c->post_info[1] = n_words;
-    hipStream_t s = c->stream;
-    HIPCHK(hipMemsetAsync(d_post_off, 0, 8 * (n_words + 1), s));
-    if (E == 0) {  // no entries: all-zero offsets
-        sync(c);
-        if (h_entries) *h_entries = 0;
-        return;
-    }
-    Pool &p = c->pool;
-    Scratch sc(p);
-    ev_make(c, c->post_ev);
-    PostPlan P{};
-    P.terms = d_terms;
-    P.counts = d_tf ? d_counts : nullptr;
-    P.n_docs = n_docs;
-    P.doc_base = doc_base;
-    P.lo = lo;
-    P.hi = lo + E;
-    P.n_words = n_words;
-    P.df = (unsigned long long *)d_post_off;
-    P.stat = sc.get<unsigned long long>(4);
-    uint64_t *stmp = sc.get<uint64_t>(mrg_scan_tmp_elems(n_words + 1));
-    uint64_t scratch = 32 + 8 * mrg_scan_tmp_elems(n_words + 1);
-    HIPCHK(hipMemsetAsync(P.stat, 0xFF, 8, s));
-    HIPCHK(hipMemsetAsync(P.stat + 1, 0, 24, s));
-    // ---- count and validate, then the offsets
-    ev_rec(c, c->post_ev, 0);
-    mrg_post_launch_count(P, s);
-    ev_rec(c, c->post_ev, 1);
-    mrg_post_launch_max(P, s);
-    mrg_scan_u64(d_post_off, d_post_off, n_words + 1, stmp, s);  // d_post_off[n_words] = E
-    ev_rec(c, c->post_ev, 2);
-    HIPCHK(hipGetLastError());
-    unsigned long long hstat[4] = {};
-    HIPCHK(hipMemcpyAsync(hstat, P.stat, sizeof hstat, hipMemcpyDeviceToHost, s));
-    sync(c);
-    c->post_ms[0] = ev_ms(c, c->post_ev, 0, 1);
-    c->post_ms[1] = ev_ms(c, c->post_ev, 1, 2);
-    c->post_info[6] = scratch;
-    if (hstat[0] != ~0ull)
-        raise(MRG_EINVAL, "mrg_vocab_postings: the term at index %llu is not in the vocabulary (%llu words)", hstat[0],
-              (unsigned long long)n_words);
-    c->post_info[2] = hstat[3];
-    c->post_info[4] = hstat[1];
-    c->post_info[5] = hstat[2];
-    if (h_entries) *h_entries = E;
-    if (!d_docs) return;
-    // ---- pack, stable sort by the term's bytes, unpack
-    uint64_t *d_off = sc.get<uint64_t>((uint64_t)n_docs + 1);
-    PostRec *a = sc.get<PostRec>(E), *b = sc.get<PostRec>(E);
-    void *sort_tmp = sc.get<uint8_t>(mrg_sort_post_tmp_bytes(E));
-    c->post_info[6] = scratch + 8 * ((uint64_t)n_docs + 1) + 2 * sizeof(PostRec) * E + mrg_sort_post_tmp_bytes(E);
-    P.row_off = d_off;
-    HIPCHK(hipMemcpyAsync(d_off, h_row_off, 8 * ((uint64_t)n_docs + 1), hipMemcpyHostToDevice, s));
-    ev_rec(c, c->post_ev, 2);
-    mrg_post_launch_pack(P, a, s);
-    ev_rec(c, c->post_ev, 3);
-    uint32_t nb = 0;  // the bytes that n_words - 1 can set
-    for (uint64_t x = n_words - 1; x; x >>= 8) ++nb;
-    int passes = 0;
-    const PostRec *r = mrg_radix_sort_post(a, b, E, (1u << nb) - 1u, sort_tmp, s, &passes);
-    ev_rec(c, c->post_ev, 4);
-    mrg_post_launch_unpack(r, E, d_docs, d_tf, s);
-    ev_rec(c, c->post_ev, 5);
-    HIPCHK(hipGetLastError());
-    sync(c);  // (also: the pageable offsets have been read)
-    c->post_info[3] = (uint64_t)passes;
-    c->post_ms[2] = ev_ms(c, c->post_ev, 2, 3);
-    c->post_ms[3] = ev_ms(c, c->post_ev, 3, 4);
-    c->post_ms[4] = ev_ms(c, c->post_ev, 4, 5);
-}
+namespace {
 
 void export_sizes(mrg_ctx *c, uint32_t n_owners, uint64_t *h_rec, uint64_t *h_heap) {
     need_job(c);
@@ -3578,14 +2494,7 @@ int mrg_close(mrg_ctx *c) {
         (void)hipSetDevice(c->device);
         (void)hipStreamSynchronize(c->stream);
         for (auto &e : c->ev) (void)hipEventDestroy(e);
-        for (auto &e : c->enc_ev)
-            if (e) (void)hipEventDestroy(e);
-        for (auto &e : c->dec_ev)
-            if (e) (void)hipEventDestroy(e);
-        for (auto &e : c->terms_ev)
-            if (e) (void)hipEventDestroy(e);
-        for (auto &e : c->post_ev)
-            if (e) (void)hipEventDestroy(e);
+        for (VocDiag *d : {&c->enc, &c->dec, &c->terms, &c->post}) d->destroy();
         (void)hipFree(c->d_cnt);
         (void)hipHostFree(c->h_cnt);
         if (c->h_stage) (void)hipHostFree(c->h_stage);
@@ -3745,115 +2654,6 @@ int mrg_job_copy_topk(mrg_ctx *c, uint8_t *h_dst, uint64_t cap) {
             HIPCHK(hipMemcpyAsync(h_dst, c->d_top, c->top_bytes, hipMemcpyDeviceToHost, c->stream));
         }
         sync(c);
-    });
-}
-
-int mrg_job_vocab(mrg_ctx *c, uint64_t max_words, uint64_t min_count, mrg_vocab **out) {
-    if (out) *out = nullptr;
-    return guard([&] {
-        if (!out) raise(MRG_EINVAL, "null out");
-        *out = job_vocab(c, max_words, min_count);
-    });
-}
-
-int mrg_vocab_size(const mrg_vocab *v, uint64_t *n_words, uint64_t *text_bytes) {
-    return guard([&] {
-        if (!v) raise(MRG_EINVAL, "null vocabulary");
-        if (n_words) *n_words = v->n;
-        if (text_bytes) *text_bytes = v->text_bytes;
-    });
-}
-
-int mrg_vocab_copy_text(const mrg_vocab *v, uint8_t *h_dst, uint64_t cap) {
-    return guard([&] {
-        if (!v) raise(MRG_EINVAL, "null vocabulary");
-        if (cap < v->text_bytes) raise(MRG_EINVAL, "destination too small (%llu < %llu)", (unsigned long long)cap,
-                                       (unsigned long long)v->text_bytes);
-        if (!v->text_bytes) return;
-        if (!h_dst) raise(MRG_EINVAL, "null argument");
-        HIPCHK(hipSetDevice(v->device));
-        HIPCHK(hipMemcpy(h_dst, v->T.text, v->text_bytes, hipMemcpyDeviceToHost));
-    });
-}
-
-void mrg_vocab_free(mrg_vocab *v) { vocab_destroy(v); }
-
-int mrg_vocab_encode(mrg_ctx *c, const mrg_vocab *v, const uint8_t *d_bytes, const uint64_t *h_doc_off, uint32_t n_docs,
-                     uint32_t *d_ids, uint64_t cap_ids, uint64_t *h_tok_off) {
-    return guard([&] { vocab_encode(c, v, d_bytes, h_doc_off, n_docs, d_ids, cap_ids, h_tok_off); });
-}
-
-int mrg_vocab_from_text(mrg_ctx *c, const uint8_t *h_text, uint64_t bytes, uint32_t flags, mrg_vocab **out) {
-    return guard([&] {
-        if (!out) raise(MRG_EINVAL, "null out pointer");
-        *out = nullptr;
-        *out = vocab_from_text(c, h_text, bytes, flags);
-    });
-}
-
-int mrg_vocab_decode(mrg_ctx *c, const mrg_vocab *v, const uint32_t *d_ids, const uint64_t *h_tok_off, uint32_t n_docs,
-                     const uint8_t *h_unk, uint32_t unk_len, uint8_t *d_out, uint64_t cap, uint64_t *h_out_off) {
-    return guard([&] { vocab_decode(c, v, d_ids, h_tok_off, n_docs, h_unk, unk_len, d_out, cap, h_out_off); });
-}
-
-int mrg_vocab_term_counts(mrg_ctx *c, const mrg_vocab *v, const uint32_t *d_ids, const uint64_t *h_tok_off,
-                          uint32_t n_docs, uint32_t *d_terms, uint32_t *d_counts, uint64_t cap, uint64_t *h_row_off,
-                          uint64_t *h_unk) {
-    return guard([&] { vocab_term_counts(c, v, d_ids, h_tok_off, n_docs, d_terms, d_counts, cap, h_row_off, h_unk); });
-}
-
-// Diagnostics of the last mrg_vocab_term_counts (not in include/mrgpu.h; tools/time_terms.py): h_info[0..8) =
-// ids, row entries, UNK ids, documents of the wave, workgroup and large path, large-path slices, scratch
-// bytes; h_ms[0..4) = the LDS paths' count pass, the large path's count pass with the row scan, the LDS
-// paths' emit pass, the large path's emit pass (HIP events, with mrg_set_timing).
-int mrg_terms_info(mrg_ctx *c, uint64_t *h_info, double *h_ms) {
-    return guard([&] {
-        if (!c) raise(MRG_EINVAL, "null context");
-        if (h_info) memcpy(h_info, c->terms_info, sizeof c->terms_info);
-        if (h_ms) memcpy(h_ms, c->terms_ms, sizeof c->terms_ms);
-    });
-}
-
-int mrg_vocab_postings(mrg_ctx *c, const mrg_vocab *v, const uint32_t *d_terms, const uint32_t *d_counts,
-                       const uint64_t *h_row_off, uint32_t n_docs, uint32_t doc_base, uint64_t *d_post_off, uint32_t *d_docs,
-                       uint32_t *d_tf, uint64_t cap, uint64_t *h_entries) {
-    return guard([&] {
-        vocab_postings(c, v, d_terms, d_counts, h_row_off, n_docs, doc_base, d_post_off, d_docs, d_tf, cap, h_entries);
-    });
-}
-
-// Diagnostics of the last mrg_vocab_postings (not in include/mrgpu.h; tools/time_postings.py): h_info[0..7) =
-// entries, words, the largest document frequency, radix passes run, entries counted in LDS, entries counted
-// with global atomics, scratch bytes; h_ms[0..5) = count, scan (with the largest df), pack, sort, unpack
-// (HIP events, with mrg_set_timing).
-int mrg_postings_info(mrg_ctx *c, uint64_t *h_info, double *h_ms) {
-    return guard([&] {
-        if (!c) raise(MRG_EINVAL, "null context");
-        if (h_info) memcpy(h_info, c->post_info, sizeof c->post_info);
-        if (h_ms) memcpy(h_ms, c->post_ms, sizeof c->post_ms);
-    });
-}
-
-// Diagnostics of the last mrg_vocab_decode (not in include/mrgpu.h; tools/time_decode.py): h_info[0..4) =
-// ids, output bytes, chunks, scratch bytes; h_ms[0..4) = count pass, scan + document offsets, emit pass,
-// and the last mrg_vocab_from_text (HIP events, with mrg_set_timing).
-int mrg_decode_info(mrg_ctx *c, uint64_t *h_info, double *h_ms) {
-    return guard([&] {
-        if (!c) raise(MRG_EINVAL, "null context");
-        if (h_info) memcpy(h_info, c->dec_info, sizeof c->dec_info);
-        if (h_ms) memcpy(h_ms, c->dec_ms, sizeof c->dec_ms);
-    });
-}
-
-// Diagnostics of the last mrg_vocab_encode (not in include/mrgpu.h; tools/time_encode.py): h_info[0..7) =
-// tokens, UNK tokens, long tokens, non-ASCII 1 KiB chunks, table probes, input bytes, scratch bytes;
-// h_ms[0..4) = count pass, scan + document offsets, emit pass, and the last mrg_job_vocab (HIP events,
-// with mrg_set_timing).
-int mrg_encode_info(mrg_ctx *c, uint64_t *h_info, double *h_ms) {
-    return guard([&] {
-        if (!c) raise(MRG_EINVAL, "null context");
-        if (h_info) memcpy(h_info, c->enc_info, sizeof c->enc_info);
-        if (h_ms) memcpy(h_ms, c->enc_ms, sizeof c->enc_ms);
     });
 }
 

@@ -190,6 +190,17 @@ def _u64arr(xs):
     return (C.c_uint64 * max(len(xs), 1))(*xs)
 
 
+def _voc_info(name, ctx, info_keys, ms_keys):
+    """One of the mrg_*_info diagnostics (not in include/mrgpu.h): 8 counters and len(ms_keys) HIP-event ms, as a
+    dict under the given names."""
+    f = getattr(load(), name)
+    f.restype = C.c_int
+    f.argtypes = [_vp, _u64p, C.POINTER(C.c_double)]
+    info, ms = (C.c_uint64 * 8)(), (C.c_double * len(ms_keys))()
+    _check(f(ctx.h, info, ms))
+    return {**dict(zip(info_keys, info)), **dict(zip(ms_keys, ms))}
+
+
 class Parts:
     """One map task's output (mrg_parts): per-partition exchange records + long-key heap."""
 
@@ -472,13 +483,8 @@ class Context:
     def decode_info(self):
         """Diagnostics of the last decode(): ids, output bytes, 256-id chunks, scratch bytes; HIP-event ms
         per pass and of the last vocab_from_text() (with set_timing)."""
-        f = load().mrg_decode_info
-        f.restype = C.c_int
-        f.argtypes = [_vp, _u64p, C.POINTER(C.c_double)]
-        info, ms = (C.c_uint64 * 8)(), (C.c_double * 4)()
-        _check(f(self.h, info, ms))
-        return {"ids": info[0], "output_bytes": info[1], "chunks": info[2], "scratch_bytes": info[3],
-                "ms_count": ms[0], "ms_offsets": ms[1], "ms_emit": ms[2], "ms_from_text": ms[3]}
+        return _voc_info("mrg_decode_info", self, ("ids", "output_bytes", "chunks", "scratch_bytes"),
+                         ("ms_count", "ms_offsets", "ms_emit", "ms_from_text"))
 
     def term_counts(self, vocab, ids_ptr, tok_off, terms_ptr=None, counts_ptr=None, cap=0):
         """mrg_vocab_term_counts: per-document term counts of the ids of every document (layout of decode's
@@ -497,14 +503,9 @@ class Context:
     def terms_info(self):
         """Diagnostics of the last term_counts(): ids, row entries, ID_UNK ids, documents taken by the wave,
         workgroup and large path, large-path slices, scratch bytes; HIP-event ms per phase (with set_timing)."""
-        f = load().mrg_terms_info
-        f.restype = C.c_int
-        f.argtypes = [_vp, _u64p, C.POINTER(C.c_double)]
-        info, ms = (C.c_uint64 * 8)(), (C.c_double * 4)()
-        _check(f(self.h, info, ms))
-        return {"ids": info[0], "entries": info[1], "unk": info[2], "wave_docs": info[3], "wg_docs": info[4],
-                "large_docs": info[5], "slices": info[6], "scratch_bytes": info[7], "ms_count_lds": ms[0],
-                "ms_count_large": ms[1], "ms_emit_lds": ms[2], "ms_emit_large": ms[3]}
+        return _voc_info("mrg_terms_info", self, ("ids", "entries", "unk", "wave_docs", "wg_docs", "large_docs", "slices",
+                                                  "scratch_bytes"),
+                         ("ms_count_lds", "ms_count_large", "ms_emit_lds", "ms_emit_large"))
 
     def postings(self, vocab, terms_ptr, counts_ptr, row_off, post_off_ptr, docs_ptr=None, tf_ptr=None, cap=0, doc_base=0):
         """mrg_vocab_postings: the inverted index of a CSR in term_counts' layout (uint32 terms and counts at
@@ -525,26 +526,16 @@ class Context:
         """Diagnostics of the last postings(): entries, words, the largest document frequency, radix passes
         run, entries counted in LDS and with global atomics, scratch bytes; HIP-event ms per phase (with
         set_timing)."""
-        f = load().mrg_postings_info
-        f.restype = C.c_int
-        f.argtypes = [_vp, _u64p, C.POINTER(C.c_double)]
-        info, ms = (C.c_uint64 * 8)(), (C.c_double * 5)()
-        _check(f(self.h, info, ms))
-        return {"entries": info[0], "words": info[1], "max_df": info[2], "passes": info[3], "lds_entries": info[4],
-                "global_entries": info[5], "scratch_bytes": info[6], "ms_count": ms[0], "ms_scan": ms[1],
-                "ms_pack": ms[2], "ms_sort": ms[3], "ms_unpack": ms[4]}
+        return _voc_info("mrg_postings_info", self, ("entries", "words", "max_df", "passes", "lds_entries", "global_entries",
+                                                     "scratch_bytes"),
+                         ("ms_count", "ms_scan", "ms_pack", "ms_sort", "ms_unpack"))
 
     def encode_info(self):
         """Diagnostics of the last encode(): tokens, UNK and long tokens, non-ASCII 1 KiB chunks, table
         probes, input and scratch bytes; HIP-event ms per pass and of the last vocab() (with set_timing)."""
-        f = load().mrg_encode_info
-        f.restype = C.c_int
-        f.argtypes = [_vp, _u64p, C.POINTER(C.c_double)]
-        info, ms = (C.c_uint64 * 8)(), (C.c_double * 4)()
-        _check(f(self.h, info, ms))
-        return {"tokens": info[0], "unk": info[1], "long_tokens": info[2], "nonascii_chunks": info[3],
-                "probes": info[4], "input_bytes": info[5], "scratch_bytes": info[6], "ms_count": ms[0],
-                "ms_offsets": ms[1], "ms_emit": ms[2], "ms_vocab": ms[3]}
+        return _voc_info("mrg_encode_info", self, ("tokens", "unk", "long_tokens", "nonascii_chunks", "probes",
+                                                   "input_bytes", "scratch_bytes"),
+                         ("ms_count", "ms_offsets", "ms_emit", "ms_vocab"))
 
     # ---- plugin surface (host buffers)
     def map_task(self, app, data, doc, doc_id, n_reduce, flags=0):
