@@ -341,6 +341,52 @@ int mrg_vocab_term_counts(mrg_ctx *ctx, const mrg_vocab *v, const uint32_t *d_id
 int mrg_vocab_postings(mrg_ctx *ctx, const mrg_vocab *v, const uint32_t *d_terms, const uint32_t *d_counts,
                        const uint64_t *h_row_off, uint32_t n_docs, uint32_t doc_base, uint64_t *d_post_off,
                        uint32_t *d_docs, uint32_t *d_tf, uint64_t cap, uint64_t *h_entries);
+/* (6, additive): mrg_vocab_search.  The inverted index + a batch of queries -> the k best documents of every
+ * query by BM25, on the device.  d_post_off (words + 1), d_docs and d_tf are what mrg_vocab_postings wrote for
+ * this vocabulary, n_entries its E.  The collection is the documents doc_base .. doc_base + n_docs - 1;
+ * d_doc_len[i] (device, n_docs uint32) is the length in ids of document doc_base + i, MRG_ID_UNK ids included
+ * (h_tok_off[i+1] - h_tok_off[i] of mrg_vocab_encode).  The queries are laid out like the documents of
+ * mrg_vocab_decode: query q is d_q_ids[h_q_off[q] .. h_q_off[q+1]) -- device ids, host offsets, h_q_off[0] may
+ * be greater than 0 -- which is what mrg_vocab_encode of the query texts returns.  At most 2^20 query ids in one
+ * call (the library copies them to the host).
+ * The score is BM25 with the always-positive idf, over the one index passed:
+ *   N = n_docs;  avgdl = (sum of d_doc_len) / N      (summed exactly, divided in double, rounded to float)
+ *   df(t) = d_post_off[t+1] - d_post_off[t]
+ *   idf(t) = ln(1 + (N - df + 0.5) / (df + 0.5))     (in double, rounded to float)
+ *   w(t,d) = idf(t) * tf*(k1+1) / (tf + k1*(1 - b + b*dl(d)/avgdl))      (float32)
+ *   score(q,d) = the sum over the positions j of q, in order, of w(q[j], d)
+ * A term that stands m times in a query counts m times; an MRG_ID_UNK position and a term with no postings
+ * count nothing.  A document is a hit of q when its score is > 0.
+ * h_top_n[q] = min(k, hits of q); row q of the output is d_top_docs[q*k .. q*k + h_top_n[q]) with d_top_scores
+ * at the same positions, by score descending, then document ascending; the documents carry doc_base.  The
+ * entries of a row from h_top_n[q] on are not written.  The selection at the k-th place is exact: every
+ * document above the k-th score is returned, and of those with exactly the k-th score the smallest documents.
+ * The output is fully determined by the input: two calls give identical bytes, whatever the scheduling and
+ * however the call cuts the queries into chunks (MRG_SEARCH_ACC_BYTES, an environment variable read per call,
+ * default 256 MiB: the bytes of dense score rows, n_docs floats per query, that are worked on together; a
+ * query whose one row does not fit is taken alone).
+ * Checked before any device work, MRG_EINVAL with every output untouched: a NULL context or vocabulary, a
+ * vocabulary of another device, NULL d_post_off, h_q_off, d_top_docs, d_top_scores or h_top_n, NULL d_docs,
+ * d_tf or d_doc_len with n_entries > 0, misaligned pointers (4 bytes; d_post_off 8), offsets that are not
+ * non-decreasing, doc_base + n_docs > 2^32, n_entries >= 2^32, k outside 1..MRG_SEARCH_MAX_K, k1 outside
+ * [0, 1000], b outside [0, 1], either one NaN, more than 2^20 query ids.  Checked against the device's data,
+ * MRG_EINVAL with the outputs unspecified: a query id >= the vocabulary's words other than MRG_ID_UNK
+ * (mrg_last_error names the smallest index in d_q_ids, "index N"); for the words the queries name,
+ * d_post_off[t] <= d_post_off[t+1] <= n_entries; every visited posting's document lies in the collection and
+ * the documents of a visited word ascend strictly, as mrg_vocab_term_counts -> mrg_vocab_postings produces
+ * them (mrg_last_error names the smallest offending position in d_docs, "posting N").  These checks are part
+ * of the kernel: the call never writes outside its accumulators.  After every error the context and the
+ * vocabulary stay usable.  n_queries = 0, n_docs = 0, n_entries = 0, an empty vocabulary (every id must then
+ * be MRG_ID_UNK) or all-empty queries: h_top_n all 0, MRG_OK.
+ * The call needs no job and touches no job state.  It runs on the context's stream with scratch from the
+ * context's pool, all returned before the call ends, on error exits too; on return the outputs are complete.
+ * Scratch: per query of a chunk 4 bytes per document (the row), 8 k bytes of candidates and 1 KiB; 20 bytes
+ * per 4096 postings visited; 16 bytes per query id. */
+#define MRG_SEARCH_MAX_K 1024u
+int mrg_vocab_search(mrg_ctx *ctx, const mrg_vocab *v, const uint64_t *d_post_off, const uint32_t *d_docs,
+                     const uint32_t *d_tf, uint64_t n_entries, const uint32_t *d_doc_len, uint32_t n_docs,
+                     uint32_t doc_base, const uint32_t *d_q_ids, const uint64_t *h_q_off, uint32_t n_queries,
+                     float k1, float b, uint32_t k, uint32_t *d_top_docs, float *d_top_scores, uint32_t *h_top_n);
 
 /* ---- multi-GPU: one rank per GPU, the shuffle as an RCCL all-to-all over xGMI ----
  * The reference moves map output to the reduce workers through mr-{m}-{r}.txt files in a shared

@@ -669,6 +669,49 @@ void mrg_post_launch_max(const PostPlan &p, hipStream_t s);    // stat[3], befor
 void mrg_post_launch_pack(const PostPlan &p, PostRec *out, hipStream_t s);
 void mrg_post_launch_unpack(const PostRec *in, uint64_t n, uint32_t *docs, uint32_t *tf, hipStream_t s);  // tf may be null
 
+// ---- k_search.hip: BM25 top-k over the inverted index
+// The part of one (query, position) segment of postings that falls into one window of MRG_SEARCH_TILE
+// postings: [lo, hi) of d_docs / d_tf, lo >= seg_lo = the segment's first posting; `row` is the query's
+// accumulator row in its chunk, idf the float idf of the position's word.
+struct SearchTile {
+    uint32_t lo, hi, seg_lo, row;
+    float idf;
+};
+// One mrg_vocab_search call (the index, the scoring constants, the error cell) and its current chunk of
+// `rows` queries: everything below `rows` is chunk scratch, indexed by the row in the chunk.
+struct SearchPlan {
+    const uint32_t *docs, *tf, *doc_len;
+    uint32_t n_docs, doc_base;
+    uint32_t shift;              // (address of docs / 4) & 3: posting p stands in window (p + shift) / MRG_SEARCH_TILE
+    uint32_t tf_vec;             // tf is 16-byte aligned where docs is
+    float k1, k1p1, b, avgdl;    // k1p1 = k1 + 1 (float); avgdl > 0
+    unsigned long long *err;     // all ones: smallest position in docs of a posting out of range or not ascending
+    uint32_t rows, k;
+    uint32_t q0;                 // the chunk's first query: row r is query q0 + r
+    uint32_t want;               // min(k, n_docs): the rank the select looks for
+    uint64_t stride;             // floats per accumulator row: n_docs rounded up to 4
+    float *acc;                  // [rows * stride] zeroed: the scores
+    uint32_t *hist;              // [rows * 256] zeroed: the select's histogram of the current byte
+    uint32_t *sel;               // [rows * 4]: prefix, rank still wanted, scores above the prefix, top_n
+    uint32_t ntile;              // tiles of MRG_SEARCH_SEL_TILE documents per row
+    uint32_t *cnt;               // [rows * ntile * 2]: documents above / at the threshold per tile, then their scans
+    uint32_t *cand_doc;          // [rows * k] the candidates: document index (without doc_base), score bits
+    uint32_t *cand_bits;
+    uint32_t *top_n;             // [n_queries] of the whole call
+    uint32_t *out_docs;          // the call's outputs
+    float *out_scores;
+};
+#define MRG_SEARCH_SEL_TILE 1024u
+// po[2 i], po[2 i + 1] = post_off[id], post_off[id + 1] of query id i (0, 0 for an id >= n_words)
+void mrg_search_launch_gather(const uint32_t *q_ids, uint64_t n_ids, const uint64_t *post_off, uint64_t n_words,
+                              uint64_t *po, hipStream_t s);
+void mrg_search_launch_sum(const uint32_t *doc_len, uint32_t n_docs, unsigned long long *sum, hipStream_t s);  // *sum zeroed
+// acc[row][doc - doc_base] += w for the n tiles at `tiles`, which belong to one position of the chunk's queries
+void mrg_search_launch_acc(const SearchPlan &p, const SearchTile *tiles, uint64_t n, hipStream_t s);
+// the chunk's rows -> top_n[q0 ..] and the candidates (select, ordered compaction) -> the output rows q0 ..
+void mrg_search_launch_select(const SearchPlan &p, hipStream_t s);
+void mrg_search_launch_order(const SearchPlan &p, hipStream_t s);
+
 // ---- k_gen.hip
 int mrg_gen_zipf_impl(uint8_t *dst, uint64_t n, uint64_t seed, uint64_t file_index, uint32_t vocab, double s, uint32_t style,
                       hipStream_t st);

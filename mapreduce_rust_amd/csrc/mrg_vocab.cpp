@@ -1,7 +1,10 @@
 // mrg_vocab.cpp -- the vocabulary calls of libmrgpu.so (include/mrgpu.h): a vocabulary from a job's ranked keys
-// or from text, text -> ids, ids -> text, per-document term counts, the inverted index; and their diagnostics.
+// or from text, text -> ids, ids -> text, per-document term counts, the inverted index, BM25 search over it; and
+// their diagnostics.
 // Apart from mrg_job_vocab, which ranks the job's keys through job_topk, no call touches job state: each uses the
 // context's device, stream, timing switch and pool, whose scratch goes back on every exit, and its own VocDiag.
+#include <math.h>
+
 #include <memory>
 
 #include "mrg_host.h"
@@ -629,6 +632,197 @@ void vocab_postings(mrg_ctx *c, const mrg_vocab *v, const uint32_t *d_terms, con
     c->post.ms[4] = c->post.elapsed(c, 4, 5);
 }
 
+// The inverted index of mrg_vocab_postings + a batch of queries -> the k best documents of every query by BM25
+// (k_search.hip).  Plan: the offsets of every query position and the sum of the document
+// lengths come back in one stream wait; the host validates, computes the idfs and cuts the segments into tiles.
+// Then the queries go in chunks of dense score rows: one accumulate launch per query position, the radix select
+// with the ordered compaction, the ordering of the candidates.
+void vocab_search(mrg_ctx *c, const mrg_vocab *v, const uint64_t *d_post_off, const uint32_t *d_docs, const uint32_t *d_tf,
+                  uint64_t n_entries, const uint32_t *d_doc_len, uint32_t n_docs, uint32_t doc_base, const uint32_t *d_q_ids,
+                  const uint64_t *h_q_off, uint32_t n_queries, float k1, float b, uint32_t k, uint32_t *d_top_docs,
+                  float *d_top_scores, uint32_t *h_top_n) {
+    voc_args(c, v, n_queries);
+    if (!d_post_off) raise(MRG_EINVAL, "null d_post_off (the vocabulary's words + 1 offsets of mrg_vocab_postings)");
+    if (!h_q_off) raise(MRG_EINVAL, "null offsets (h_q_off needs n_queries + 1 entries)");
+    if (!d_top_docs || !d_top_scores || !h_top_n)
+        raise(MRG_EINVAL, "null output (d_top_docs and d_top_scores need n_queries * k entries, h_top_n n_queries)");
+    if (n_entries && (!d_docs || !d_tf || !d_doc_len)) raise(MRG_EINVAL, "null d_docs, d_tf or d_doc_len with %llu entries",
+                                                             (unsigned long long)n_entries);
+    if (((uintptr_t)d_docs | (uintptr_t)d_tf | (uintptr_t)d_doc_len | (uintptr_t)d_q_ids | (uintptr_t)d_top_docs |
+         (uintptr_t)d_top_scores) & 3u)
+        raise(MRG_EINVAL, "d_docs, d_tf, d_doc_len, d_q_ids, d_top_docs and d_top_scores must be 4-byte aligned");
+    if ((uintptr_t)d_post_off & 7u) raise(MRG_EINVAL, "d_post_off must be 8-byte aligned");
+    if ((uint64_t)doc_base + n_docs > (1ull << 32))
+        raise(MRG_EINVAL, "doc_base + n_docs = %llu: documents are 32 bits", (unsigned long long)doc_base + n_docs);
+    if (n_entries > 0xFFFFFFFFull) raise(MRG_EINVAL, "mrg_vocab_search: %llu entries: at most 4294967295",
+                                         (unsigned long long)n_entries);
+    if (k < 1u || k > MRG_SEARCH_MAX_K) raise(MRG_EINVAL, "k = %u: 1 to %u", k, MRG_SEARCH_MAX_K);
+    if (!(k1 >= 0.0f && k1 <= 1000.0f)) raise(MRG_EINVAL, "k1 = %g: 0 to 1000", (double)k1);
+    if (!(b >= 0.0f && b <= 1.0f)) raise(MRG_EINVAL, "b = %g: 0 to 1", (double)b);
+    voc_enter(c, h_q_off, n_queries, "query offsets must be non-decreasing (query %u)");
+    const uint64_t qlo = h_q_off[0], n_ids = h_q_off[n_queries] - qlo;
+    if (n_ids > (1ull << 20)) raise(MRG_EINVAL, "mrg_vocab_search: %llu query ids in one call: at most 1048576",
+                                    (unsigned long long)n_ids);
+    if (n_ids && !d_q_ids) raise(MRG_EINVAL, "null query ids");
+    c->srch.clear(4);
+    c->srch.info[0] = n_queries;
+    c->srch.info[1] = n_ids;
+    if (!n_ids) {  // no query positions: no hits
+        std::fill(h_top_n, h_top_n + n_queries, 0u);
+        return;
+    }
+    Pool &p = c->pool;
+    hipStream_t s = c->stream;
+    Scratch sc(p);
+    c->srch.make(c);
+    const uint64_t n_words = v->n;
+
+    // ---- plan
+    c->srch.rec(c, 4);
+    uint64_t *d_po = sc.get<uint64_t>(2 * n_ids);
+    unsigned long long *d_small = sc.get<unsigned long long>(2);  // the sum of the lengths, the error position
+    HIPCHK(hipMemsetAsync(d_small, 0, 8, s));
+    HIPCHK(hipMemsetAsync(d_small + 1, 0xFF, 8, s));
+    mrg_search_launch_gather(d_q_ids + qlo, n_ids, d_post_off, n_words, d_po, s);
+    if (n_entries) mrg_search_launch_sum(d_doc_len, n_docs, d_small, s);
+    HIPCHK(hipGetLastError());
+    std::vector<uint32_t> ids(n_ids);
+    std::vector<uint64_t> po(2 * n_ids);
+    unsigned long long sum_len = 0;
+    HIPCHK(hipMemcpyAsync(ids.data(), d_q_ids + qlo, 4 * n_ids, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(po.data(), d_po, 16 * n_ids, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&sum_len, d_small, 8, hipMemcpyDeviceToHost, s));
+    sync(c);
+    for (uint64_t i = 0; i < n_ids; ++i)
+        if (ids[i] != MRG_ID_UNK && ids[i] >= n_words)
+            raise(MRG_EINVAL, "mrg_vocab_search: the id at index %llu is not in the vocabulary (%llu words)",
+                  (unsigned long long)(qlo + i), (unsigned long long)n_words);
+    for (uint64_t i = 0; i < n_ids; ++i)
+        if (po[2 * i] > po[2 * i + 1] || po[2 * i + 1] > n_entries)
+            raise(MRG_EINVAL, "mrg_vocab_search: d_post_off of word %u: [%llu, %llu) is not a range of the %llu entries", ids[i],
+                  (unsigned long long)po[2 * i], (unsigned long long)po[2 * i + 1], (unsigned long long)n_entries);
+    std::vector<uint32_t> top(n_queries, 0u);
+    uint64_t visited = 0;
+    for (uint64_t i = 0; i < n_ids; ++i) visited += po[2 * i + 1] - po[2 * i];
+    c->srch.info[2] = visited;
+    if (!visited || !n_docs) {  // no postings to visit: no hits
+        c->srch.rec(c, 5);
+        sync(c);
+        c->srch.ms[0] = c->srch.elapsed(c, 4, 5);
+        std::copy(top.begin(), top.end(), h_top_n);
+        return;
+    }
+    // the chunks: as many queries as have their dense rows in MRG_SEARCH_ACC_BYTES (one at least; the row of a
+    // query is a grid coordinate of the select: at most 65535)
+    uint64_t acc_bytes = 256ull << 20;
+    if (const char *e = getenv("MRG_SEARCH_ACC_BYTES")) acc_bytes = (uint64_t)std::max<long long>(1, atoll(e));
+    SearchPlan P{};
+    P.docs = d_docs;
+    P.tf = d_tf;
+    P.doc_len = d_doc_len;
+    P.n_docs = n_docs;
+    P.doc_base = doc_base;
+    P.shift = (uint32_t)(((uintptr_t)d_docs >> 2) & 3u);
+    P.tf_vec = (((uintptr_t)d_docs ^ (uintptr_t)d_tf) & 15u) == 0u;
+    P.k1 = k1;
+    P.k1p1 = k1 + 1.0f;
+    P.b = b;
+    const double avgdl = (double)sum_len / (double)n_docs;
+    P.avgdl = avgdl > 0.0 ? (float)avgdl : 1.0f;  // (every length is 0: dl / avgdl counts as 0)
+    P.err = d_small + 1;
+    P.k = k;
+    P.want = std::min(k, n_docs);
+    P.stride = ((uint64_t)n_docs + 3u) & ~3ull;
+    P.ntile = (uint32_t)((P.stride + MRG_SEARCH_SEL_TILE - 1u) / MRG_SEARCH_SEL_TILE);
+    P.out_docs = d_top_docs;
+    P.out_scores = d_top_scores;
+    const uint32_t rows_max = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(n_queries, 65535u),
+                                                           std::max<uint64_t>(1, acc_bytes / (4u * P.stride)));
+    // the tiles, by (chunk, position, query): launch j of a chunk takes position j of its queries
+    struct Launch {
+        uint64_t first, n;  // tiles
+    };
+    std::vector<SearchTile> tiles;
+    std::vector<Launch> launches;
+    std::vector<uint32_t> chunk_launches;  // launches of every chunk
+    for (uint64_t q0 = 0; q0 < n_queries; q0 += rows_max) {
+        const uint32_t rows = (uint32_t)std::min<uint64_t>(rows_max, n_queries - q0);
+        uint64_t longest = 0;
+        for (uint32_t r = 0; r < rows; ++r) longest = std::max(longest, h_q_off[q0 + r + 1] - h_q_off[q0 + r]);
+        uint32_t nl = 0;
+        for (uint64_t j = 0; j < longest; ++j) {
+            const uint64_t first = tiles.size();
+            for (uint32_t r = 0; r < rows; ++r) {
+                const uint64_t at = h_q_off[q0 + r] + j;
+                if (at >= h_q_off[q0 + r + 1]) continue;
+                const uint64_t a = po[2 * (at - qlo)], e = po[2 * (at - qlo) + 1], df = e - a;
+                if (!df) continue;  // MRG_ID_UNK, or a word with no postings
+                // (a df above N cannot ascend strictly inside the collection: the kernel reports it)
+                const double x = df <= n_docs ? ((double)n_docs - (double)df + 0.5) / ((double)df + 0.5) : 0.0;
+                const float idf = (float)log(1.0 + x);
+                for (uint64_t lo = a; lo < e;) {
+                    const uint64_t hi = std::min(e, ((lo + P.shift) / MRG_SEARCH_TILE + 1u) * MRG_SEARCH_TILE - P.shift);
+                    tiles.push_back(SearchTile{(uint32_t)lo, (uint32_t)hi, (uint32_t)a, r, idf});
+                    lo = hi;
+                }
+            }
+            if (tiles.size() > first) {
+                launches.push_back(Launch{first, tiles.size() - first});
+                ++nl;
+            }
+        }
+        chunk_launches.push_back(nl);
+    }
+    SearchTile *d_tiles = sc.get<SearchTile>(tiles.size());
+    P.top_n = sc.get<uint32_t>(n_queries);
+    HIPCHK(hipMemcpyAsync(d_tiles, tiles.data(), sizeof(SearchTile) * tiles.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(P.top_n, 0, 4 * (uint64_t)n_queries, s));
+    const uint64_t n_acc = (uint64_t)rows_max * P.stride, n_cnt = 2 * (uint64_t)rows_max * P.ntile;
+    P.acc = sc.get<float>(n_acc);
+    P.hist = sc.get<uint32_t>(256 * (uint64_t)rows_max);
+    P.sel = sc.get<uint32_t>(4 * (uint64_t)rows_max);
+    P.cnt = sc.get<uint32_t>(n_cnt);
+    P.cand_doc = sc.get<uint32_t>((uint64_t)rows_max * k);
+    P.cand_bits = sc.get<uint32_t>((uint64_t)rows_max * k);
+    c->srch.info[3] = chunk_launches.size();
+    c->srch.info[4] = launches.size();
+    c->srch.info[5] = 16 * n_ids + 16 + sizeof(SearchTile) * tiles.size() + 4 * (uint64_t)n_queries + 4 * n_acc +
+                      (1024 + 16 + 8 * (uint64_t)k) * rows_max + 4 * n_cnt;
+    HIPCHK(hipMemsetAsync(P.hist, 0, 1024 * (uint64_t)rows_max, s));
+    c->srch.rec(c, 5);
+    if (c->timing) c->srch.ms[0] = c->srch.elapsed(c, 4, 5);
+
+    // ---- the chunks
+    uint64_t li = 0;
+    for (uint64_t q0 = 0, ch = 0; q0 < n_queries; q0 += rows_max, ++ch) {
+        P.rows = (uint32_t)std::min<uint64_t>(rows_max, n_queries - q0);
+        P.q0 = (uint32_t)q0;
+        c->srch.rec(c, 0);
+        HIPCHK(hipMemsetAsync(P.acc, 0, 4 * (uint64_t)P.rows * P.stride, s));
+        for (uint32_t j = 0; j < chunk_launches[ch]; ++j, ++li)
+            mrg_search_launch_acc(P, d_tiles + launches[li].first, launches[li].n, s);
+        c->srch.rec(c, 1);
+        mrg_search_launch_select(P, s);
+        c->srch.rec(c, 2);
+        mrg_search_launch_order(P, s);
+        c->srch.rec(c, 3);
+        HIPCHK(hipGetLastError());
+        if (c->timing) {  // (the events are reused by the next chunk: read them now)
+            c->srch.ms[1] += c->srch.elapsed(c, 0, 1);
+            c->srch.ms[2] += c->srch.elapsed(c, 1, 2);
+            c->srch.ms[3] += c->srch.elapsed(c, 2, 3);
+        }
+    }
+    unsigned long long herr = 0;
+    HIPCHK(hipMemcpyAsync(top.data(), P.top_n, 4 * (uint64_t)n_queries, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&herr, P.err, 8, hipMemcpyDeviceToHost, s));
+    sync(c);  // (also: the pageable tiles have been read)
+    if (herr != ~0ull)
+        raise(MRG_EINVAL, "mrg_vocab_search: posting %llu: its document is outside [doc_base, doc_base + n_docs), or not "
+                          "above the document before it in its word's postings", herr);
+    std::copy(top.begin(), top.end(), h_top_n);
+}
+
 // one of the mrg_*_info entry points: all of the record's info, the first n_ms of its milliseconds
 int voc_info(mrg_ctx *c, VocDiag mrg_ctx::*diag, int n_ms, uint64_t *h_info, double *h_ms) {
     return guard([&] {
@@ -716,6 +910,21 @@ int mrg_vocab_postings(mrg_ctx *c, const mrg_vocab *v, const uint32_t *d_terms, 
 // with global atomics, scratch bytes; h_ms[0..5) = count, scan (with the largest df), pack, sort, unpack
 // (HIP events, with mrg_set_timing).
 int mrg_postings_info(mrg_ctx *c, uint64_t *h_info, double *h_ms) { return voc_info(c, &mrg_ctx::post, 5, h_info, h_ms); }
+
+int mrg_vocab_search(mrg_ctx *c, const mrg_vocab *v, const uint64_t *d_post_off, const uint32_t *d_docs, const uint32_t *d_tf,
+                     uint64_t n_entries, const uint32_t *d_doc_len, uint32_t n_docs, uint32_t doc_base,
+                     const uint32_t *d_q_ids, const uint64_t *h_q_off, uint32_t n_queries, float k1, float b, uint32_t k,
+                     uint32_t *d_top_docs, float *d_top_scores, uint32_t *h_top_n) {
+    return guard([&] {
+        vocab_search(c, v, d_post_off, d_docs, d_tf, n_entries, d_doc_len, n_docs, doc_base, d_q_ids, h_q_off, n_queries, k1, b,
+                     k, d_top_docs, d_top_scores, h_top_n);
+    });
+}
+
+// Diagnostics of the last mrg_vocab_search (not in include/mrgpu.h; tools/time_search.py): h_info[0..6) =
+// queries, query positions, postings visited, chunks, accumulate launches, scratch bytes; h_ms[0..4) = plan,
+// accumulate, select (with the compaction), order, summed over the chunks (HIP events, with mrg_set_timing).
+int mrg_search_info(mrg_ctx *c, uint64_t *h_info, double *h_ms) { return voc_info(c, &mrg_ctx::srch, 4, h_info, h_ms); }
 
 // Diagnostics of the last mrg_vocab_decode (not in include/mrgpu.h; tools/time_decode.py): h_info[0..4) =
 // ids, output bytes, chunks, scratch bytes; h_ms[0..4) = count pass, scan + document offsets, emit pass,

@@ -29,6 +29,10 @@ TERMS_WG_MAX = 4096
 # finds the rows of POST_TILE consecutive entries (MRG_POST_LDS_WORDS, MRG_POST_TILE of csrc/mrg_device.h)
 POST_LDS_WORDS = 8192
 POST_TILE = 2048
+# search: one workgroup accumulates the postings of a query position inside one window of SEARCH_TILE postings;
+# a query returns at most SEARCH_MAX_K documents (MRG_SEARCH_TILE, MRG_SEARCH_MAX_K of csrc/mrg_device.h)
+SEARCH_TILE = 4096
+SEARCH_MAX_K = 1024
 
 
 def debug_hash_bits(n):
@@ -127,6 +131,8 @@ _SIGS = {
     "mrg_vocab_decode": (C.c_int, [_vp, _vp, _vp, _u64p, C.c_uint32, C.c_char_p, C.c_uint32, _vp, C.c_uint64, _u64p]),
     "mrg_vocab_term_counts": (C.c_int, [_vp, _vp, _vp, _u64p, C.c_uint32, _vp, _vp, C.c_uint64, _u64p, _u64p]),
     "mrg_vocab_postings": (C.c_int, [_vp, _vp, _vp, _vp, _u64p, C.c_uint32, C.c_uint32, _vp, _vp, _vp, C.c_uint64, _u64p]),
+    "mrg_vocab_search": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint64, _vp, C.c_uint32, C.c_uint32, _vp, _u64p, C.c_uint32,
+                                   C.c_float, C.c_float, C.c_uint32, _vp, _vp, _u32p]),
     "mrg_map": (C.c_int, [_vp, C.c_int, C.c_char_p, C.c_size_t, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32,
                           C.POINTER(_vp)]),
     "mrg_parts_get": (C.c_int, [_vp, C.c_uint32, C.POINTER(_vp), _u64p, C.POINTER(_vp), _u64p]),
@@ -529,6 +535,29 @@ class Context:
         return _voc_info("mrg_postings_info", self, ("entries", "words", "max_df", "passes", "lds_entries", "global_entries",
                                                      "scratch_bytes"),
                          ("ms_count", "ms_scan", "ms_pack", "ms_sort", "ms_unpack"))
+
+    def search(self, vocab, post_off_ptr, docs_ptr, tf_ptr, n_entries, doc_len_ptr, n_docs, q_ids_ptr, q_off, k,
+               top_docs_ptr, top_scores_ptr, k1=1.2, b=0.75, doc_base=0):
+        """mrg_vocab_search: the k best documents of every query by BM25 over the index postings() wrote
+        (post_off_ptr, docs_ptr, tf_ptr, its n_entries) for the documents doc_base .. doc_base + n_docs - 1, whose
+        lengths in ids are the uint32 at doc_len_ptr.  Query q is the ids q_ids[q_off[q]:q_off[q + 1]] at the
+        device pointer q_ids_ptr (encode's output for the query texts).  Returns top_n: row q of the results is
+        top_docs[q * k:q * k + top_n[q]] (uint32) with top_scores (float32) at the same positions, by score
+        descending, then document ascending; the rest of a row is not written."""
+        if len(q_off) < 1:
+            raise ValueError("q_off needs n_queries + 1 entries (at least [0])")
+        n = len(q_off) - 1
+        top = (C.c_uint32 * max(n, 1))()
+        _check(load().mrg_vocab_search(self.h, vocab.h, post_off_ptr, docs_ptr, tf_ptr, n_entries, doc_len_ptr, n_docs,
+                                       doc_base, q_ids_ptr, _u64arr(q_off), n, k1, b, k, top_docs_ptr, top_scores_ptr, top))
+        return list(top)[:n]
+
+    def search_info(self):
+        """Diagnostics of the last search(): queries, query positions, postings visited, chunks, accumulate
+        launches, scratch bytes; HIP-event ms per phase, summed over the chunks (with set_timing)."""
+        return _voc_info("mrg_search_info", self, ("queries", "positions", "postings", "chunks", "acc_launches",
+                                                   "scratch_bytes"),
+                         ("ms_plan", "ms_accumulate", "ms_select", "ms_order"))
 
     def encode_info(self):
         """Diagnostics of the last encode(): tokens, UNK and long tokens, non-ASCII 1 KiB chunks, table

@@ -33,6 +33,8 @@ pub const fn mrg_flag_top(k: u32) -> u32 {
 }
 /// `mrg_vocab_encode`: the id of a word that is not in the vocabulary.
 pub const MRG_ID_UNK: u32 = 0xFFFF_FFFF;
+/// `mrg_vocab_search`: the largest k.
+pub const MRG_SEARCH_MAX_K: u32 = 1024;
 pub const MRG_XREC_BYTES: usize = 24;
 pub const MRG_ABI_VERSION: u32 = 6;
 pub const MRG_COMM_ID_BYTES: usize = 128;
@@ -137,6 +139,7 @@ extern "C" {
     pub fn mrg_vocab_decode(ctx: *mut mrg_ctx, v: *const mrg_vocab, d_ids: *const u32, h_tok_off: *const u64, n_docs: u32, h_unk: *const u8, unk_len: u32, d_out: *mut u8, cap: u64, h_out_off: *mut u64) -> c_int;
     pub fn mrg_vocab_term_counts(ctx: *mut mrg_ctx, v: *const mrg_vocab, d_ids: *const u32, h_tok_off: *const u64, n_docs: u32, d_terms: *mut u32, d_counts: *mut u32, cap: u64, h_row_off: *mut u64, h_unk: *mut u64) -> c_int;
     pub fn mrg_vocab_postings(ctx: *mut mrg_ctx, v: *const mrg_vocab, d_terms: *const u32, d_counts: *const u32, h_row_off: *const u64, n_docs: u32, doc_base: u32, d_post_off: *mut u64, d_docs: *mut u32, d_tf: *mut u32, cap: u64, h_entries: *mut u64) -> c_int;
+    pub fn mrg_vocab_search(ctx: *mut mrg_ctx, v: *const mrg_vocab, d_post_off: *const u64, d_docs: *const u32, d_tf: *const u32, n_entries: u64, d_doc_len: *const u32, n_docs: u32, doc_base: u32, d_q_ids: *const u32, h_q_off: *const u64, n_queries: u32, k1: f32, b: f32, k: u32, d_top_docs: *mut u32, d_top_scores: *mut f32, h_top_n: *mut u32) -> c_int;
 
     pub fn mrg_comm_get_id(id: *mut u8) -> c_int;
     pub fn mrg_comm_init(ctx: *mut mrg_ctx, id: *const u8, n_ranks: c_int, rank: c_int,
