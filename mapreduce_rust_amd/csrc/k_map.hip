@@ -17,9 +17,14 @@
 //      LDS bank) into W16 (\w) and S16 (White_Space) masks; the first halo segment by 16 lanes and
 //      two ballots; token starts = non-space bytes after a space (the neighbour lane's last class by
 //      DPP wave_shr); a DPP prefix sum gives every start a queue slot;
-//   2. per tile each lane stores its 2-segment mask window (W and S of segments g, g+1) -- a consumer
-//      lane reads ONE 8-byte word to find its token's raw length (first space), the \w span and
-//      whether a deleted byte sits inside the token ("don't");
+//   2. the wc map (block queue) stages the whole 2 KiB block in the wave's LDS
+//      window once, stores one mask word (W16 | S16 << 16) per segment and fills ONE token queue from
+//      one prefix sum over both tiles' start counts; the queue holds 320 starts, and a block with more
+//      (dense text) is drained 40 segments at a time.  A consumer lane reads the words of segments g
+//      and g + 1 (one ds_read2_b32) to find its token's raw length (first space), the \w span and
+//      whether a deleted byte sits inside the token ("don't").  The indexer and the wide map stage,
+//      scan and queue each 1 KiB tile on its own (the indexer's LDS has no room for the block's
+//      window), with an 8-byte mask pair (segments g, g + 1) per segment;
 //   3. TWO tokens per lane per round (queue entries q and q + 64): 5 window dwords aligned to the
 //      key's first byte (v_alignbyte) -> v_perm with a per-(length, 1-byte gap) selector from an LDS
 //      table gives the big-endian packed key (k0, k1); further interior deletions are squeezed out
@@ -45,8 +50,8 @@ namespace {
 
 // Block rounds (r04, MRG_MAP_BR=1 in commit 5e363df, since removed): both tiles of a block tokenized
 // by rounds of four tokens per lane with 12 waves per workgroup -- slower (157 VGPRs, 3 waves per
-// SIMD).  Tiles are staged one at a time (a whole-block window needs the 16
-// KiB that 16-byte table slots freed, and those slots cost ASCII text 3.5 %: section 11.1).
+// SIMD).  The indexer and the wide map stage tiles one at a time; the wc map
+// stages the block (its window's LDS comes from a 64 Kibit doorkeeper and a 320-entry queue: below).
 constexpr int NW = MRG_MAP_WAVES;
 constexpr int WG = 64 * NW;
 constexpr int SEG = MRG_MAP_SEG;
@@ -74,6 +79,20 @@ static_assert(BEHIND == 16 && HALO % 16 == 0 && HALO >= 64, "one 16-byte vector 
 //   tile's first byte; reads are also clamped to QCAP - 1
 static_assert(QCAP >= TILE / 2 + 1, "the token queue holds every start of a tile");
 static_assert(BLK == 2 * TILE && NSUB == 2, "A/B register sets hold two tiles per lane (v0, v1)");
+// Block queue (the wc map with the LDS table: k_map<CAP, false, false>): the whole block is staged
+// and queued once.  Same checks against the block-wide arrays.
+constexpr int WINB = BEHIND + BLK + HALO + 48;   // the block's window row
+constexpr int NMWB = BLK / SEG + 1;              // one W16 | S16 << 16 word per segment + the halo's first
+constexpr int QRANGE = 40;                       // segments drained at a time by a block past QCAPB starts
+constexpr int QCAPB = QRANGE * SEG / 2;          // the block's queue: 320 starts (C3: 245 +- 5.5 per block)
+static_assert(WINB % 16 == 0, "16-byte window rows");
+static_assert(16 * (1 + BLK / 16 + HALO / 16) <= WINB, "staged vectors fit the block's window row");
+static_assert(BEHIND + (BLK - 1) + 31 + 20 <= WINB, "the 5-dword key read stays in the block's window row");
+static_assert(NMWB == 2 * 64 + 1, "each lane owns segments lane and 64 + lane; lane 0 also the halo's");
+//   queue: two starts are never adjacent bytes (a start follows a space), so the QRANGE * SEG bytes
+//   of a segment range hold at most QRANGE * SEG / 2 starts, the range's first byte included
+static_assert(QCAPB * 2 >= QRANGE * SEG && QRANGE >= 1, "a segment range's starts fit the block's queue");
+static_assert(QCAPB >= 128, "a round reads entries q and q + 64 of a queue that may hold two full rounds");
 
 // ---------------------------------------------------------------- wave primitives (DPP, wave64)
 __device__ __forceinline__ uint32_t from_next_lane(uint32_t v) {  // lane l <- lane l+1 (lane 63 <- 0)
@@ -251,7 +270,7 @@ struct alignas(16) KeyPair {
 // (Measured by simulation at C3: 8-way tag groups 69.2 % hits, 2-way sets 68.1 %.)
 //
 // Admission (doorkeeper): a key may claim an empty way only on its second sighting in this
-// workgroup -- the first sets its two bits in a 128 Kibit LDS Bloom filter (positions from the hash
+// workgroup -- the first sets its two bits in a 64 Kibit LDS Bloom filter (positions from the hash
 // bits above the set index and from a remix of the hash; 32 Kibit for the indexer) and goes to the
 // tail.  The table fills once and keeps its keys, so without the filter it
 // fills with whatever the first few thousand tokens hold, singletons included; with it, mostly with
@@ -261,7 +280,7 @@ struct alignas(16) KeyPair {
 #define MRG_MAP_DOOR 1
 #endif
 #ifndef MRG_MAP_DOOR_WORDS
-#define MRG_MAP_DOOR_WORDS 4096
+#define MRG_MAP_DOOR_WORDS 2048  // 64 Kibit (128 Kibit measured the same; the block queue's LDS comes from here)
 #endif
 #ifndef MRG_MAP_DOOR_LEVELS
 #define MRG_MAP_DOOR_LEVELS 1
@@ -813,12 +832,18 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
     // the arguments live in device memory (not the kernarg segment): fields are loaded where they
     // are used instead of being held in SGPRs for the whole kernel
     const MapArgs &A = *Ap;
-    // per wave: staged window, 2-segment mask windows, token queue (waves work on their own tiles)
-    __shared__ __attribute__((aligned(16))) uint8_t s_win[NW][WIN];
-    __shared__ __attribute__((aligned(8))) uint64_t s_mp[NW][NMP];  // W(g)|W(g+1)<<16 | (S(g)|S(g+1)<<16)<<32
+    // per wave: staged window, segment masks, token queue (waves work on their own blocks)
+    // BQ: the block queue (one staging, one scan, one queue fill per 2 KiB block).  The indexer and
+    // the wide map keep the per-tile path (the indexer's LDS has no room for the block's window).
+    constexpr bool BQ = !IDX && !WIDE;
+    constexpr int WROW = BQ ? WINB : WIN, QROW = BQ ? QCAPB : QCAP;
+    __shared__ __attribute__((aligned(16))) uint8_t s_win[NW][WROW];
+    // per tile: 64 pairs W(g)|W(g+1)<<16 | (S(g)|S(g+1)<<16)<<32; BQ: one word W(g)|S(g)<<16 per
+    // segment of the block and the halo's first (a consumer reads words g and g + 1)
+    __shared__ __attribute__((aligned(8))) uint32_t s_mp[NW][BQ ? NMWB : 2 * NMP];
     // 8-byte aligned rows: the class fix's compacted decode uses a row as 64 u64 slots between tiles
-    __shared__ __attribute__((aligned(8))) uint16_t s_q[NW][QCAP];
-    static_assert((QCAP * sizeof(uint16_t)) % 8 == 0 && QCAP * sizeof(uint16_t) >= 64 * 8, "queue rows hold 64 u64 slots");
+    __shared__ __attribute__((aligned(8))) uint16_t s_q[NW][QROW];
+    static_assert((QROW * sizeof(uint16_t)) % 8 == 0 && QROW * sizeof(uint16_t) >= 64 * 8, "queue rows hold 64 u64 slots");
     // LUT and length masks first in LDS (highest alignment): their base then fits the 16-bit
     // offset field of ds_read, so a lookup needs no separate address add
     // Byte class per byte position p of a dword: s_lut[p][c] = (W | S << 4) << p, one byte per byte
@@ -949,7 +974,8 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
     GAS uint64_t *const pool = gp(A.pool);
     GAS uint64_t *const pool16 = gp(A.pool16);
     uint8_t *win = s_win[wv];
-    uint64_t *mp = s_mp[wv];
+    uint32_t *mw = s_mp[wv];                                // BQ: the block's mask words
+    uint64_t *mp = reinterpret_cast<uint64_t *>(s_mp[wv]);  // per tile: the mask pairs
     uint16_t *queue = s_q[wv];
     __syncthreads();
 
@@ -1029,16 +1055,25 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
 #define MRG_PT(i)
 #define MRG_FT(i)
 #endif
-    // A token of the wave's queue: entry q (of total) holds its start s (tile offset); its raw
-    // length, \w span and deleted bytes come from one 8-byte mask-pair read, its key bytes from the
-    // window.  fast: a key of <= 16 bytes ending inside the 2-segment window; slow: the rest (the
+    // A token of the wave's queue: entry q (of total) holds its start s (offset in the staged tile or
+    // block); its raw length, \w span and deleted bytes come from one read of the masks of segments
+    // s / 16 and s / 16 + 1, its key bytes from the window.  fast: a key of <= 16 bytes ending
+    // inside the 2-segment window; slow: the rest (the
     // exact walker).  Returns the deleted-byte runs still to squeeze out (more than one).
     auto extract = [&](uint32_t q, uint32_t sraw, uint32_t total, bool &fast, bool &slow, uint32_t &s,
                        uint64_t &tk0, uint64_t &tk1) -> uint32_t {
         const bool act = q < total;
         s = act ? sraw : 0u;
-        const uint64_t mw = mp[s >> 4];
-        const uint32_t Wp = (uint32_t)mw, Sp = (uint32_t)(mw >> 32);
+        uint32_t Wp, Sp;
+        if constexpr (BQ) {  // the words of segments g and g + 1 (one ds_read2_b32), halves regrouped
+            const uint32_t ma = mw[s >> 4], mb = mw[(s >> 4) + 1u];
+            Wp = __builtin_amdgcn_perm(mb, ma, 0x05040100u);
+            Sp = __builtin_amdgcn_perm(mb, ma, 0x07060302u);
+        } else {
+            const uint64_t pr = mp[s >> 4];
+            Wp = (uint32_t)pr;
+            Sp = (uint32_t)(pr >> 32);
+        }
         const uint32_t i = s & 15u;
         const uint32_t Sr = Sp >> i;
         const uint32_t n = (uint32_t)__builtin_ctz(Sr | 0x80000000u);  // raw length (if Sr != 0)
@@ -1099,11 +1134,12 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
         }
     };
 
-    // A deferred slow token through the tile's byte classes (r04): the mask pairs mp[] hold W16 / S16
-    // of every segment of the tile, exact for UTF-8 too (pair k = segments k and k + 1, so the last
-    // pair's high halves are the first halo segment), and the window holds its bytes -- the token's
+    // A deferred slow token through the staged byte classes (r04): the masks hold W16 / S16 of every
+    // staged segment, exact for UTF-8 too (per tile: pair k = segments k and k + 1, so the last
+    // pair's high halves are the first halo segment; block queue: word nseg is the first halo
+    // segment), and the window holds its bytes -- the token's
     // end and key need no codepoint decoding: the key is the W bytes before the first S byte.  s = the
-    // token's tile offset, nseg = the tile's segments.  False when the token runs past the first halo
+    // token's offset, nseg = the staged segments.  False when the token runs past the first halo
     // segment (then the codepoint walker).
     auto mask_walk = [&](uint32_t s, uint32_t nseg, uint64_t &tk0, uint64_t &tk1, uint32_t &tlen,
                          uint32_t &traw) -> bool {
@@ -1113,10 +1149,17 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
         const uint32_t *win32 = reinterpret_cast<const uint32_t *>(win);
         uint32_t i = s & 15u;
         for (uint32_t seg = s >> 4; seg <= nseg; ++seg, i = 0) {
-            const uint64_t mw = mp[seg < nseg ? seg : nseg - 1u];
-            const uint32_t sh = seg < nseg ? 0u : 16u;
-            uint32_t W = ((((uint32_t)mw >> sh) & 0xFFFFu) >> i) << i;
-            const uint32_t S = ((((uint32_t)(mw >> 32) >> sh) & 0xFFFFu) >> i) << i;
+            uint32_t W, S;
+            if constexpr (BQ) {  // word nseg is the halo's first segment
+                const uint32_t m = mw[seg];
+                W = ((m & 0xFFFFu) >> i) << i;
+                S = ((m >> 16) >> i) << i;
+            } else {
+                const uint64_t pr = mp[seg < nseg ? seg : nseg - 1u];
+                const uint32_t sh = seg < nseg ? 0u : 16u;
+                W = ((((uint32_t)pr >> sh) & 0xFFFFu) >> i) << i;
+                S = ((((uint32_t)(pr >> 32) >> sh) & 0xFFFFu) >> i) << i;
+            }
             const uint32_t e = S ? (uint32_t)__builtin_ctz(S) : 16u;
             W &= (1u << e) - 1u;
             // key bytes (only the first 16 are packed): each run of W bytes as one selector load (the
@@ -1453,6 +1496,168 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
             return;
         }
 
+        // tokens of the wave's queue (entries 0 .. total - 1), TWO per lane per round (entries q and
+        // q + 64: two independent LDS dependency chains in one instruction stream, so each wait covers
+        // both).  Returns the number of slow tokens, deferred to the front of the queue.
+        auto rounds = [&](uint32_t total, bool may_claim) -> uint32_t {
+            uint32_t nslow = 0;
+            for (uint32_t base = 0; base < total; base += 128) {
+                bool fa, sa, fb, sb;
+                uint32_t sA, sB;
+                uint64_t a0, a1, b0, b1;
+                // both queue entries first, unconditionally (entries past `total` are stale but in
+                // bounds), so the two chains share every LDS wait
+                const uint32_t qa = base + (uint32_t)lane, qb = qa + 64u;
+                const uint32_t ra = queue[min(qa, (uint32_t)QROW - 1u)], rb = queue[min(qb, (uint32_t)QROW - 1u)];
+                uint32_t ga = extract(qa, ra, total, fa, sa, sA, a0, a1);
+                uint32_t gb = extract(qb, rb, total, fb, sb, sB, b0, b1);
+                if (!(abl & 1024u) && __any((ga | gb) != 0u)) {
+                    squeeze(ga, a0, a1);
+                    squeeze(gb, b0, b1);
+                }
+                // slow tokens (past the 2-segment window, or > 16 raw key bytes) are deferred: their
+                // starts go to the consumed front of the queue (every lane has read both its entries,
+                // and the deferred count never exceeds the entries read so far)
+                const uint64_t ma = __ballot(sa), mb = __ballot(sb);
+                if (ma | mb) {
+                    const uint32_t ra = __builtin_amdgcn_mbcnt_hi((uint32_t)(ma >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ma, 0u));
+                    const uint32_t rb = __builtin_amdgcn_mbcnt_hi((uint32_t)(mb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mb, 0u));
+                    const uint32_t na = (uint32_t)__builtin_popcountll(ma);
+                    if (sa) queue[nslow + ra] = (uint16_t)sA;
+                    if (sb) queue[nslow + na + rb] = (uint16_t)sB;
+                    nslow += na + (uint32_t)__builtin_popcountll(mb);
+                }
+                my_tokens += (fa ? 1u : 0u) + (fb ? 1u : 0u);
+                const bool hv[2] = {fa, fb};
+                const uint64_t kk0[2] = {a0, b0}, kk1[2] = {a1, b1};
+                if constexpr (WIDE) {
+                    wide_store(A, tails, fa, a0, a1);
+                    wide_store(A, tails, fb, b0, b1);
+                } else {
+                    emit_fastN<2>(A, abl, hbits, table, tails, pool, pool16, hv, kk0, kk1, docid, may_claim);
+                }
+            }
+            return nslow;
+        };
+        // deferred slow tokens (queue entries 0 .. nslow - 1: offsets from At), one per lane: through
+        // the nseg segments' masks, or (a token running past the first halo segment) the exact
+        // per-codepoint walker (forward reads only: the staged bytes are [At, whi))
+        auto slow_tokens = [&](uint32_t nslow, uint64_t At, uint64_t whi, uint32_t nseg) {
+            if (!nslow || (abl & 512u)) return;
+            const uint64_t wbase = At - (uint64_t)BEHIND;
+            wave_sync_lds();
+            auto rd = [&](uint64_t a) -> uint32_t {
+                if (a >= At && a < whi) return (uint32_t)win[a - wbase];
+                return (uint32_t)gp(A.in)[a];
+            };
+            for (uint32_t base = 0; base < nslow; base += 64) {
+                const uint32_t q = base + (uint32_t)lane;
+                bool have = false;
+                uint64_t tk0 = 0, tk1 = 0, a = 0;
+                uint32_t tlen = 0, traw = 0;
+                if (q < nslow) {
+                    const uint32_t s = queue[q];
+                    a = At + s;
+                    if (!(abl & 128u) && mask_walk(s, nseg, tk0, tk1, tlen, traw)) {
+                        have = tlen > 0;
+                    } else {
+                        uint64_t e2;
+                        if (walk_token(rd, a, doc_hi, A.counters, tk0, tk1, tlen, e2) && tlen > 0) {
+                            have = true;
+                            traw = (uint32_t)(e2 - a);
+                        }
+                    }
+                }
+                my_tokens += have ? 1u : 0u;
+                emit<CAP, IDX, WIDE>(A, table, tails, have, tk0, tk1, tlen, a, traw, docid);
+            }
+        };
+        // an atomic LDS load (ds_read_b32): a volatile read of the same word compiled to a FLAT
+        // load + s_waitcnt vmcnt(0), which made every tile wait for the previous tile's tail stores
+        auto table_open = [&]() -> bool {
+            return __builtin_amdgcn_readfirstlane(__hip_atomic_load(&s_fill, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) <
+                   (uint32_t)CAP;
+        };
+
+        if constexpr (BQ) {
+            // ---- block queue: the whole block staged, scanned and queued once
+            const uint64_t whi = umin64(Ab + (uint64_t)(BLK + HALO), doc_hi);
+            // stage the block and its 64-byte halo (the previous block's readers are done: program order)
+            wave_sync_lds();
+            reinterpret_cast<uint4 *>(win)[1 + lane] = X.v0;
+            reinterpret_cast<uint4 *>(win)[65 + lane] = X.v1;
+            if (lane >= 1 && lane < 5) reinterpret_cast<uint4 *>(win)[128 + lane] = X.e;
+            // masks: one word per segment, the halo's first segment behind them
+            mw[lane] = m0;
+            mw[64 + lane] = m1;
+            if (lane == 0) mw[2 * 64] = mh;
+            // token starts of this lane's two segments (lane and 64 + lane): the previous byte's class
+            // from lane l-1 (lane 0: the byte before the block, and tile 0's last byte)
+            uint32_t pv0 = from_prev_lane(m0) >> 31, pv1 = from_prev_lane(m1) >> 31;
+            const uint32_t m0_last = lane_u32(m0, 63) >> 31;
+            if (lane == 0) {
+                pv0 = prev_blk;
+                pv1 = m0_last;
+            }
+            // (bytes outside the document are White_Space: no start needs clipping to the block's end)
+            const uint32_t S0 = m0 >> 16, S1 = m1 >> 16;
+            uint32_t st0 = ~S0 & ((S0 << 1) | pv0) & 0xFFFFu;
+            uint32_t st1 = ~S1 & ((S1 << 1) | pv1) & 0xFFFFu;
+            if (abl & 64u) {  // timing only: no queue writes, no tokens
+                my_tokens += (st0 ^ st1) & 1u;
+                st0 = 0;
+                st1 = 0;
+            }
+            my_tokens += (abl & 4u) ? (uint32_t)__builtin_popcount(st0 | (st1 << 16)) : 0u;
+            // every start gets a queue slot by ONE wave prefix sum over both counts (16 bits each: at
+            // most 512 starts per tile); tile 0's starts first
+            uint32_t pos0, pos1;
+            auto scan2 = [&](uint32_t a0, uint32_t a1) -> uint32_t {
+                const uint32_t c0 = (uint32_t)__builtin_popcount(a0), c1 = (uint32_t)__builtin_popcount(a1);
+                const uint32_t incl = wave_incl_scan(c0 | (c1 << 16));
+                const uint32_t tot = lane_u32(incl, 63);
+                pos0 = (incl & 0xFFFFu) - c0;
+                pos1 = (tot & 0xFFFFu) + (incl >> 16) - c1;
+                return (abl & 68u) ? 0u : (tot & 0xFFFFu) + (tot >> 16);
+            };
+            // the starts of segments [lo, hi) of the block
+            auto in_range = [&](uint32_t lo, uint32_t hi, uint32_t &a0, uint32_t &a1) {
+                const uint32_t g0 = (uint32_t)lane, g1 = 64u + (uint32_t)lane;
+                a0 = g0 >= lo && g0 < hi ? st0 : 0u;
+                a1 = g1 >= lo && g1 < hi ? st1 : 0u;
+            };
+            uint32_t a0 = st0, a1 = st1, seg_hi = BLK / SEG;
+            uint32_t total = scan2(a0, a1);
+            if (total > (uint32_t)QCAPB) {  // more starts than the queue holds (dense text: "a a a "):
+                seg_hi = QRANGE;            // the block is drained QRANGE segments at a time
+                in_range(0u, seg_hi, a0, a1);
+                total = scan2(a0, a1);
+            }
+            for (;;) {
+                while (a0) {
+                    const uint32_t kb = (uint32_t)__builtin_ctz(a0);
+                    a0 &= a0 - 1u;
+                    queue[pos0++] = (uint16_t)(l16 + kb);
+                }
+                while (a1) {
+                    const uint32_t kb = (uint32_t)__builtin_ctz(a1);
+                    a1 &= a1 - 1u;
+                    queue[pos1++] = (uint16_t)((uint32_t)TILE + l16 + kb);
+                }
+                MRG_PT(2);
+                const bool may_claim = table_open();
+                wave_sync_lds();
+                const uint32_t nslow = rounds(total, may_claim);
+                MRG_PT(3);
+                slow_tokens(nslow, Ab, whi, (uint32_t)(BLK / SEG));
+                if (seg_hi >= (uint32_t)(BLK / SEG)) break;
+                const uint32_t seg_lo = seg_hi;
+                seg_hi = min(seg_lo + (uint32_t)QRANGE, (uint32_t)(BLK / SEG));
+                in_range(seg_lo, seg_hi, a0, a1);
+                total = scan2(a0, a1);
+                wave_sync_lds();  // the queue's readers are done before it is filled again
+            }
+        } else {
 #pragma unroll
         for (uint32_t j = 0; j < NSUB; ++j) {
             const uint64_t At = Ab + (uint64_t)j * TILE;
@@ -1462,7 +1667,6 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
             const uint32_t mprev = m0;
             const uint64_t t1 = umin64(At + (uint64_t)TILE, doc_hi);
             const uint64_t whi = umin64(t1 + (uint64_t)HALO, doc_hi);
-            const uint64_t wbase = At - (uint64_t)BEHIND;
             // stage the tile and its 64-byte halo (the previous tile's readers are done: program order)
             wave_sync_lds();
             reinterpret_cast<uint4 *>(win)[1 + lane] = j == 0 ? X.v0 : X.v1;
@@ -1496,85 +1700,13 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
             }
             const uint32_t total = (abl & 68u) ? 0u : lane_u32(incl, 63);
             MRG_PT(2);
-            uint32_t nslow = 0;
-            // an atomic LDS load (ds_read_b32): a volatile read of the same word compiled to a FLAT
-            // load + s_waitcnt vmcnt(0), which made every tile wait for the previous tile's tail stores
-            const bool may_claim =
-                __builtin_amdgcn_readfirstlane(__hip_atomic_load(&s_fill, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) <
-                (uint32_t)CAP;
+            const bool may_claim = table_open();
             my_tokens += (abl & 4u) ? cnt : 0u;
             wave_sync_lds();
-
-            // tokens of the queue, TWO per lane per round (entries q and q + 64: two independent LDS
-            // dependency chains in one instruction stream, so each wait covers both)
-            for (uint32_t base = 0; base < total; base += 128) {
-                bool fa, sa, fb, sb;
-                uint32_t sA, sB;
-                uint64_t a0, a1, b0, b1;
-                // both queue entries first, unconditionally (entries past `total` are stale but in
-                // bounds), so the two chains share every LDS wait
-                const uint32_t qa = base + (uint32_t)lane, qb = qa + 64u;
-                const uint32_t ra = queue[min(qa, (uint32_t)QCAP - 1u)], rb = queue[min(qb, (uint32_t)QCAP - 1u)];
-                uint32_t ga = extract(qa, ra, total, fa, sa, sA, a0, a1);
-                uint32_t gb = extract(qb, rb, total, fb, sb, sB, b0, b1);
-                if (!(abl & 1024u) && __any((ga | gb) != 0u)) {
-                    squeeze(ga, a0, a1);
-                    squeeze(gb, b0, b1);
-                }
-                // slow tokens (past the 2-segment window, or > 16 raw key bytes) are deferred: their
-                // starts go to the consumed front of the queue (every lane has read both its entries,
-                // and the deferred count never exceeds the entries read so far)
-                const uint64_t ma = __ballot(sa), mb = __ballot(sb);
-                if (ma | mb) {
-                    const uint32_t ra = __builtin_amdgcn_mbcnt_hi((uint32_t)(ma >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ma, 0u));
-                    const uint32_t rb = __builtin_amdgcn_mbcnt_hi((uint32_t)(mb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mb, 0u));
-                    const uint32_t na = (uint32_t)__builtin_popcountll(ma);
-                    if (sa) queue[nslow + ra] = (uint16_t)sA;
-                    if (sb) queue[nslow + na + rb] = (uint16_t)sB;
-                    nslow += na + (uint32_t)__builtin_popcountll(mb);
-                }
-                my_tokens += (fa ? 1u : 0u) + (fb ? 1u : 0u);
-                const bool hv[2] = {fa, fb};
-                const uint64_t kk0[2] = {a0, b0}, kk1[2] = {a1, b1};
-                if constexpr (WIDE) {
-                    wide_store(A, tails, fa, a0, a1);
-                    wide_store(A, tails, fb, b0, b1);
-                } else {
-                    emit_fastN<2>(A, abl, hbits, table, tails, pool, pool16, hv, kk0, kk1, docid, may_claim);
-                }
-            }
-            // deferred slow tokens, one per lane: through the tile's masks, or (a token running past
-            // the first halo segment) the exact per-codepoint walker (forward reads only: the staged
-            // bytes are [At, whi))
+            const uint32_t nslow = rounds(total, may_claim);
             MRG_PT(3);
-            if (nslow && !(abl & 512u)) {
-                wave_sync_lds();
-                auto rd = [&](uint64_t a) -> uint32_t {
-                    if (a >= At && a < whi) return (uint32_t)win[a - wbase];
-                    return (uint32_t)gp(A.in)[a];
-                };
-                for (uint32_t base = 0; base < nslow; base += 64) {
-                    const uint32_t q = base + (uint32_t)lane;
-                    bool have = false;
-                    uint64_t tk0 = 0, tk1 = 0, a = 0;
-                    uint32_t tlen = 0, traw = 0;
-                    if (q < nslow) {
-                        const uint32_t s = queue[q];
-                        a = At + s;
-                        if (!(abl & 128u) && mask_walk(s, 64u, tk0, tk1, tlen, traw)) {
-                            have = tlen > 0;
-                        } else {
-                            uint64_t e2;
-                            if (walk_token(rd, a, doc_hi, A.counters, tk0, tk1, tlen, e2) && tlen > 0) {
-                                have = true;
-                                traw = (uint32_t)(e2 - a);
-                            }
-                        }
-                    }
-                    my_tokens += have ? 1u : 0u;
-                    emit<CAP, IDX, WIDE>(A, table, tails, have, tk0, tk1, tlen, a, traw, docid);
-                }
-            }
+            slow_tokens(nslow, At, whi, 64u);
+        }
         }
         MRG_PT(4);
     };
