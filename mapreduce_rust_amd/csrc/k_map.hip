@@ -8,9 +8,9 @@
 //
 // Layout: documents back to back in one HBM buffer; each document is cut into 2 KiB
 // blocks (two 1 KiB tiles) on a 16-byte-aligned grid.  One 16-wave workgroup per CU owns an equal
-// share of the blocks; its waves take the next block from an LDS counter (no workgroup barrier in
-// the main loop), with the next block's three 16-byte loads per lane in flight in registers (A/B
-// register sets).  The 16 waves share the workgroup's LDS combine table.
+// share of the blocks; its waves take runs of consecutive blocks from an LDS counter (no workgroup
+// barrier in the main loop), with the next block's three 16-byte loads per lane
+// in flight in registers (A/B register sets).  The 16 waves share the workgroup's LDS combine table.
 //
 // ASCII tiles (wave-uniform test) take the fast path, written for few instructions per byte:
 //   1. lane l classifies its two 16-byte segments through a 128-entry byte LUT (32 dwords, one per
@@ -870,7 +870,8 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
     __shared__ __attribute__((aligned(4))) uint8_t s_wix[WIDE ? MRG_WMAP_IXR * MRG_WIDE_IX1 : 4];
     __shared__ uint32_t s_next, s_ngen;                  // next block of the workgroup's share; list length
     __shared__ uint32_t s_stolen;                        // pool blocks this workgroup's waves have claimed
-    __shared__ uint32_t s_pool[NW][3];                   // per wave: its pool chunk [cur, end) past n_static, part | tried << 8
+    __shared__ uint32_t s_share[2];                      // the workgroup's share of the static blocks: [lo, hi)
+    __shared__ uint32_t s_pool[NW];                      // per wave: the pool part it takes from | parts tried << 8
     __shared__ uint32_t s_nuni;                          // non-ASCII tiles tokenized with UTF-8-exact masks
     // the class table's blocks for U+0000..U+07FF (2-byte codepoints: Latin-1, Latin Extended, Greek,
     // Cyrillic, ...) and U+2000..U+20FF (General Punctuation: the quotes and dashes of English text),
@@ -928,6 +929,9 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
     if (tid == 0) {
         s_next = 0;
         s_stolen = 0;
+        // (block numbers fit 32 bits: the host refuses a larger launch)
+        s_share[0] = (uint32_t)(A.n_static * blockIdx.x / gridDim.x);
+        s_share[1] = (uint32_t)(A.n_static * (blockIdx.x + 1) / gridDim.x);
         s_ngen = 0;
         s_nuni = 0;
         s_tot[0] = 0;
@@ -1020,14 +1024,14 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
         X.e = ld(lane == 0 ? 0u : 128u + (uint32_t)lane);
     };
 
-    // Work split: workgroup w owns blocks [wlo_b, whi_b) (equal shares of the first n_static); its
-    // waves take the next block from an LDS counter, so a wave that the SIMD's age-ordered issue leaves
+    // Work split: workgroup w owns blocks [s_share[0], s_share[1]) (equal shares of the first n_static); its
+    // waves take the next run of blocks from an LDS counter, so a wave that the SIMD's age-ordered issue leaves
     // behind simply takes fewer blocks (a static per-wave split left the youngest waves finishing last).
     // The blocks past n_static are a pool the waves of workgroups done with their share take from
     // (r06: workgroups ran 7.14-7.58 ms on equal shares of C3, the launch lasting as long as the
     // slowest), MRG_MAP_STEAL_K at a time from one of 8 part counters, within the workgroup's budget.
-    const uint64_t ns = A.n_static;  // blocks in equal shares (of A.n_chunks)
-    const uint64_t wlo_b = ns * blockIdx.x / gridDim.x, whi_b = ns * (blockIdx.x + 1) / gridDim.x;
+    // (the share's bounds live in LDS, s_share: a claim reads them beside its atomic, and the main loop
+    // holds no registers for them)
     // non-ASCII tiles: appended to this workgroup's list (absolute tile index: block * NSUB + tile),
     // processed after the main loop by all 16 waves
     GAS uint32_t *glist = gp(A.gbits) + (uint64_t)blockIdx.x * A.kwords;
@@ -1200,14 +1204,23 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
         return false;
     };
 
-    auto process_blk = [&](const BlkInfo &I, const Blk &X, uint64_t cblk, auto &&mid) {
+    auto process_blk = [&](const BlkInfo &I, const Blk &X, uint32_t cblk, auto &&mid) {
         const uint64_t Ab = I.Ab, doc_lo = I.doc_lo, doc_hi = I.doc_hi;
         const uint32_t docid = I.docid;
         // classify segment [B, B + 16) (relative to Ab) into W16 | S16 << 16; bytes outside the
         // document count as White_Space (exact for every staged byte: no window cut)
         const uint32_t lo_rel = doc_lo > Ab ? (uint32_t)(doc_lo - Ab) : 0u;
         const uint32_t hi_rel = (uint32_t)umin64(doc_hi - Ab, (uint64_t)(BLK + HALO));
-        auto classify = [&](const uint4 &x, uint32_t B) -> uint32_t {
+        // A block that lies inside its document with its halo (all but about two blocks per document)
+        // has no such byte: `edge` is wave-uniform, and only an edge block pays for the masks
+        const bool edge = lo_rel != 0u || hi_rel != (uint32_t)(BLK + HALO);
+        auto clip = [&](uint32_t m, uint32_t B) -> uint32_t {
+            const uint32_t lo_inv = lo_rel > B ? min(lo_rel - B, 16u) : 0u;
+            const uint32_t hi_ok = B < hi_rel ? min(hi_rel - B, 16u) : 0u;
+            const uint32_t valid = ((1u << hi_ok) - 1u) & ~((1u << lo_inv) - 1u);
+            return (m & (valid | (valid << 16))) | ((~valid & 0xFFFFu) << 16);
+        };
+        auto classify = [&](const uint4 &x) -> uint32_t {
             // all 16 lookups in flight before the first use (one LDS wait per segment); byte b of a
             // dword reads table b, whose entries are already shifted to bit b (W) and 4 + b (S)
             uint32_t e[16];
@@ -1226,15 +1239,11 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
             const uint32_t y = (yk[0] | (yk[1] << 8)) | ((yk[2] | (yk[3] << 8)) << 16);
             const uint32_t t = y & 0x0F0F0F0Fu, u = (y >> 4) & 0x0F0F0F0Fu;
             // bytes 0 and 2 of t | t >> 4: W of bytes 0-7 and 8-15 (u: S)
-            const uint32_t m = __builtin_amdgcn_perm(u | (u >> 4), t | (t >> 4), 0x06040200u);  // W16 | S16 << 16
-            const uint32_t lo_inv = lo_rel > B ? min(lo_rel - B, 16u) : 0u;
-            const uint32_t hi_ok = B < hi_rel ? min(hi_rel - B, 16u) : 0u;
-            const uint32_t valid = ((1u << hi_ok) - 1u) & ~((1u << lo_inv) - 1u);
-            return (m & (valid | (valid << 16))) | ((~valid & 0xFFFFu) << 16);
+            return __builtin_amdgcn_perm(u | (u >> 4), t | (t >> 4), 0x06040200u);  // W16 | S16 << 16
         };
         auto na = [](const uint4 &x) { return ((x.x | x.y | x.z | x.w) & 0x80808080u) != 0u; };
         const uint32_t l16 = (uint32_t)lane * SEG;
-        uint32_t m0 = classify(X.v0, l16), m1 = classify(X.v1, 1024u + l16);
+        uint32_t m0 = classify(X.v0), m1 = classify(X.v1);
         // the first halo segment (lane 1's e) by 16 lanes, one byte each, through two ballots
         uint32_t mh;
         {
@@ -1243,10 +1252,14 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
             const uint32_t k = (uint32_t)lane & 15u;
             const uint32_t dwv = k < 8u ? (k < 4u ? e0 : e1) : (k < 12u ? e2 : e3);
             const uint32_t cl = s_lut[0][__builtin_amdgcn_ubfe(dwv, 8u * (k & 3u), 8)];
-            const bool in = (uint32_t)BLK + k < hi_rel;  // bytes past the document are White_Space
-            const uint32_t wm = (uint32_t)__ballot(lane < 16 && in && (cl & 1u));
-            const uint32_t sm = (uint32_t)__ballot(lane < 16 && (!in || (cl & 0x10u)));
+            const uint32_t wm = (uint32_t)__ballot(lane < 16 && (cl & 1u));
+            const uint32_t sm = (uint32_t)__ballot(lane < 16 && (cl & 0x10u));
             mh = (wm & 0xFFFFu) | (sm << 16);
+        }
+        if (edge) {  // bytes before and past the document are White_Space
+            m0 = clip(m0, l16);
+            m1 = clip(m1, 1024u + l16);
+            mh = clip(mh, (uint32_t)BLK);
         }
         const bool n0 = na(X.v0), n1 = na(X.v1), ne = na(X.e);
         // class of the byte before the block (lane 0's e, byte 15)
@@ -1374,13 +1387,17 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
                         }
                         wave_sync_lds();
                         if ((uint32_t)lane < T) {
-                            const uint64_t s = slot[lane];
+                            // (the slot's address is formed here: hoisted out of the main loop it held a
+                            // VGPR the kernel does not have, and was spilled to scratch)
+                            uint32_t ln = (uint32_t)lane;
+                            asm volatile("" : "+v"(ln));
+                            const uint64_t s = slot[ln];
                             const uint32_t sw = (uint32_t)s;
                             auto rd = [&](uint64_t x) -> uint32_t { return (sw >> (8u * (uint32_t)x)) & 0xFFu; };
                             uint32_t cp = 0, raw;
                             const uint32_t n = (uint32_t)mrg_utf8_decode(rd, 0ull, s >> 32, &cp, &raw);
                             const uint32_t cl = uni_class(uc, cp);
-                            ((LDS uint32_t *)slot)[2 * lane] =
+                            ((LDS uint32_t *)slot)[2 * ln] =
                                 n | (cl == MRG_CLS_W ? 8u : 0u) | (cl == MRG_CLS_S ? 16u : 0u);
                         }
                         wave_sync_lds();
@@ -1485,8 +1502,10 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
         if (defer_blk) {  // recorded; processed after the main loop
             if (lane == 0) {
                 for (uint32_t j = 0; j < NSUB && Ab + (uint64_t)j * TILE < doc_hi; ++j) {
+                    // (a list is sized for every tile the workgroup can map: an entry past it is
+                    // counted, not written, and the launch is rerun with longer lists)
                     const uint32_t k = atomicAdd(&s_ngen, 1u);
-                    glist[k] = (uint32_t)(cblk * NSUB + j);
+                    if (k < A.kwords) glist[k] = (uint32_t)(cblk * NSUB + j);
                 }
             }
             return;
@@ -1714,33 +1733,36 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
     // Main loop: two register sets, A and B.  Block c's loads were issued one block earlier; the
     // next block's loads go out before c is processed, so exactly five loads are younger than c's
     // when its data is first used.  Past the end, the "next" block is a reload of the current one.
-    // the wave's pool state lives in LDS (s_pool[wv]): registers held across the main loop would add
-    // to the kernel's SGPR spills; it is touched once per block
-    constexpr uint64_t NONE = ~0ull;
+    // A wave claims a RUN of consecutive blocks at a time and walks it without another atomic: the run
+    // [run_cur, run_end) (absolute block numbers, two SGPRs) comes from the workgroup's share (A.run
+    // blocks per LDS atomic; 1 = a block per claim, as before runs) or from the pool (MRG_MAP_STEAL_K
+    // blocks per device atomic); both sources fill the same pair.  The pool part a wave is at stays in
+    // LDS (s_pool[wv]): it is touched once per pool claim.
+    constexpr uint32_t NONE = ~0u;
     uint32_t dcur = 0;
-    if (lane == 0) {
-        s_pool[wv][0] = 0;
-        s_pool[wv][1] = 0;
-        s_pool[wv][2] = (blockIdx.x & 7u) | ((A.n_static < A.n_chunks ? 0u : 8u) << 8);
-    }
-    auto grab = [&]() -> uint64_t {
+    uint32_t run_cur = 0, run_end = 0;
+    if (lane == 0) s_pool[wv] = (blockIdx.x & 7u) | ((A.n_static < A.n_chunks ? 0u : 8u) << 8);
+    auto grab = [&]() -> uint32_t {
+        if (run_cur < run_end) return run_cur++;
+        const uint32_t R = max(A.run, 1u);
         uint32_t r = 0;
-        if (lane == 0) r = atomicAdd(&s_next, 1u);
-        const uint64_t c0 = wlo_b + (uint64_t)first_u32(r);
-        if (c0 < whi_b) return c0;
+        if (lane == 0) r = atomicAdd(&s_next, R);
+        const uint32_t whi_b = first_u32(s_share[1]);
+        const uint64_t c0 = (uint64_t)first_u32(s_share[0]) + (uint64_t)first_u32(r);
+        if (c0 < (uint64_t)whi_b) {
+            run_cur = (uint32_t)c0 + 1u;
+            run_end = (uint32_t)umin64(c0 + R, (uint64_t)whi_b);
+            return (uint32_t)c0;
+        }
         const uint64_t ns2 = A.n_static, np = A.n_chunks - ns2;   // (re-read: not held in registers)
         wave_sync_lds();
-        const uint32_t cur = first_u32(s_pool[wv][0]), end = first_u32(s_pool[wv][1]);
-        if (cur < end) {
-            if (lane == 0) s_pool[wv][0] = cur + 1u;
-            return ns2 + cur;
-        }
-        uint32_t pt = first_u32(s_pool[wv][2]);
+        uint32_t pt = first_u32(s_pool[wv]);
         while ((pt >> 8) < 8u) {
             const uint32_t part = pt & 7u;
             uint32_t k = 0;
             if (lane == 0) k = atomicAdd(&s_stolen, (uint32_t)MRG_MAP_STEAL_K);
-            if (first_u32(k) >= A.steal_max) {  // this workgroup's budget is spent
+            // a claim takes up to MRG_MAP_STEAL_K blocks: all of them must fit the workgroup's budget
+            if (first_u32(k) + (uint32_t)MRG_MAP_STEAL_K > A.steal_max) {  // the budget is spent
                 pt = 8u << 8;
                 break;
             }
@@ -1749,22 +1771,33 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
             if (lane == 0) q = atomicAdd(&A.pool_ctr[16u * part], (unsigned long long)MRG_MAP_STEAL_K);
             const uint32_t at = plo + first_u32((uint32_t)umin64(q, 0xFFFFFFFFull));
             if (at < phi) {
-                if (lane == 0) {
-                    s_pool[wv][0] = at + 1u;
-                    s_pool[wv][1] = min(phi, at + (uint32_t)MRG_MAP_STEAL_K);
-                    s_pool[wv][2] = pt;
-                }
+                if (lane == 0) s_pool[wv] = pt;
+                run_cur = (uint32_t)ns2 + at + 1u;
+                run_end = (uint32_t)ns2 + min(phi, at + (uint32_t)MRG_MAP_STEAL_K);
                 // the document cursor walks forward (locate_blk); a search only when the chunk lies before
                 // it (the wrap from part 7 to part 0)
                 if (cp(A.chunk_base)[dcur] > ns2 + at) dcur = find_doc(A, ns2 + at);
-                return ns2 + at;
+                return (uint32_t)ns2 + at;
             }
             pt = ((pt & 7u) + 1u) % 8u | (((pt >> 8) + 1u) << 8);
         }
-        if (lane == 0) s_pool[wv][2] = pt;
+        if (lane == 0) s_pool[wv] = pt;
         return NONE;
     };
-    uint64_t c = grab();
+    // The block after `P` (block cp_ of the job) when the wave's next block cn is the next 2 KiB of the
+    // same document (nearly always: a run's blocks are consecutive): its bounds follow from P's, with
+    // no table lookup.  Block cp_ + 1 belongs to P's document exactly when it starts before the
+    // document's end (mrg_map_tiles).  dcur then lags behind; locate_blk walks it forward when needed.
+    auto next_blk = [&](const BlkInfo &P, uint32_t cp_, uint32_t cn) -> BlkInfo {
+        if (cn != cp_ + 1u || P.Ab + (uint64_t)BLK >= P.doc_hi) return locate_blk(A, cn, dcur);
+        BlkInfo b = P;
+        b.Ab = P.Ab + (uint64_t)BLK;
+        const uint64_t whi = umin64(b.Ab + (uint64_t)(BLK + HALO), b.doc_hi);
+        b.v0 = 0u;  // the 16 bytes before it are the previous block's
+        b.v1 = (uint32_t)((((whi + 15u) & ~15ull) - (b.Ab - (uint64_t)BEHIND)) >> 4);
+        return b;
+    };
+    uint32_t c = grab();
     if (c != NONE) dcur = find_doc(A, c);
     Blk XA, XB;
     BlkInfo IA{}, IB{};
@@ -1784,14 +1817,14 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
         settle(XA);
     }
     while (c != NONE) {
-        const uint64_t cB = grab();
-        IB = cB != NONE ? locate_blk(A, cB, dcur) : IA;
+        const uint32_t cB = grab();
+        IB = cB != NONE ? next_blk(IA, c, cB) : IA;
         load_blk(IB, XB);
         process_blk(IA, XA, c, [&]() { settle(XB); });
         c = cB;
         if (c == NONE) break;
-        const uint64_t cA = grab();
-        IA = cA != NONE ? locate_blk(A, cA, dcur) : IB;
+        const uint32_t cA = grab();
+        IA = cA != NONE ? next_blk(IB, c, cA) : IB;
         load_blk(IA, XA);
         process_blk(IB, XB, c, [&]() { settle(XA); });
         c = cA;
@@ -1807,7 +1840,7 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
     lds_only_barrier();   // s_ngen final
     if (s_ngen) __syncthreads();  // (uniform) the list is complete: its global writes, then the barrier
     {
-        const uint32_t ng = s_ngen;
+        const uint32_t ng = min(s_ngen, A.kwords);
         for (uint32_t i = (uint32_t)wv; i < ng; i += NW) {
             {
                 const uint32_t kk = first_u32(glist[i]);
@@ -1913,6 +1946,7 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
         g_add(&A.counters[CNT_REC], (unsigned long long)s_tot[1]);
         if (s_tot[2]) g_add(&A.counters[CNT_REC16], (unsigned long long)s_tot[2]);
         if (s_ngen + s_nuni) g_add(&A.counters[CNT_NONASCII], (unsigned long long)(s_ngen + s_nuni));
+        if (s_ngen > A.kwords) g_add(&A.counters[CNT_OVF], (unsigned long long)(s_ngen - A.kwords));  // tiles not listed
         gp(A.lcount)[blockIdx.x] = s_lcnt;
         if (s_lcnt) g_add(&A.counters[CNT_LONG], (unsigned long long)s_lcnt);
     }

@@ -92,7 +92,7 @@ struct MapArgs {
     // non-ASCII tiles, recorded by the main loop and processed after it: workgroup g appends the
     // index of each such tile (block * NSUB + tile, absolute) to gbits[g * kwords ..)
     uint32_t *gbits;
-    uint32_t kwords;             // list capacity per workgroup (tiles of its share + its steal budget)
+    uint32_t kwords;             // list capacity per workgroup (tiles of its share + its steal budget); bounds the appends
     unsigned long long *counters;
     uint32_t hash_bits;          // 0 = full; else truncate internal hashes (collision test knob)
     uint32_t ablate;             // perf diagnostics only (env MRG_ABLATE; results are WRONG when set):
@@ -125,10 +125,14 @@ struct MapArgs {
     // load balance (mrgpu.cpp map_steal): blocks [0, n_static) are split into
     // equal workgroup shares; blocks [n_static, n_chunks) are a pool in 8 parts, part j's next block at
     // pool_ctr[16 * j] (zeroed per launch), that a wave takes MRG_MAP_STEAL_K blocks at a time once its
-    // workgroup's share is done, at most steal_max blocks per workgroup (the per-workgroup capacities
-    // are sized for share + steal_max).  n_static = n_chunks: static shares only.
+    // workgroup's share is done, at most steal_max blocks per workgroup: a claim that would pass the
+    // budget is not made (the per-workgroup capacities are sized for share + steal_max + one claim).
+    // n_static = n_chunks: static shares only.  run: consecutive blocks of its workgroup's share a wave
+    // claims per LDS atomic (MRG_MAP_RUN where a share is long enough, else shorter: mrgpu.cpp map_steal;
+    // 1 = one block per claim).
     uint64_t n_static;
     uint32_t steal_max;
+    uint32_t run;
     unsigned long long *pool_ctr;
 };
 // One staged small write of a job's setup (mrgpu.cpp stage_h2d / stage_fill): `n` bytes to `dst`, from
@@ -143,6 +147,9 @@ void mrg_launch_stage_scatter(const uint8_t *d_stage, uint32_t table_off, uint32
 
 #ifndef MRG_MAP_STEAL_K
 #define MRG_MAP_STEAL_K 4        // blocks a wave takes from the pool at a time
+#endif
+#ifndef MRG_MAP_RUN
+#define MRG_MAP_RUN 4            // blocks of its workgroup's share a wave claims at a time (env MRG_MAP_RUN)
 #endif
 #define MRG_WMAP_MAXB1 4096      // L1 buckets the wide map's LDS cursors hold
 #define MRG_WIDE_IX1 260         // bytes of one partition's L1 splitter index (257 entries + prefix bits)

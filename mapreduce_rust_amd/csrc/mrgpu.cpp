@@ -937,12 +937,19 @@ WideMapPlan wide_map_plan(mrg_ctx *c, Scratch &keep, const uint64_t *d_doc_off, 
 struct MapSteal {
     uint64_t n_static = 0;     // blocks in equal shares
     uint32_t steal_max = 0;    // pool blocks one workgroup may take
+    uint32_t run = 1;          // blocks of its share a wave claims at a time (MRG_MAP_RUN)
     uint64_t per_wg_blocks = 0;
     double wg_scale = 1.0;
 };
 MapSteal map_steal(uint64_t n_chunks, int grid) {
     MapSteal m;
     const uint64_t g = (uint64_t)std::max(grid, 1);
+    // runs of MRG_MAP_RUN blocks where every wave of a workgroup still gets four of them; a smaller share in
+    // shorter runs, down to single blocks (a 4 MB job has 8 blocks per workgroup: runs of 4 would leave 14 of
+    // its 16 waves idle).  MRG_MAP_RUN in the environment is taken as it stands.
+    const uint64_t share = n_chunks / g;
+    m.run = (uint32_t)std::max<uint64_t>(std::min<uint64_t>(MRG_MAP_RUN, share / (4 * MRG_MAP_WAVES)), 1);
+    if (getenv("MRG_MAP_RUN")) m.run = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(env_u64("MRG_MAP_RUN", 1), 1), 64);
     const uint64_t div = env_u64("MRG_MAP_STEAL", 16);  // the pool is 1/div of the blocks (0: no pool)
     const uint64_t pool = div ? n_chunks / div : 0;
     if (pool == 0 || pool < env_u64("MRG_TEST_STEAL_MIN", 64 * g)) {  // nothing worth balancing (tests: any pool)
@@ -952,7 +959,8 @@ MapSteal map_steal(uint64_t n_chunks, int grid) {
     }
     m.n_static = n_chunks - pool;
     m.steal_max = (uint32_t)(2 * pool / g + 1024);
-    m.per_wg_blocks = (m.n_static + g - 1) / g + 1 + m.steal_max;
+    // share + budget + one claim (the kernel refuses a claim that would pass the budget: the last term is slack)
+    m.per_wg_blocks = (m.n_static + g - 1) / g + 1 + m.steal_max + std::max<uint64_t>(m.run, MRG_MAP_STEAL_K);
     m.wg_scale = (double)m.per_wg_blocks / ((double)n_chunks / (double)g);
     return m;
 }
@@ -975,6 +983,7 @@ void set_steal(mrg_ctx *c, Scratch &att, MapArgs &A, const MapSteal &ms, uint64_
     if (n_chunks * MRG_MAP_NSUB >= 0xFFFFFFFFull) raise(MRG_ENOMEM, "input too large for one map launch");
     A.n_static = ms.n_static;
     A.steal_max = ms.steal_max;
+    A.run = ms.run;
     A.pool_ctr = nullptr;
     if (ms.n_static < n_chunks) {
         A.pool_ctr = att.get<unsigned long long>(8 * 16);
@@ -986,9 +995,11 @@ void set_steal(mrg_ctx *c, Scratch &att, MapArgs &A, const MapSteal &ms, uint64_
 // records per workgroup + a shared list of lovf), the non-ASCII tile lists (one entry per tile of a
 // workgroup's share and steal budget at most) and the steal plan.  Returns the long-token slots.
 // knobs: MRG_TEST_LONG_PER / MRG_TEST_LONG_LIST apply (the LDS-combine map's first launch only: a
-// rerun grows the regions from the measured demand).
+// rerun grows the regions from the measured demand).  attempt: the launches of this map so far; a tile
+// list is sized for every tile its workgroup can map, and a rerun (whatever overflowed) lengthens it
+// (MRG_TEST_KWORDS: the first launch's list capacity, to reach that path).
 uint64_t map_args_shared(mrg_ctx *c, Scratch &att, MapArgs &A, const MapIn &in, const MapSteal &ms, uint64_t lcap,
-                         bool knobs) {
+                         bool knobs, uint32_t attempt) {
     A.in = c->d_in;
     A.doc_off = in.doc_off;
     A.chunk_base = in.chunk_base;
@@ -1011,7 +1022,10 @@ uint64_t map_args_shared(mrg_ctx *c, Scratch &att, MapArgs &A, const MapIn &in, 
     A.lcount = att.get<uint32_t>((uint64_t)in.grid);
     A.lper = (uint32_t)lper;
     A.lovf = lovf;
-    A.kwords = (uint32_t)(MRG_MAP_NSUB * ms.per_wg_blocks);
+    uint64_t kwords = MRG_MAP_NSUB * ms.per_wg_blocks * (1 + (uint64_t)std::min(attempt, 7u));
+    if (attempt == 0) kwords = env_u64("MRG_TEST_KWORDS", kwords);
+    if (kwords > 0xFFFFFFF0ull) raise(MRG_ENOMEM, "input too large for one map launch");
+    A.kwords = (uint32_t)kwords;
     A.gbits = att.get<uint32_t>((uint64_t)in.grid * A.kwords);
     set_steal(c, att, A, ms, in.n_chunks);
     return lslots;
@@ -1091,7 +1105,7 @@ void job_map_wide(mrg_ctx *c, Scratch &sc, const WideMapPlan &wp, const MapIn &i
         if (wcap > 0xFFFFFFF0ull) raise(MRG_ENOMEM, "input too large for one map launch");
         MapArgs *dargs = att.get<MapArgs>(1);
         A = MapArgs{};
-        map_args_shared(c, att, A, in, ms, lcap, false);
+        map_args_shared(c, att, A, in, ms, lcap, false, launches);
         const uint64_t nslots = (uint64_t)B1 * grid * wcap;
         A.wrec = att.get<uint64_t>(w12 ? (12 * nslots + 16 + 7) / 8 : 2 * nslots + 2);
         A.wcnt = att.get<uint32_t>((uint64_t)B1 * grid);
@@ -1294,7 +1308,7 @@ void job_map(mrg_ctx *c) {
         A.fcnt = att.get<uint32_t>((uint64_t)grid * cap);
         A.fdoc = idx ? att.get<uint32_t>((uint64_t)grid * cap) : nullptr;
         A.foff = att.get<uint32_t>((uint64_t)grid * (MRG_NBUCKET + 1));
-        const uint64_t lslots = map_args_shared(c, att, A, in, ms, lcap, launches == 0);
+        const uint64_t lslots = map_args_shared(c, att, A, in, ms, lcap, launches == 0, launches);
         A.ablate = getenv("MRG_ABLATE") ? (uint32_t)atoi(getenv("MRG_ABLATE")) : 0u;
         A.prof = nullptr;
         if (getenv("MRG_PROF")) {
