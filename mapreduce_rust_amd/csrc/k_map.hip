@@ -393,10 +393,18 @@ __device__ __forceinline__ bool walk_token(const RD &rd, uint64_t a, uint64_t do
     return true;
 }
 
-// Tail regions of this workgroup, one per hash bucket b: cur[b] = the pool record index of the next
-// append (starts at the region's first record), end[b] = one past the region's last record.  An
-// append is ONE 64-bit LDS atomic that returns the record index itself, and the end is read beside
-// it (it does not depend on the atomic), so a tail token costs one LDS round trip before its store.
+// Tail regions of this workgroup, one per hash bucket b and record class.  Two forms, chosen by the
+// host per launch (mrgpu.cpp map_tail_packed) and compiled as the kernel's T64 flag:
+//   packed (T64 = false): cur[b] is ONE word per (bucket, class): low 32 bits = the pool record index
+//     of the next append (starts at the region's first record), high 32 bits = one past the region's
+//     last record.  An append is one 64-bit LDS add of 0 or 1 that returns index and end together;
+//     the capacity test is a 32-bit compare and the record's address one 32 x 32 -> 64 multiply-add.
+//     The index keeps counting past a full region (the host sizes a rerun from it), so the form is
+//     valid only while no low word can carry into its end: every index of the launch, plus the appends
+//     one workgroup can make, stays below 2^32.  end / end16 are unused (null).
+//   64-bit (T64 = true): cur[b] = the next record index, end[b] = one past the region's last record,
+//     both 64-bit; the end is read beside the atomic (it does not depend on it).
+// Either way a tail token costs one LDS round trip before its store.
 struct TailRegions {
     unsigned long long *cur;
     const unsigned long long *end;
@@ -482,10 +490,60 @@ __device__ __forceinline__ void store_tail(GAS uint64_t *pool, GAS uint64_t *poo
     }
 }
 
+// "The key has 13..16 bytes": the low word of k1 tested as a 32-bit value of its own.  (The plain cast is
+// widened back by the compiler to a 64-bit compare of the zero-extended word, which costs a move, two
+// compares and a held zero register per token; the empty asm makes the word opaque to that.)
+__device__ __forceinline__ bool key_over12(uint64_t k1) {
+    uint32_t lo = (uint32_t)k1;
+    asm("" : "+v"(lo));
+    return lo != 0u;
+}
+
+// The packed form's stores (TailRegions): the record's address from a 32-bit index, one multiply-add
+template <bool IDX>
+__device__ __forceinline__ void store_tail32(GAS uint64_t *pool, uint32_t i, uint64_t k0, uint64_t k1, uint32_t doc) {
+    GAS uint8_t *dst = reinterpret_cast<GAS uint8_t *>(pool) + (uint64_t)i * MRG_TAIL_BYTES(IDX);
+    if (IDX) {
+        reinterpret_cast<GAS uint64_t *>(dst)[0] = k0;
+        reinterpret_cast<GAS uint64_t *>(dst)[1] = k1;
+        reinterpret_cast<GAS uint64_t *>(dst)[2] = doc;
+    } else {
+        *reinterpret_cast<GAS u32x3a *>(dst) = u32x3a{(uint32_t)k0, (uint32_t)(k0 >> 32), (uint32_t)(k1 >> 32)};
+    }
+}
+__device__ __forceinline__ void store_tail32_16(GAS uint64_t *pool16, uint32_t i, uint64_t k0, uint64_t k1) {
+    *reinterpret_cast<GAS u64x2 *>(reinterpret_cast<GAS uint8_t *>(pool16) + (uint64_t)i * 16u) = u64x2{k0, k1};
+}
+
+// A record whose region is full (rare): the bucket's shared overflow list (16-byte records for any wc
+// key, the indexer's 24); a full list is counted, and the host reruns the launch
+template <bool IDX>
+__device__ __forceinline__ void ovf_append(const MapArgs &A, uint32_t b, uint64_t k0, uint64_t k1, uint32_t docid) {
+    const uint32_t j = g_add(&A.onext[b], 1u);
+    if (j < A.ocap) {
+        GAS uint64_t *dst = gp(A.ovf) + ((uint64_t)b * A.ocap + j) * (IDX ? 3u : 2u);
+        dst[0] = k0;
+        dst[1] = k1;
+        if (IDX) dst[2] = docid;
+    } else {
+        g_add(&A.counters[CNT_OVF], 1ull);
+    }
+}
+
+// The packed form's append to a 16-byte region, off the token round (wc keys of 13..16 bytes are rare
+// in text): the cursor add, the store, and the overflow list when the region is full
+__device__ __forceinline__ void tail16_append(const MapArgs &A, const TailRegions &R, GAS uint64_t *pool16, uint32_t b,
+                                              uint64_t k0, uint64_t k1) {
+    const uint64_t ce = atomicAdd(&R.cur16[b], 1ull);
+    const uint32_t i = (uint32_t)ce;
+    if (i < (uint32_t)(ce >> 32)) store_tail32_16(pool16, i, k0, k1);
+    else ovf_append<false>(A, b, k0, k1, 0u);
+}
+
 // N tokens per lane through the LDS table in one instruction stream: the set reads, count adds and
 // tail-cursor adds of all N are issued back to back, so every LDS round trip is paid once for N
 // independent chains.  Same semantics as emit() applied to token 0, then 1, ...
-template <int N, int CAP, bool IDX>
+template <int N, int CAP, bool IDX, bool T64>
 __device__ __forceinline__ void emit_fastN(const MapArgs &A, uint32_t abl, uint32_t hbits, LdsTable<CAP, IDX> &T,
                                            TailRegions R, GAS uint64_t *pool, GAS uint64_t *pool16,
                                            const bool (&has)[N], const uint64_t (&k0)[N], const uint64_t (&k1)[N],
@@ -495,7 +553,7 @@ __device__ __forceinline__ void emit_fastN(const MapArgs &A, uint32_t abl, uint3
     uint32_t h[N], s[N], b[N];
     bool act[N], w16[N], hit[N], m0[N];
     KeyPair kw0[N], kw1[N];
-    uint64_t end[N];
+    uint64_t end[N];  // T64 only
 #pragma unroll
     for (int t = 0; t < N; ++t) {
         h[t] = key_hash(k0[t], k1[t], dkey, hbits);
@@ -565,14 +623,15 @@ __device__ __forceinline__ void emit_fastN(const MapArgs &A, uint32_t abl, uint3
     for (int t = 0; t < N; ++t) {
         s[t] = act[t] ? (h[t] & (NS - 1)) : 0u;
         b[t] = bucket_of(h[t]);
-        w16[t] = !IDX && (uint32_t)k1[t] != 0u;  // wc keys of 13..16 bytes: the 16-byte regions
+        // wc keys of 13..16 bytes (the low word of k1, as a 32-bit value): the 16-byte regions
+        w16[t] = !IDX && (T64 ? (uint32_t)k1[t] != 0u : key_over12(k1[t]));
     }
-    // both ways of every set: 2N 16-byte reads in flight together, with the region ends
+    // both ways of every set: 2N 16-byte reads in flight together (T64: with the region ends)
 #pragma unroll
     for (int t = 0; t < N; ++t) {
         kw0[t] = T.key[s[t]];
         kw1[t] = T.key[s[t] + NS];
-        end[t] = (w16[t] ? R.end16 : R.end)[b[t]];
+        if constexpr (T64) end[t] = (w16[t] ? R.end16 : R.end)[b[t]];
     }
 #pragma unroll
     for (int t = 0; t < N; ++t) {
@@ -625,12 +684,52 @@ __device__ __forceinline__ void emit_fastN(const MapArgs &A, uint32_t abl, uint3
             if (grp[t] == (uint32_t)g) hit[t] = lh != 0u;
     }
 #endif
-    bool tl[N], anyt = false;
+    bool tl[N];
 #pragma unroll
-    for (int t = 0; t < N; ++t) {
-        tl[t] = has[t] && !hit[t] && !(abl & 1u);
-        anyt = anyt || tl[t];
-    }
+    for (int t = 0; t < N; ++t) tl[t] = has[t] && !hit[t] && !(abl & 1u);
+    if constexpr (!T64) {
+        // packed cursors: the round appends to the 12-byte class only (the indexer's one class); a key
+        // of 13..16 bytes goes through the cold block below.  Every token's append in one LDS round
+        // trip (a lane adds 0 for a token that hit): the add returns the record index and the
+        // region's end together
+        bool hot[N], anyt = false;
+#pragma unroll
+        for (int t = 0; t < N; ++t) {
+            hot[t] = tl[t] && !w16[t];
+            anyt = anyt || hot[t];
+        }
+        uint64_t ce[N];
+        if (anyt) {
+#pragma unroll
+            for (int t = 0; t < N; ++t) ce[t] = atomicAdd(&R.cur[b[t]], hot[t] ? 1ull : 0ull);
+        } else {
+#pragma unroll
+            for (int t = 0; t < N; ++t) ce[t] = 0;
+        }
+        // one wave-uniform test for everything rare: a full region (the bucket's shared overflow list)
+        // and, wc, a key of 13..16 bytes (the cold append; the order of appends within a region matters
+        // to no reader).  A stored token is a hot one and a hot one a tail token, so "a tail token, not
+        // stored" is exactly those two.
+        bool rare = false, ok[N];
+#pragma unroll
+        for (int t = 0; t < N; ++t) {
+            const uint32_t i = (uint32_t)ce[t];
+            ok[t] = hot[t] && i < (uint32_t)(ce[t] >> 32);
+            if (ok[t]) store_tail32<IDX>(pool, i, k0[t], k1[t], docid);
+            rare = rare || (tl[t] != ok[t]);
+        }
+        if (__any(rare)) {
+#pragma unroll
+            for (int t = 0; t < N; ++t) {
+                if (hot[t] && !ok[t]) ovf_append<IDX>(A, b[t], k0[t], k1[t], docid);
+                if constexpr (!IDX)
+                    if (tl[t] && !hot[t]) tail16_append(A, R, pool16, b[t], k0[t], k1[t]);
+            }
+        }
+    } else {
+    bool anyt = false;
+#pragma unroll
+    for (int t = 0; t < N; ++t) anyt = anyt || tl[t];
     // every token's append in one LDS round trip (a lane adds 0 for a token that hit)
     uint64_t idx[N];
     if (anyt) {
@@ -650,25 +749,16 @@ __device__ __forceinline__ void emit_fastN(const MapArgs &A, uint32_t abl, uint3
     }
     if (__any(anyo)) {  // region full (rare): the bucket's shared overflow list
 #pragma unroll
-        for (int t = 0; t < N; ++t) {
-            if (!ovf[t]) continue;
-            const uint32_t j = g_add(&A.onext[b[t]], 1u);
-            if (j < A.ocap) {
-                GAS uint64_t *dst = gp(A.ovf) + ((uint64_t)b[t] * A.ocap + j) * (IDX ? 3u : 2u);
-                dst[0] = k0[t];
-                dst[1] = k1[t];
-                if (IDX) dst[2] = docid;
-            } else {
-                g_add(&A.counters[CNT_OVF], 1ull);
-            }
-        }
+        for (int t = 0; t < N; ++t)
+            if (ovf[t]) ovf_append<IDX>(A, b[t], k0[t], k1[t], docid);
+    }
     }
 }
 
 // One round of token emission by a whole wave (all 64 lanes call it): LDS-table insert of short
 // keys; a miss is appended to its hash bucket's region of this workgroup (an LDS counter per
 // bucket, no HBM atomics).  Long keys become long-token records.
-template <int CAP, bool IDX, bool WIDE>
+template <int CAP, bool IDX, bool WIDE, bool T64>
 __device__ __forceinline__ void emit(const MapArgs &A, LdsTable<CAP, IDX> &table, TailRegions R, bool have,
                                      uint64_t tk0, uint64_t tk1, uint32_t tlen, uint64_t tstart, uint32_t traw,
                                      uint32_t docid) {
@@ -688,21 +778,21 @@ __device__ __forceinline__ void emit(const MapArgs &A, LdsTable<CAP, IDX> &table
     }
     if (tail && !(map_ablate(A) & 1u)) {
         const uint32_t b = bucket_of(h);
-        const bool w16 = !IDX && (uint32_t)tk1 != 0u;
+        const bool w16 = !IDX && (T64 ? (uint32_t)tk1 != 0u : key_over12(tk1));
+        if constexpr (!T64) {  // packed cursors: index and end in one word (see TailRegions)
+            if (w16) {
+                tail16_append(A, R, gp(A.pool16), b, tk0, tk1);
+            } else {
+                const uint64_t ce = atomicAdd(&R.cur[b], 1ull);
+                const uint32_t i = (uint32_t)ce;
+                if (i < (uint32_t)(ce >> 32)) store_tail32<IDX>(gp(A.pool), i, tk0, tk1, docid);
+                else ovf_append<IDX>(A, b, tk0, tk1, docid);  // region full (rare)
+            }
+        } else {
         const uint64_t end = (w16 ? R.end16 : R.end)[b];
         const uint64_t idx = atomicAdd(&(w16 ? R.cur16 : R.cur)[b], 1ull);
-        if (idx < end) {
-            store_tail<IDX>(gp(A.pool), gp(A.pool16), w16, idx, tk0, tk1, docid);
-        } else {  // region full (rare): the bucket's shared overflow list (16-byte records, any key)
-            const uint32_t j = g_add(&A.onext[b], 1u);
-            if (j < A.ocap) {
-                GAS uint64_t *dst = gp(A.ovf) + ((uint64_t)b * A.ocap + j) * (IDX ? 3u : 2u);
-                dst[0] = tk0;
-                dst[1] = tk1;
-                if (IDX) dst[2] = docid;
-            } else {
-                g_add(&A.counters[CNT_OVF], 1ull);
-            }
+        if (idx < end) store_tail<IDX>(gp(A.pool), gp(A.pool16), w16, idx, tk0, tk1, docid);
+        else ovf_append<IDX>(A, b, tk0, tk1, docid);  // region full (rare): the bucket's shared overflow list
         }
     }
     }
@@ -738,7 +828,7 @@ __device__ __forceinline__ void emit(const MapArgs &A, LdsTable<CAP, IDX> &table
 // decode + two-level class table), one token per lane per emission round.  Called after the main
 // loop (the main loop only records which tiles need it), so its registers never add to the hot
 // loop's.
-template <int CAP, bool IDX, bool WIDE>
+template <int CAP, bool IDX, bool WIDE, bool T64>
 __device__ __forceinline__ uint32_t generic_tile(const MapArgs &A, LdsTable<CAP, IDX> table, TailRegions R,
                                               const uint8_t *win, uint64_t At, uint64_t t0, uint64_t t1,
                                               uint64_t doc_lo, uint64_t doc_hi, uint64_t wlo, uint64_t whi,
@@ -811,7 +901,7 @@ __device__ __forceinline__ uint32_t generic_tile(const MapArgs &A, LdsTable<CAP,
             }
             if (!__any(have)) break;
             my_tokens += have ? 1u : 0u;
-            emit<CAP, IDX, WIDE>(A, table, R, have, tk0, tk1, tlen, tstart, traw, docid);
+            emit<CAP, IDX, WIDE, T64>(A, table, R, have, tk0, tk1, tlen, tstart, traw, docid);
         }
     return my_tokens;
 }
@@ -827,7 +917,7 @@ __device__ __forceinline__ uint32_t uni_class(const LDS uint8_t *uc, uint32_t cp
     else return mrg_uclass(cp);
     return (byte >> (2u * (cp & 3u))) & 3u;
 }
-template <int CAP, bool IDX, bool WIDE>
+template <int CAP, bool IDX, bool WIDE, bool T64>
 __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
     // the arguments live in device memory (not the kernarg segment): fields are loaded where they
     // are used instead of being held in SGPRs for the whole kernel
@@ -860,10 +950,12 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
     __shared__ KeyPair s_key[WIDE ? 2 : CAP];
     __shared__ unsigned int s_cnt[WIDE ? 2 : CAP];
     __shared__ __attribute__((aligned(16))) unsigned int s_doc[IDX ? CAP : 1];
-    __shared__ unsigned long long s_tcur[WIDE ? 1 : MRG_NBUCKET];  // next pool record of (bucket, this WG)
-    __shared__ unsigned long long s_tend[WIDE ? 1 : MRG_NBUCKET];  // end of that region
+    // tail cursors per bucket (TailRegions): packed, one word {next record, region end} per class; T64: the
+    // next record and the region's end as two 64-bit arrays per class
+    __shared__ unsigned long long s_tcur[WIDE ? 1 : MRG_NBUCKET];
+    __shared__ unsigned long long s_tend[(WIDE || !T64) ? 1 : MRG_NBUCKET];
     __shared__ unsigned long long s_tcur16[(IDX || WIDE) ? 1 : MRG_NBUCKET];  // wc: the 16-byte regions
-    __shared__ unsigned long long s_tend16[(IDX || WIDE) ? 1 : MRG_NBUCKET];
+    __shared__ unsigned long long s_tend16[(IDX || WIDE || !T64) ? 1 : MRG_NBUCKET];
     __shared__ uint32_t s_hist[WIDE ? 1 : MRG_NBUCKET + 1];
     __shared__ unsigned int s_wcur[WIDE ? MRG_WMAP_MAXB1 : 1];                  // wide: records per L1 bucket
     __shared__ __attribute__((aligned(16))) uint64_t s_wspl[WIDE ? 2 * MRG_WMAP_MAXB1 : 1];  // its splitters
@@ -917,13 +1009,22 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
     for (int b = tid; b < (WIDE ? 0 : MRG_NBUCKET); b += WG) {
         const uint32_t cap = gp(A.bcap)[b];
         const uint64_t base = gp(A.rbase)[b] + (uint64_t)blockIdx.x * cap;
-        s_tcur[b] = base;
-        s_tend[b] = base + cap;
+        // (packed: the host launches this form only when every index of the launch fits 32 bits)
+        if constexpr (T64) {
+            s_tcur[b] = base;
+            s_tend[b] = base + cap;
+        } else {
+            s_tcur[b] = base | ((base + cap) << 32);
+        }
         if (!IDX) {
             const uint32_t cap16 = gp(A.bcap16)[b];
             const uint64_t base16 = gp(A.rbase16)[b] + (uint64_t)blockIdx.x * cap16;
-            s_tcur16[b] = base16;
-            s_tend16[b] = base16 + cap16;
+            if constexpr (T64) {
+                s_tcur16[b] = base16;
+                s_tend16[b] = base16 + cap16;
+            } else {
+                s_tcur16[b] = base16 | ((base16 + cap16) << 32);
+            }
         }
     }
     if (tid == 0) {
@@ -1553,7 +1654,7 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
                     wide_store(A, tails, fa, a0, a1);
                     wide_store(A, tails, fb, b0, b1);
                 } else {
-                    emit_fastN<2>(A, abl, hbits, table, tails, pool, pool16, hv, kk0, kk1, docid, may_claim);
+                    emit_fastN<2, CAP, IDX, T64>(A, abl, hbits, table, tails, pool, pool16, hv, kk0, kk1, docid, may_claim);
                 }
             }
             return nslow;
@@ -1588,7 +1689,7 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
                     }
                 }
                 my_tokens += have ? 1u : 0u;
-                emit<CAP, IDX, WIDE>(A, table, tails, have, tk0, tk1, tlen, a, traw, docid);
+                emit<CAP, IDX, WIDE, T64>(A, table, tails, have, tk0, tk1, tlen, a, traw, docid);
             }
         };
         // an atomic LDS load (ds_read_b32): a volatile read of the same word compiled to a FLAT
@@ -1854,7 +1955,7 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
                 if (j0 >= T.v0 && j0 < T.v1) reinterpret_cast<uint4 *>(win)[j0] = x0;
                 if (has1 && j1 >= T.v0 && j1 < T.v1) reinterpret_cast<uint4 *>(win)[j1] = x1;
                 wave_sync_lds();
-                my_tokens += generic_tile<CAP, IDX, WIDE>(A, table, tails, win, T.At, T.t0, T.t1,
+                my_tokens += generic_tile<CAP, IDX, WIDE, T64>(A, table, tails, win, T.At, T.t0, T.t1,
                                                     T.doc_lo, T.doc_hi, T.wlo, T.whi, T.docid);
             }
         }
@@ -1878,11 +1979,14 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
     uint16_t *s_rank = &s_q[0][0];
     GAS uint32_t *bcount = gp(A.bcount) + (uint64_t)blockIdx.x * MRG_NBUCKET;
     for (int b = tid; b < MRG_NBUCKET; b += WG) {  // appends made (may exceed the capacity)
-        const uint32_t n = (uint32_t)(s_tcur[b] - (s_tend[b] - gp(A.bcap)[b]));
+        // (packed: the same difference of the word's halves, modulo 2^32)
+        const uint32_t n = T64 ? (uint32_t)(s_tcur[b] - (s_tend[b] - gp(A.bcap)[b]))
+                               : (uint32_t)s_tcur[b] - ((uint32_t)(s_tcur[b] >> 32) - gp(A.bcap)[b]);
         my_tail += n;
         bcount[b] = n;
         if (!IDX) {
-            const uint32_t n16 = (uint32_t)(s_tcur16[b] - (s_tend16[b] - gp(A.bcap16)[b]));
+            const uint32_t n16 = T64 ? (uint32_t)(s_tcur16[b] - (s_tend16[b] - gp(A.bcap16)[b]))
+                                     : (uint32_t)s_tcur16[b] - ((uint32_t)(s_tcur16[b] >> 32) - gp(A.bcap16)[b]);
             my_tail += n16;
             my_tail16 += n16;
             gp(A.bcount16)[(uint64_t)blockIdx.x * MRG_NBUCKET + b] = n16;
@@ -2056,8 +2160,15 @@ void mrg_launch_long_compact(const MapArgs &A, int grid, uint64_t *start, uint32
 }
 
 template <int CAP, bool IDX, bool WIDE = false>
-static void launch_map_t(const MapArgs *a, int grid, hipStream_t s) {
-    hipLaunchKernelGGL((k_map<CAP, IDX, WIDE>), dim3(grid), dim3(WG), 0, s, a);
+static void launch_map_t(const MapArgs *a, int grid, hipStream_t s, bool tail64) {
+    // (the wide map has cursors of its own and no tail regions: one instantiation)
+    if constexpr (!WIDE) {
+        if (!tail64) {
+            hipLaunchKernelGGL((k_map<CAP, IDX, false, false>), dim3(grid), dim3(WG), 0, s, a);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((k_map<CAP, IDX, WIDE, true>), dim3(grid), dim3(WG), 0, s, a);
 }
 
 static int map_cap_for(int app, int lds_cap) {
@@ -2065,19 +2176,20 @@ static int map_cap_for(int app, int lds_cap) {
     return lds_cap >= 4096 ? 4096 : 2048;
 }
 
-void mrg_launch_map(const MapArgs *h, MapArgs *a, int app, int grid, int lds_cap, hipStream_t s, bool wide) {
+void mrg_launch_map(const MapArgs *h, MapArgs *a, int app, int grid, int lds_cap, hipStream_t s, bool wide,
+                    bool tail64) {
     const bool idx = app == 1;
     if (h) (void)hipMemcpyAsync(a, h, sizeof(MapArgs), hipMemcpyHostToDevice, s);
     if (wide && !idx) {  // the wide map (no LDS table): one layout whatever lds_cap
-        launch_map_t<2048, false, true>(a, grid, s);
+        launch_map_t<2048, false, true>(a, grid, s, true);
         return;
     }
     if (map_cap_for(app, lds_cap) == 4096) {
-        if (idx) launch_map_t<4096, true>(a, grid, s);
-        else launch_map_t<4096, false>(a, grid, s);
+        if (idx) launch_map_t<4096, true>(a, grid, s, tail64);
+        else launch_map_t<4096, false>(a, grid, s, tail64);
     } else {
-        if (idx) launch_map_t<2048, true>(a, grid, s);
-        else launch_map_t<2048, false>(a, grid, s);
+        if (idx) launch_map_t<2048, true>(a, grid, s, tail64);
+        else launch_map_t<2048, false>(a, grid, s, tail64);
     }
 }
 
@@ -2089,16 +2201,17 @@ uint64_t mrg_map_tiles(uint64_t lo, uint64_t hi) {
     return (hi - (lo & ~15ull) + BLK - 1) / BLK;
 }
 
+// (asked of the 64-bit tail form, which has the larger LDS: a grid that fits it fits the packed form)
 int mrg_map_max_grid(int app, int lds_cap, int device) {
     int ncu = 256;
     (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device);
     int per = 1;
     hipError_t e;
     if (map_cap_for(app, lds_cap) == 4096)
-        e = app == 1 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_map<4096, true, false>, WG, 0)
-                     : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_map<4096, false, false>, WG, 0);
-    else if (app == 1) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_map<2048, true, false>, WG, 0);
-    else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_map<2048, false, false>, WG, 0);
+        e = app == 1 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_map<4096, true, false, true>, WG, 0)
+                     : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_map<4096, false, false, true>, WG, 0);
+    else if (app == 1) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_map<2048, true, false, true>, WG, 0);
+    else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_map<2048, false, false, true>, WG, 0);
     if (e != hipSuccess || per < 1) per = 1;
     return ncu * per;
 }

@@ -965,6 +965,15 @@ MapSteal map_steal(uint64_t n_chunks, int grid) {
     return m;
 }
 
+// The packed tail cursors (k_map.hip TailRegions: record index and region end in one 64-bit word) are
+// valid while no index can carry into its end.  A region's index starts below rtot and grows by one
+// per append, past a full region too; a workgroup appends at most one record per token it maps, and a
+// block holds at most BLK / 2 token starts.  So every index of the launch stays below the left side.
+inline bool map_tail_packed(uint64_t rtot, uint64_t rtot16, const MapSteal &ms) {
+    const uint64_t appends = ms.per_wg_blocks * (uint64_t)(MRG_MAP_NSUB * MRG_MAP_TILE) / 2 + 1;
+    return rtot + appends < (1ull << 32) && rtot16 + appends < (1ull << 32);
+}
+
 // ---- what the LDS-combine map (job_map) and the wide map (job_map_wide) share.  The device blocks of
 // one launch belong to a Scratch of the attempt (`att`), which a rerun returns before it takes its own.
 
@@ -1320,7 +1329,10 @@ void job_map(mrg_ctx *c) {
         stage_h2d(c, dargs, &A, sizeof(MapArgs));
         flush_stage(c);
         ev_rec(c, c->ev, 0);
-        mrg_launch_map(nullptr, dargs, c->app, grid, c->lds_cap, s);  // also with no tiles: writes empty flush regions
+        // (MRG_TEST_TAIL64=1: the 64-bit cursors whatever the sizes, for the tests)
+        const bool tail64 = !map_tail_packed(rtot, rtot16, ms) || env_u64("MRG_TEST_TAIL64", 0) != 0;
+        // also with no tiles: writes empty flush regions
+        mrg_launch_map(nullptr, dargs, c->app, grid, c->lds_cap, s, false, tail64);
         ev_rec(c, c->ev, 1);
         HIPCHK(hipGetLastError());
         ++launches;
