@@ -163,8 +163,29 @@ struct TileInfo {
 
 struct BlkInfo {
     uint64_t Ab, doc_lo, doc_hi;
-    uint32_t docid, v0, v1;
+    uint32_t docid, v0, v1, cend;
 };
+
+// What the main loop keeps of the block it is at: the document's start only as
+// the offset process_blk reduces it to anyway, lo = doc_lo - Ab clamped to [-BEHIND, 16) (a block of
+// the 16-byte grid starts at most 15 bytes before its document), and no load bounds -- they are used
+// once, when the block's loads are issued.
+struct CurBlk {
+    uint64_t Ab, doc_hi;
+    int32_t lo;
+    uint32_t docid;
+    uint32_t cend;  // the first block of the next document (block numbers fit 32 bits)
+};
+__device__ __forceinline__ CurBlk cur_of(const BlkInfo &b) {
+    const int64_t d = (int64_t)(b.doc_lo - b.Ab);
+    return CurBlk{b.Ab, b.doc_hi, (int32_t)(d < -(int64_t)BEHIND ? -(int64_t)BEHIND : d), b.docid, b.cend};
+}
+// min(x, m) of a 64-bit x as 32-bit scalar work (the SALU has no ordered 64-bit compare: umin64 of a
+// wave-uniform value goes through the VALU)
+__device__ __forceinline__ uint32_t clip_u32(uint64_t x, uint32_t m) {
+    const uint32_t l = (uint32_t)(x >> 32) ? 0xFFFFFFFFu : (uint32_t)x;
+    return l < m ? l : m;
+}
 
 // Block c of the job (BLK bytes on the document's 16-byte grid).  A wave visits its blocks in increasing
 // order, so the document index only moves forward (usually not at all).  v0/v1: the loadable
@@ -175,6 +196,7 @@ __device__ __forceinline__ BlkInfo locate_blk(const MapArgs &A, uint64_t c, uint
     BlkInfo b;
     b.doc_lo = doff[d];
     b.doc_hi = doff[d + 1];
+    b.cend = (uint32_t)cb[d + 1];  // (the host refuses a launch of 2^32 blocks)
     b.Ab = (b.doc_lo & ~15ull) + (c - cb[d]) * (uint64_t)BLK;
     b.docid = A.doc_id ? cp(A.doc_id)[d] : d;
     const uint64_t vbase = b.Ab - (uint64_t)BEHIND;  // may wrap below 0: only differences are used
@@ -770,7 +792,7 @@ __device__ __forceinline__ void emit(const MapArgs &A, LdsTable<CAP, IDX> &table
     uint32_t h = 0;
     const uint32_t dkey = IDX ? docid : MRG_EMPTY_DOC;
     if (have && !is_long) {
-        h = key_hash(tk0, tk1, dkey, A.hash_bits);
+        h = key_hash(tk0, tk1, dkey, T64 ? A.hash_bits : 0u);
     }
     {
         const bool act = have && !is_long && !(map_ablate(A) & 2u);
@@ -963,6 +985,7 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
     __shared__ uint32_t s_next, s_ngen;                  // next block of the workgroup's share; list length
     __shared__ uint32_t s_stolen;                        // pool blocks this workgroup's waves have claimed
     __shared__ uint32_t s_share[2];                      // the workgroup's share of the static blocks: [lo, hi)
+    __shared__ __attribute__((aligned(16))) uint32_t s_nxt[NW][8];                    // per wave: the next block's CurBlk after a full lookup
     __shared__ uint32_t s_pool[NW];                      // per wave: the pool part it takes from | parts tried << 8
     __shared__ uint32_t s_nuni;                          // non-ASCII tiles tokenized with UTF-8-exact masks
     // the class table's blocks for U+0000..U+07FF (2-byte codepoints: Latin-1, Latin Extended, Greek,
@@ -1075,7 +1098,9 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
 #else
     constexpr uint32_t abl = MRG_MAP_ABL_CONST;
 #endif
-    const uint32_t hbits = A.hash_bits;
+    // the forced-collision hash mask (a test knob) exists in the general variant only (T64: the host launches
+    // it whenever hash_bits is set); the packed variant hashes in full, with no mask in the token round
+    const uint32_t hbits = T64 ? A.hash_bits : 0u;
     GAS uint64_t *const pool = gp(A.pool);
     GAS uint64_t *const pool16 = gp(A.pool16);
     uint8_t *win = s_win[wv];
@@ -1106,14 +1131,18 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
     struct Blk {
         uint4 v0, v1, e;
     };
+    struct BlkLoad {  // a block's base and its loadable vectors [v0, v1) relative to Ab - 16
+        uint64_t Ab;
+        uint32_t v0, v1;
+    };
 #ifdef MRG_MAP_ABLATION
-    BlkInfo first_blk{};  // ablate & 8 (timing only): every block re-reads the wave's first block
+    BlkLoad first_blk{};  // ablate & 8 (timing only): every block re-reads the wave's first block
 #endif
-    auto load_blk = [&](const BlkInfo &b0, Blk &X) {
+    auto load_blk = [&](const BlkLoad &b0, Blk &X) {
 #ifdef MRG_MAP_ABLATION
-        const BlkInfo &b = (abl & 8u) ? first_blk : b0;  // a real block: its own base and bounds
+        const BlkLoad &b = (abl & 8u) ? first_blk : b0;  // a real block: its own base and bounds
 #else
-        const BlkInfo &b = b0;
+        const BlkLoad &b = b0;
 #endif
         const GAS uint8_t *src = gp(A.in) + (b.Ab - (uint64_t)BEHIND);
         auto ld = [&](uint32_t idx) -> uint4 {
@@ -1135,7 +1164,8 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
     // holds no registers for them)
     // non-ASCII tiles: appended to this workgroup's list (absolute tile index: block * NSUB + tile),
     // processed after the main loop by all 16 waves
-    GAS uint32_t *glist = gp(A.gbits) + (uint64_t)blockIdx.x * A.kwords;
+    // (the list's address is formed where it is used, not held across the main loop)
+    auto glist_of = [&]() -> GAS uint32_t * { return gp(A.gbits) + (uint64_t)blockIdx.x * A.kwords; };
 
     // one block: masks of its 1 KiB tiles up front, then tile by tile through the
     // wave's LDS window
@@ -1305,13 +1335,14 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
         return false;
     };
 
-    auto process_blk = [&](const BlkInfo &I, const Blk &X, uint32_t cblk, auto &&mid) {
-        const uint64_t Ab = I.Ab, doc_lo = I.doc_lo, doc_hi = I.doc_hi;
+    auto process_blk = [&](const CurBlk &I, const Blk &X, uint32_t cblk, auto &&mid) {
+        const uint64_t Ab = I.Ab, doc_hi = I.doc_hi;
         const uint32_t docid = I.docid;
+        const int lo = I.lo;  // the document's start in block offsets, [-16, 16)
         // classify segment [B, B + 16) (relative to Ab) into W16 | S16 << 16; bytes outside the
         // document count as White_Space (exact for every staged byte: no window cut)
-        const uint32_t lo_rel = doc_lo > Ab ? (uint32_t)(doc_lo - Ab) : 0u;
-        const uint32_t hi_rel = (uint32_t)umin64(doc_hi - Ab, (uint64_t)(BLK + HALO));
+        const uint32_t lo_rel = lo > 0 ? (uint32_t)lo : 0u;
+        const uint32_t hi_rel = clip_u32(doc_hi - Ab, (uint32_t)(BLK + HALO));
         // A block that lies inside its document with its halo (all but about two blocks per document)
         // has no such byte: `edge` is wave-uniform, and only an edge block pays for the masks
         const bool edge = lo_rel != 0u || hi_rel != (uint32_t)(BLK + HALO);
@@ -1344,17 +1375,23 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
         };
         auto na = [](const uint4 &x) { return ((x.x | x.y | x.z | x.w) & 0x80808080u) != 0u; };
         const uint32_t l16 = (uint32_t)lane * SEG;
+        // the lane number for this block's lane tests: opaque, so that the tests are made here (a v_cmp each)
+        // and not hoisted out of the main loop as lane masks, two SGPRs each, which did not fit and were
+        // spilled and reloaded per block
+        uint32_t ln = (uint32_t)lane;
+        asm volatile("" : "+v"(ln));
         uint32_t m0 = classify(X.v0), m1 = classify(X.v1);
         // the first halo segment (lane 1's e) by 16 lanes, one byte each, through two ballots
         uint32_t mh;
         {
             const uint32_t e0 = lane_u32(X.e.x, 1), e1 = lane_u32(X.e.y, 1), e2 = lane_u32(X.e.z, 1),
                            e3 = lane_u32(X.e.w, 1);
-            const uint32_t k = (uint32_t)lane & 15u;
+            const uint32_t k = ln & 15u;
             const uint32_t dwv = k < 8u ? (k < 4u ? e0 : e1) : (k < 12u ? e2 : e3);
             const uint32_t cl = s_lut[0][__builtin_amdgcn_ubfe(dwv, 8u * (k & 3u), 8)];
-            const uint32_t wm = (uint32_t)__ballot(lane < 16 && (cl & 1u));
-            const uint32_t sm = (uint32_t)__ballot(lane < 16 && (cl & 0x10u));
+            // (lanes 16..63 repeat lanes 0..15: the ballots' low halves are the segment's masks)
+            const uint32_t wm = (uint32_t)__ballot((cl & 1u) != 0u);
+            const uint32_t sm = (uint32_t)__ballot((cl & 0x10u) != 0u);
             mh = (wm & 0xFFFFu) | (sm << 16);
         }
         if (edge) {  // bytes before and past the document are White_Space
@@ -1365,14 +1402,14 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
         const bool n0 = na(X.v0), n1 = na(X.v1), ne = na(X.e);
         // class of the byte before the block (lane 0's e, byte 15)
         uint32_t prev_blk =
-            Ab > doc_lo ? (uint32_t)(s_lut[0][lane_u32(X.e.w, 0) >> 24] >> 4) & 1u : 1u;
+            lo < 0 ? (uint32_t)(s_lut[0][lane_u32(X.e.w, 0) >> 24] >> 4) & 1u : 1u;
         // A non-ASCII byte where the fast path reads (either tile, the first halo segment, the bytes
         // before the block): the LUT classes of the non-ASCII bytes are replaced by UTF-8-exact ones,
         // after which both tiles are tokenized exactly like ASCII tiles -- every byte of a codepoint
         // carries its class, so the W / S masks mean the same.  Invalid UTF-8 defers the block's tiles
         // to generic_tile after the main loop (which reports the first bad byte).
         bool defer_blk = false;
-        if (!(abl & 256u) && !(MRG_MAP_ABL_CONST & 0x20000u) && __any(n0 || n1 || (lane <= 1 && ne))) {
+        if (!(abl & 256u) && !(MRG_MAP_ABL_CONST & 0x20000u) && __any(n0 || n1 || (ln <= 1u && ne))) {
 #ifdef MRG_MAP_NO_UNI
             defer_blk = true;  // A/B builds only: every such block to the exact walker, as in r03
 #else
@@ -1388,11 +1425,8 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
             // into the wave's queue and decoded one per lane from the staged window: two stagings,
             // two queue fills and two divergent read-backs per block, and a queue that invalid input
             // with more than 528 leads per tile could overflow.)
-            const int64_t dlo = (int64_t)(doc_lo - Ab);  // two's complement (see lo below)
-            // the document in block offsets: lo in [-16, 16), hi in (0, 2112].  (A select on
-            // doc_lo > Ab lost its first case in the compiled code: keep a clamped signed difference.)
-            const int lo = (int)(dlo < -(int64_t)BEHIND ? -(int64_t)BEHIND : dlo);
-            const int hi = (int)umin64(doc_hi - Ab, (uint64_t)(BLK + HALO));
+            // the document in block offsets: lo in [-16, 16) (CurBlk), hi in (0, 2112]
+            const int hi = (int)hi_rel;
             const LDS uint8_t *uc = (const LDS uint8_t *)s_uc;
             bool bad = false;
             auto hb = [](uint32_t d) { return ((((d & 0x80808080u) >> 7) * 0x00204081u) >> 21) & 0xFu; };
@@ -1419,7 +1453,7 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
             const uint32_t before = lane_u32(X.e.w, 0);  // block bytes -4..-1
             int pbp = 0;
             bool has_b = false;
-            if (dlo < 0 && (before >> 24) >= 0x80u) {
+            if (lo < 0 && (before >> 24) >= 0x80u) {
                 uint32_t bb = before >> 24;
                 pbp = -1;
                 for (int k = 2; k <= 4 && (bb & 0xC0u) == 0x80u; ++k) {
@@ -1602,6 +1636,7 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
         MRG_PT(0);
         if (defer_blk) {  // recorded; processed after the main loop
             if (lane == 0) {
+                GAS uint32_t *glist = glist_of();
                 for (uint32_t j = 0; j < NSUB && Ab + (uint64_t)j * TILE < doc_hi; ++j) {
                     // (a list is sized for every tile the workgroup can map: an entry past it is
                     // counted, not written, and the launch is rerun with longer lists)
@@ -1701,21 +1736,21 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
 
         if constexpr (BQ) {
             // ---- block queue: the whole block staged, scanned and queued once
-            const uint64_t whi = umin64(Ab + (uint64_t)(BLK + HALO), doc_hi);
+            const uint64_t whi = Ab + (uint64_t)clip_u32(doc_hi - Ab, (uint32_t)(BLK + HALO));
             // stage the block and its 64-byte halo (the previous block's readers are done: program order)
             wave_sync_lds();
             reinterpret_cast<uint4 *>(win)[1 + lane] = X.v0;
             reinterpret_cast<uint4 *>(win)[65 + lane] = X.v1;
-            if (lane >= 1 && lane < 5) reinterpret_cast<uint4 *>(win)[128 + lane] = X.e;
+            if (ln - 1u < 4u) reinterpret_cast<uint4 *>(win)[128 + lane] = X.e;
             // masks: one word per segment, the halo's first segment behind them
             mw[lane] = m0;
             mw[64 + lane] = m1;
-            if (lane == 0) mw[2 * 64] = mh;
+            if (ln == 0u) mw[2 * 64] = mh;
             // token starts of this lane's two segments (lane and 64 + lane): the previous byte's class
             // from lane l-1 (lane 0: the byte before the block, and tile 0's last byte)
             uint32_t pv0 = from_prev_lane(m0) >> 31, pv1 = from_prev_lane(m1) >> 31;
             const uint32_t m0_last = lane_u32(m0, 63) >> 31;
-            if (lane == 0) {
+            if (ln == 0u) {
                 pv0 = prev_blk;
                 pv1 = m0_last;
             }
@@ -1885,23 +1920,11 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
         if (lane == 0) s_pool[wv] = pt;
         return NONE;
     };
-    // The block after `P` (block cp_ of the job) when the wave's next block cn is the next 2 KiB of the
-    // same document (nearly always: a run's blocks are consecutive): its bounds follow from P's, with
-    // no table lookup.  Block cp_ + 1 belongs to P's document exactly when it starts before the
-    // document's end (mrg_map_tiles).  dcur then lags behind; locate_blk walks it forward when needed.
-    auto next_blk = [&](const BlkInfo &P, uint32_t cp_, uint32_t cn) -> BlkInfo {
-        if (cn != cp_ + 1u || P.Ab + (uint64_t)BLK >= P.doc_hi) return locate_blk(A, cn, dcur);
-        BlkInfo b = P;
-        b.Ab = P.Ab + (uint64_t)BLK;
-        const uint64_t whi = umin64(b.Ab + (uint64_t)(BLK + HALO), b.doc_hi);
-        b.v0 = 0u;  // the 16 bytes before it are the previous block's
-        b.v1 = (uint32_t)((((whi + 15u) & ~15ull) - (b.Ab - (uint64_t)BEHIND)) >> 4);
-        return b;
-    };
     uint32_t c = grab();
     if (c != NONE) dcur = find_doc(A, c);
     Blk XA, XB;
-    BlkInfo IA{}, IB{};
+    CurBlk I{};
+    uint32_t *nxt = s_nxt[wv];  // the next block's record after a full lookup (see step)
     // Make a block's registers available HERE (the compiler waits for its loads at this point, when
     // only older loads and stores are outstanding), before the next block's loads are issued --
     // otherwise the scheduler sinks the first use below them and the wait covers the new loads too.
@@ -1909,26 +1932,71 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
         asm volatile("" : "+v"(X.v0.x), "+v"(X.v0.y), "+v"(X.v0.z), "+v"(X.v0.w), "+v"(X.v1.x), "+v"(X.v1.y),
                      "+v"(X.v1.z), "+v"(X.v1.w), "+v"(X.e.x), "+v"(X.e.y), "+v"(X.e.z), "+v"(X.e.w));
     };
+    // ONE record of the block the wave is at (I) lives across process_blk.  When the wave's next block cn
+    // is the next 2 KiB of the same document (nearly always: a run's blocks are consecutive, and block
+    // c + 1 belongs to c's document exactly when it starts before the document's end, mrg_map_tiles),
+    // its loads need only I, and afterwards I is advanced in place: Ab + BLK, the document's start
+    // far behind, the same end and id (c + 1 < cend is how
+    // locate_blk itself assigns block c + 1 to this document).  No table is read; dcur then lags behind and
+    // locate_blk walks it forward when needed.  Otherwise (a run's first block, or the run leaves the document) the full
+    // lookup runs before the loads are issued and its result waits in the wave's LDS slot, not in
+    // registers held through the token rounds.
+    // `want`: the one block number that continues I's document after block c, or c itself (never handed out
+    // again) when c is the document's last block -- so "the next block is the successor" is one scalar compare,
+    // made before the loads and again after the block rather than kept as a lane mask through it.
+    auto want_of = [&]() { return c + 1u < I.cend ? c + 1u : c; };
+    auto step = [&](const Blk &Xc, Blk &Xn) {
+        uint32_t cn = grab();
+        const uint32_t want = want_of();
+        BlkLoad L;
+        if (cn == want) {
+            const uint32_t hi = clip_u32(I.doc_hi - (I.Ab + (uint64_t)BLK), (uint32_t)(BLK + HALO));
+            L = BlkLoad{I.Ab + (uint64_t)BLK, 0u, ((hi + 15u) >> 4) + 1u};  // (the 16 bytes before it are block c's)
+        } else if (cn != NONE) {
+            const BlkInfo b = locate_blk(A, cn, dcur);
+            L = BlkLoad{b.Ab, b.v0, b.v1};
+            const CurBlk n = cur_of(b);
+            if (lane == 0) {
+                *reinterpret_cast<uint4 *>(nxt) = uint4{(uint32_t)n.Ab, (uint32_t)(n.Ab >> 32), (uint32_t)n.doc_hi,
+                                                        (uint32_t)(n.doc_hi >> 32)};
+                *reinterpret_cast<uint4 *>(nxt + 4) = uint4{(uint32_t)n.lo, n.docid, n.cend, 0u};
+            }
+        } else {
+            // past the end the "next" block is a reload of this block's first vector, which every block
+            // may load: v0 <= 1 (a block starts at most 15 bytes before its document) and v1 >= 2
+            L = BlkLoad{I.Ab, 1u, 2u};
+        }
+        load_blk(L, Xn);
+        process_blk(I, Xc, c, [&]() { settle(Xn); });
+        asm volatile("" : "+s"(cn));
+        if (cn == want_of()) {
+            I.Ab += (uint64_t)BLK;
+            I.lo = -(int32_t)BEHIND;
+        } else if (cn != NONE) {
+            wave_sync_lds();  // lane 0's writes above, read by every lane
+            const uint4 r0 = *reinterpret_cast<const uint4 *>(nxt), r1 = *reinterpret_cast<const uint4 *>(nxt + 4);
+            I.Ab = (uint64_t)first_u32(r0.x) | ((uint64_t)first_u32(r0.y) << 32);
+            I.doc_hi = (uint64_t)first_u32(r0.z) | ((uint64_t)first_u32(r0.w) << 32);
+            I.lo = (int32_t)first_u32(r1.x);
+            I.docid = first_u32(r1.y);
+            I.cend = first_u32(r1.z);
+        }
+        c = cn;
+    };
     if (c != NONE) {
-        IA = locate_blk(A, c, dcur);
+        const BlkInfo b = locate_blk(A, c, dcur);
+        I = cur_of(b);
+        const BlkLoad L{b.Ab, b.v0, b.v1};
 #ifdef MRG_MAP_ABLATION
-        first_blk = IA;
+        first_blk = L;
 #endif
-        load_blk(IA, XA);
+        load_blk(L, XA);
         settle(XA);
     }
     while (c != NONE) {
-        const uint32_t cB = grab();
-        IB = cB != NONE ? next_blk(IA, c, cB) : IA;
-        load_blk(IB, XB);
-        process_blk(IA, XA, c, [&]() { settle(XB); });
-        c = cB;
+        step(XA, XB);
         if (c == NONE) break;
-        const uint32_t cA = grab();
-        IA = cA != NONE ? next_blk(IB, c, cA) : IB;
-        load_blk(IA, XA);
-        process_blk(IB, XB, c, [&]() { settle(XA); });
-        c = cA;
+        step(XB, XA);
     }
     MRG_PT(4);
 #ifdef MRG_MAP_PROF
@@ -1942,6 +2010,7 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
     if (s_ngen) __syncthreads();  // (uniform) the list is complete: its global writes, then the barrier
     {
         const uint32_t ng = min(s_ngen, A.kwords);
+        const GAS uint32_t *glist = glist_of();
         for (uint32_t i = (uint32_t)wv; i < ng; i += NW) {
             {
                 const uint32_t kk = first_u32(glist[i]);
@@ -1998,7 +2067,7 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
     for (int i = tid; i < CAP; i += WG) {
         const KeyPair k = s_key[i];
         if (k.a == MRG_EMPTY_K0) continue;
-        const uint32_t b = bucket_of(key_hash(k.a, k.b, IDX ? s_doc[i] : MRG_EMPTY_DOC, A.hash_bits));
+        const uint32_t b = bucket_of(key_hash(k.a, k.b, IDX ? s_doc[i] : MRG_EMPTY_DOC, hbits));
         s_rank[i] = (uint16_t)atomicAdd(&s_hist[b], 1u);
     }
     lds_only_barrier();
@@ -2022,7 +2091,7 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
         const KeyPair k = s_key[i];
         if (k.a == MRG_EMPTY_K0) continue;
         const uint32_t d = IDX ? s_doc[i] : MRG_EMPTY_DOC;
-        const uint32_t b = bucket_of(key_hash(k.a, k.b, d, A.hash_bits));
+        const uint32_t b = bucket_of(key_hash(k.a, k.b, d, hbits));
         const uint64_t pos2 = reg + s_hist[b] + s_rank[i];
         gp(A.fk0)[pos2] = k.a;
         gp(A.fk1)[pos2] = k.b;

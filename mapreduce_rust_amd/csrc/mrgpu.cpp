@@ -1329,8 +1329,9 @@ void job_map(mrg_ctx *c) {
         stage_h2d(c, dargs, &A, sizeof(MapArgs));
         flush_stage(c);
         ev_rec(c, c->ev, 0);
-        // (MRG_TEST_TAIL64=1: the 64-bit cursors whatever the sizes, for the tests)
-        const bool tail64 = !map_tail_packed(rtot, rtot16, ms) || env_u64("MRG_TEST_TAIL64", 0) != 0;
+        // (MRG_TEST_TAIL64=1: the 64-bit cursors whatever the sizes, for the tests.  The forced-collision hash
+        // mask, a test knob too, exists in that general variant only: the packed one hashes in full)
+        const bool tail64 = !map_tail_packed(rtot, rtot16, ms) || A.hash_bits != 0 || env_u64("MRG_TEST_TAIL64", 0) != 0;
         // also with no tiles: writes empty flush regions
         mrg_launch_map(nullptr, dargs, c->app, grid, c->lds_cap, s, false, tail64);
         ev_rec(c, c->ev, 1);
