@@ -113,6 +113,15 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
     v += __builtin_amdgcn_update_dpp(0u, v, 0x143, 0xC, 0xF, false);  // row_bcast:31 -> rows 2, 3
     return v;
 }
+// Lane conditions as lane masks.  The ballot of ONE compare is the compare's own scalar result (no
+// instruction); of anything else -- a combination of compares, a bool that lived through a branch --
+// it is a v_cndmask to 0 / 1 and a v_cmp back, which is also what __any(bool) and __ballot(bool)
+// compile to.  So the token round takes the ballot of each compare, combines the 64-bit masks with
+// scalar logic, tests "any lane" as mask != 0, and turns a mask back into this lane's condition with
+// lane_of (no instruction either: the mask is used as the lane mask it is).  The argument of lane_of
+// must be wave-uniform, as every ballot is.
+__device__ __forceinline__ uint64_t wave_mask(bool b) { return __builtin_amdgcn_ballot_w64(b); }
+__device__ __forceinline__ bool lane_of(uint64_t m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
 // a workgroup barrier for LDS only: the wave's outstanding global stores are not waited for (a
 // __syncthreads() waits for them too -- at the end of the map that is every workgroup's last tail
 // stores at once)
@@ -183,7 +192,9 @@ __device__ __forceinline__ CurBlk cur_of(const BlkInfo &b) {
 // min(x, m) of a 64-bit x as 32-bit scalar work (the SALU has no ordered 64-bit compare: umin64 of a
 // wave-uniform value goes through the VALU)
 __device__ __forceinline__ uint32_t clip_u32(uint64_t x, uint32_t m) {
-    const uint32_t l = (uint32_t)(x >> 32) ? 0xFFFFFFFFu : (uint32_t)x;
+    uint32_t h = (uint32_t)(x >> 32);
+    asm("" : "+s"(h));  // (opaque: "the high word is not zero" is otherwise re-formed into x > 0xFFFFFFFF, a v_cmp_lt_u64)
+    const uint32_t l = h ? 0xFFFFFFFFu : (uint32_t)x;
     return l < m ? l : m;
 }
 
@@ -568,20 +579,26 @@ __device__ __forceinline__ void tail16_append(const MapArgs &A, const TailRegion
 template <int N, int CAP, bool IDX, bool T64>
 __device__ __forceinline__ void emit_fastN(const MapArgs &A, uint32_t abl, uint32_t hbits, LdsTable<CAP, IDX> &T,
                                            TailRegions R, GAS uint64_t *pool, GAS uint64_t *pool16,
-                                           const bool (&has)[N], const uint64_t (&k0)[N], const uint64_t (&k1)[N],
-                                           uint32_t docid, bool may_claim) {
+                                           const uint64_t (&hasm)[N], const uint64_t (&k0)[N], const uint64_t (&k1)[N],
+                                           const uint32_t (&klen)[N], uint32_t docid, bool may_claim) {
+    // Every per-lane condition of the round is kept as its lane mask (a wave-uniform 64-bit value: hasm
+    // = the lanes that have token t): masks are combined by the SALU, tested with a scalar compare, and
+    // survive a branch as an SGPR pair.  lane_of(mask) is this lane's bit as a condition (no instruction).
     constexpr uint32_t NS = LdsTable<CAP, IDX>::NS;
     const uint32_t dkey = IDX ? docid : MRG_EMPTY_DOC;
     uint32_t h[N], s[N], b[N];
-    bool act[N], w16[N], hit[N], m0[N];
+    uint64_t actm[N], w16m[N], hitm[N], m0m[N];
     KeyPair kw0[N], kw1[N];
     uint64_t end[N];  // T64 only
 #pragma unroll
     for (int t = 0; t < N; ++t) {
         h[t] = key_hash(k0[t], k1[t], dkey, hbits);
-        act[t] = has[t] && !(abl & 2u);
+        actm[t] = (abl & 2u) ? 0ull : hasm[t];
     }
 #if MRG_MAP_DEDUP
+    bool act[N], hit[N];
+#pragma unroll
+    for (int t = 0; t < N; ++t) act[t] = lane_of(actm[t]);
     // Per-wave dedup (timing variant): MRG_MAP_DEDUP leader rounds over the round's N x 64 tokens.  A
     // leader is the first token still pending; every token with the leader's key joins its group,
     // skips the probe and the count add, and the leader adds the group's size.  When the leader
@@ -640,59 +657,74 @@ __device__ __forceinline__ void emit_fastN(const MapArgs &A, uint32_t abl, uint3
         gl_tok[g] = (uint32_t)tl0;
         gl_lane[g] = src;
     }
+#pragma unroll
+    for (int t = 0; t < N; ++t) actm[t] = wave_mask(act[t]);
 #endif
 #pragma unroll
     for (int t = 0; t < N; ++t) {
-        s[t] = act[t] ? (h[t] & (NS - 1)) : 0u;
+        s[t] = lane_of(actm[t]) ? (h[t] & (NS - 1)) : 0u;
         b[t] = bucket_of(h[t]);
-        // wc keys of 13..16 bytes (the low word of k1, as a 32-bit value): the 16-byte regions
-        w16[t] = !IDX && (T64 ? (uint32_t)k1[t] != 0u : key_over12(k1[t]));
+        // wc keys of 13..16 bytes: the 16-byte regions.  Packed form: by the key's length, which the
+        // caller has from the token's masks (a key byte is never zero, so "more than 12 bytes" is "the
+        // low word of k1 is not zero", what every other path tests; no copy of the word for the compare)
+        w16m[t] = IDX ? 0ull : T64 ? wave_mask((uint32_t)k1[t] != 0u) : wave_mask(klen[t] > 12u);
     }
     // both ways of every set: 2N 16-byte reads in flight together (T64: with the region ends)
 #pragma unroll
     for (int t = 0; t < N; ++t) {
         kw0[t] = T.key[s[t]];
         kw1[t] = T.key[s[t] + NS];
-        if constexpr (T64) end[t] = (w16[t] ? R.end16 : R.end)[b[t]];
+        if constexpr (T64) end[t] = (lane_of(w16m[t]) ? R.end16 : R.end)[b[t]];
     }
+    // (each compare's ballot is the compare's own scalar result; the combinations are scalar)
 #pragma unroll
     for (int t = 0; t < N; ++t) {
-        m0[t] = act[t] & (((kw0[t].a ^ k0[t]) | (kw0[t].b ^ k1[t])) == 0) & (!IDX || T.doc[s[t]] == dkey);
-        const bool m1 = act[t] & !m0[t] & (((kw1[t].a ^ k0[t]) | (kw1[t].b ^ k1[t])) == 0) &
-                        (!IDX || T.doc[s[t] + NS] == dkey);
-        hit[t] = m0[t] | m1;
+        m0m[t] = actm[t] & wave_mask(kw0[t].a == k0[t]) & wave_mask(kw0[t].b == k1[t]);
+        uint64_t m1m = actm[t] & wave_mask(kw1[t].a == k0[t]) & wave_mask(kw1[t].b == k1[t]);
+        if constexpr (IDX) {
+            m0m[t] &= wave_mask(T.doc[s[t]] == dkey);
+            m1m &= wave_mask(T.doc[s[t] + NS] == dkey);
+        }
+        hitm[t] = m0m[t] | m1m;
     }
     if (!(abl & 16u)) {
 #pragma unroll
         for (int t = 0; t < N; ++t)
 #if MRG_MAP_DEDUP
-            if (hit[t]) atomicAdd(&T.cnt[m0[t] ? s[t] : s[t] + NS], gadd[t]);
+            if (lane_of(hitm[t])) atomicAdd(&T.cnt[lane_of(m0m[t]) ? s[t] : s[t] + NS], gadd[t]);
 #else
-            if (hit[t]) atomicAdd(&T.cnt[m0[t] ? s[t] : s[t] + NS], 1u);
+            if (lane_of(hitm[t])) atomicAdd(&T.cnt[lane_of(m0m[t]) ? s[t] : s[t] + NS], 1u);
 #endif
     }
     // empty ways exist only until the table has filled (wave-uniform: a stale count only means
-    // an unneeded test)
+    // an unneeded test); with the table full there is no claim side, and the probe's mask goes on as
+    // it is
     if (may_claim) {
-        bool e0[N], e1[N], need[N], any = false;
+        bool e0[N], e1[N];
+        uint64_t needm[N], anym = 0;
 #pragma unroll
         for (int t = 0; t < N; ++t) {
             e0[t] = kw0[t].a == MRG_EMPTY_K0;
             e1[t] = kw1[t].a == MRG_EMPTY_K0;
-            need[t] = act[t] && !hit[t] && (e0[t] || e1[t]);
-            any = any || need[t];
+            needm[t] = actm[t] & ~hitm[t] & (wave_mask(e0[t]) | wave_mask(e1[t]));
+            anym |= needm[t];
         }
-        if (__any(any)) {
+        if (anym) {
 #pragma unroll
-            for (int t = 0; t < N; ++t)
+            for (int t = 0; t < N; ++t) {
+                bool got = false;
 #if MRG_MAP_DEDUP
-                if (need[t]) hit[t] = T.claim(s[t], e0[t], e1[t], k0[t], k1[t], dkey, h[t], gadd[t]);
+                if (lane_of(needm[t])) got = T.claim(s[t], e0[t], e1[t], k0[t], k1[t], dkey, h[t], gadd[t]);
 #else
-                if (need[t]) hit[t] = T.claim(s[t], e0[t], e1[t], k0[t], k1[t], dkey, h[t]);
+                if (lane_of(needm[t])) got = T.claim(s[t], e0[t], e1[t], k0[t], k1[t], dkey, h[t]);
 #endif
+                hitm[t] |= wave_mask(got);
+            }
         }
     }
 #if MRG_MAP_DEDUP
+#pragma unroll
+    for (int t = 0; t < N; ++t) hit[t] = lane_of(hitm[t]);
     // members take their leader's outcome (a leader that missed: every member to the tail)
 #pragma unroll
     for (int g = 0; g < MRG_MAP_DEDUP; ++g) {
@@ -705,25 +737,27 @@ __device__ __forceinline__ void emit_fastN(const MapArgs &A, uint32_t abl, uint3
         for (int t = 0; t < N; ++t)
             if (grp[t] == (uint32_t)g) hit[t] = lh != 0u;
     }
-#endif
-    bool tl[N];
 #pragma unroll
-    for (int t = 0; t < N; ++t) tl[t] = has[t] && !hit[t] && !(abl & 1u);
+    for (int t = 0; t < N; ++t) hitm[t] = wave_mask(hit[t]);
+#endif
+    uint64_t tlm[N];
+#pragma unroll
+    for (int t = 0; t < N; ++t) tlm[t] = (abl & 1u) ? 0ull : hasm[t] & ~hitm[t];
     if constexpr (!T64) {
         // packed cursors: the round appends to the 12-byte class only (the indexer's one class); a key
         // of 13..16 bytes goes through the cold block below.  Every token's append in one LDS round
         // trip (a lane adds 0 for a token that hit): the add returns the record index and the
         // region's end together
-        bool hot[N], anyt = false;
+        uint64_t hotm[N], anytm = 0;
 #pragma unroll
         for (int t = 0; t < N; ++t) {
-            hot[t] = tl[t] && !w16[t];
-            anyt = anyt || hot[t];
+            hotm[t] = tlm[t] & ~w16m[t];
+            anytm |= hotm[t];
         }
         uint64_t ce[N];
-        if (anyt) {
+        if (lane_of(anytm)) {
 #pragma unroll
-            for (int t = 0; t < N; ++t) ce[t] = atomicAdd(&R.cur[b[t]], hot[t] ? 1ull : 0ull);
+            for (int t = 0; t < N; ++t) ce[t] = atomicAdd(&R.cur[b[t]], lane_of(hotm[t]) ? 1ull : 0ull);
         } else {
 #pragma unroll
             for (int t = 0; t < N; ++t) ce[t] = 0;
@@ -732,47 +766,48 @@ __device__ __forceinline__ void emit_fastN(const MapArgs &A, uint32_t abl, uint3
         // and, wc, a key of 13..16 bytes (the cold append; the order of appends within a region matters
         // to no reader).  A stored token is a hot one and a hot one a tail token, so "a tail token, not
         // stored" is exactly those two.
-        bool rare = false, ok[N];
+        uint64_t rarem = 0, okm[N];
 #pragma unroll
         for (int t = 0; t < N; ++t) {
             const uint32_t i = (uint32_t)ce[t];
-            ok[t] = hot[t] && i < (uint32_t)(ce[t] >> 32);
-            if (ok[t]) store_tail32<IDX>(pool, i, k0[t], k1[t], docid);
-            rare = rare || (tl[t] != ok[t]);
+            okm[t] = hotm[t] & wave_mask(i < (uint32_t)(ce[t] >> 32));
+            if (lane_of(okm[t])) store_tail32<IDX>(pool, i, k0[t], k1[t], docid);
+            rarem |= tlm[t] ^ okm[t];
         }
-        if (__any(rare)) {
+        if (rarem) {
 #pragma unroll
             for (int t = 0; t < N; ++t) {
-                if (hot[t] && !ok[t]) ovf_append<IDX>(A, b[t], k0[t], k1[t], docid);
+                if (lane_of(hotm[t] & ~okm[t])) ovf_append<IDX>(A, b[t], k0[t], k1[t], docid);
                 if constexpr (!IDX)
-                    if (tl[t] && !hot[t]) tail16_append(A, R, pool16, b[t], k0[t], k1[t]);
+                    if (lane_of(tlm[t] & ~hotm[t])) tail16_append(A, R, pool16, b[t], k0[t], k1[t]);
             }
         }
     } else {
-    bool anyt = false;
+    uint64_t anytm = 0;
 #pragma unroll
-    for (int t = 0; t < N; ++t) anyt = anyt || tl[t];
+    for (int t = 0; t < N; ++t) anytm |= tlm[t];
     // every token's append in one LDS round trip (a lane adds 0 for a token that hit)
     uint64_t idx[N];
-    if (anyt) {
+    if (lane_of(anytm)) {
 #pragma unroll
-        for (int t = 0; t < N; ++t) idx[t] = atomicAdd(&(w16[t] ? R.cur16 : R.cur)[b[t]], tl[t] ? 1ull : 0ull);
+        for (int t = 0; t < N; ++t)
+            idx[t] = atomicAdd(&(lane_of(w16m[t]) ? R.cur16 : R.cur)[b[t]], lane_of(tlm[t]) ? 1ull : 0ull);
     } else {
 #pragma unroll
         for (int t = 0; t < N; ++t) idx[t] = 0;
     }
-    bool anyo = false, ovf[N];
+    uint64_t anyom = 0, ovfm[N];
 #pragma unroll
     for (int t = 0; t < N; ++t) {
-        const bool ok = tl[t] && idx[t] < end[t];
-        if (ok) store_tail<IDX>(pool, pool16, w16[t], idx[t], k0[t], k1[t], docid);
-        ovf[t] = tl[t] && !ok;
-        anyo = anyo || ovf[t];
+        const uint64_t okm = tlm[t] & wave_mask(idx[t] < end[t]);
+        if (lane_of(okm)) store_tail<IDX>(pool, pool16, lane_of(w16m[t]), idx[t], k0[t], k1[t], docid);
+        ovfm[t] = tlm[t] & ~okm;
+        anyom |= ovfm[t];
     }
-    if (__any(anyo)) {  // region full (rare): the bucket's shared overflow list
+    if (anyom) {  // region full (rare): the bucket's shared overflow list
 #pragma unroll
         for (int t = 0; t < N; ++t)
-            if (ovf[t]) ovf_append<IDX>(A, b[t], k0[t], k1[t], docid);
+            if (lane_of(ovfm[t])) ovf_append<IDX>(A, b[t], k0[t], k1[t], docid);
     }
     }
 }
@@ -1195,8 +1230,11 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
     // s / 16 and s / 16 + 1, its key bytes from the window.  fast: a key of <= 16 bytes ending
     // inside the 2-segment window; slow: the rest (the
     // exact walker).  Returns the deleted-byte runs still to squeeze out (more than one).
-    auto extract = [&](uint32_t q, uint32_t sraw, uint32_t total, bool &fast, bool &slow, uint32_t &s,
-                       uint64_t &tk0, uint64_t &tk1) -> uint32_t {
+    // klen: the key's bytes before any squeeze (a fast token's only; the caller takes the squeezed
+    // bytes off).
+    // fastm / slowm: the lanes whose token is fast / slow, as lane masks (wave_mask).
+    auto extract = [&](uint32_t q, uint32_t sraw, uint32_t total, uint64_t &fastm, uint64_t &slowm, uint32_t &s,
+                       uint64_t &tk0, uint64_t &tk1, uint32_t &klen) -> uint32_t {
         const bool act = q < total;
         s = act ? sraw : 0u;
         uint32_t Wp, Sp;
@@ -1217,10 +1255,12 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
         const uint32_t first = (uint32_t)__builtin_ctz(w | 0x80000000u);
         const uint32_t last = 31u - (uint32_t)__builtin_clz(w | 1u);
         const uint32_t span = last - first + 1u;
-        // bitwise on purpose: lane masks combined by SALU, no per-lane selects
-        const bool wz = w == 0u, big = span > 16u;
-        fast = act & ended & !wz & !big;
-        slow = act & (!ended | (!wz & big));
+        // lane masks combined by the SALU, no per-lane selects; each ballot is its compare's result
+        const uint64_t actm = wave_mask(act), endm = wave_mask(ended), wzm = wave_mask(w == 0u),
+                       bigm = wave_mask(span > 16u);
+        fastm = actm & endm & ~wzm & ~bigm;
+        slowm = actm & (~endm | (~wzm & bigm));
+        const bool fast = lane_of(fastm);
         // deleted bytes inside the token ("don't"): one 1-byte gap is folded into the selectors
         // below (key bytes from the gap on come from one window byte later); tokens with more
         // gaps squeeze them out afterwards
@@ -1228,6 +1268,7 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
         const bool one_gap = gaps != 0u && (gaps & (gaps - 1u)) == 0u;
         const uint32_t ga = one_gap ? (uint32_t)__builtin_ctz(gaps) : 16u;
         uint32_t tlen = one_gap ? span - 1u : span;
+        klen = tlen;
         // key bytes of the window from s + first, big-endian packed, zero padded: output byte p
         // of word j is key byte 4j + 3 - p (selector r + 3 - p [+ 1 past the gap], 0x0C = zero)
         // the 17 window bytes from the key's first byte as five dwords: one unaligned 16-byte
@@ -1409,7 +1450,8 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
         // carries its class, so the W / S masks mean the same.  Invalid UTF-8 defers the block's tiles
         // to generic_tile after the main loop (which reports the first bad byte).
         bool defer_blk = false;
-        if (!(abl & 256u) && !(MRG_MAP_ABL_CONST & 0x20000u) && __any(n0 || n1 || (ln <= 1u && ne))) {
+        if (!(abl & 256u) && !(MRG_MAP_ABL_CONST & 0x20000u) &&
+            (wave_mask(n0) | wave_mask(n1) | (wave_mask(ln <= 1u) & wave_mask(ne))) != 0ull) {
 #ifdef MRG_MAP_NO_UNI
             defer_blk = true;  // A/B builds only: every such block to the exact walker, as in r03
 #else
@@ -1657,39 +1699,41 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
         auto rounds = [&](uint32_t total, bool may_claim) -> uint32_t {
             uint32_t nslow = 0;
             for (uint32_t base = 0; base < total; base += 128) {
-                bool fa, sa, fb, sb;
-                uint32_t sA, sB;
+                uint64_t fa, ma, fb, mb;  // lane masks: fast and slow tokens
+                uint32_t sA, sB, la, lb;
                 uint64_t a0, a1, b0, b1;
                 // both queue entries first, unconditionally (entries past `total` are stale but in
                 // bounds), so the two chains share every LDS wait
                 const uint32_t qa = base + (uint32_t)lane, qb = qa + 64u;
                 const uint32_t ra = queue[min(qa, (uint32_t)QROW - 1u)], rb = queue[min(qb, (uint32_t)QROW - 1u)];
-                uint32_t ga = extract(qa, ra, total, fa, sa, sA, a0, a1);
-                uint32_t gb = extract(qb, rb, total, fb, sb, sB, b0, b1);
+                uint32_t ga = extract(qa, ra, total, fa, ma, sA, a0, a1, la);
+                uint32_t gb = extract(qb, rb, total, fb, mb, sB, b0, b1, lb);
                 if (!(abl & 1024u) && __any((ga | gb) != 0u)) {
+                    la -= (uint32_t)__builtin_popcount(ga);  // the key loses the bytes squeezed out
+                    lb -= (uint32_t)__builtin_popcount(gb);
                     squeeze(ga, a0, a1);
                     squeeze(gb, b0, b1);
                 }
                 // slow tokens (past the 2-segment window, or > 16 raw key bytes) are deferred: their
                 // starts go to the consumed front of the queue (every lane has read both its entries,
                 // and the deferred count never exceeds the entries read so far)
-                const uint64_t ma = __ballot(sa), mb = __ballot(sb);
                 if (ma | mb) {
                     const uint32_t ra = __builtin_amdgcn_mbcnt_hi((uint32_t)(ma >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ma, 0u));
                     const uint32_t rb = __builtin_amdgcn_mbcnt_hi((uint32_t)(mb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mb, 0u));
                     const uint32_t na = (uint32_t)__builtin_popcountll(ma);
-                    if (sa) queue[nslow + ra] = (uint16_t)sA;
-                    if (sb) queue[nslow + na + rb] = (uint16_t)sB;
+                    if (lane_of(ma)) queue[nslow + ra] = (uint16_t)sA;
+                    if (lane_of(mb)) queue[nslow + na + rb] = (uint16_t)sB;
                     nslow += na + (uint32_t)__builtin_popcountll(mb);
                 }
-                my_tokens += (fa ? 1u : 0u) + (fb ? 1u : 0u);
-                const bool hv[2] = {fa, fb};
+                my_tokens += (lane_of(fa) ? 1u : 0u) + (lane_of(fb) ? 1u : 0u);
+                const uint64_t hv[2] = {fa, fb};
                 const uint64_t kk0[2] = {a0, b0}, kk1[2] = {a1, b1};
+                const uint32_t kl[2] = {la, lb};
                 if constexpr (WIDE) {
-                    wide_store(A, tails, fa, a0, a1);
-                    wide_store(A, tails, fb, b0, b1);
+                    wide_store(A, tails, lane_of(fa), a0, a1);
+                    wide_store(A, tails, lane_of(fb), b0, b1);
                 } else {
-                    emit_fastN<2, CAP, IDX, T64>(A, abl, hbits, table, tails, pool, pool16, hv, kk0, kk1, docid, may_claim);
+                    emit_fastN<2, CAP, IDX, T64>(A, abl, hbits, table, tails, pool, pool16, hv, kk0, kk1, kl, docid, may_claim);
                 }
             }
             return nslow;
