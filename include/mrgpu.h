@@ -122,7 +122,9 @@ typedef struct {
  * MRG_ID_UNK
  * (6, additive): mrg_vocab_from_text, mrg_vocab_decode
  * (6, additive): mrg_vocab_term_counts
- * (6, additive): mrg_vocab_postings */
+ * (6, additive): mrg_vocab_postings
+ * (6, additive): mrg_vocab_search
+ * (6, additive): mrg_vocab_stats_add, mrg_vocab_search_shard, mrg_search_merge, MRG_SEARCH_MAX_SHARDS */
 #define MRG_ABI_VERSION 6
 
 const char *mrg_last_error(void);
@@ -387,6 +389,73 @@ int mrg_vocab_search(mrg_ctx *ctx, const mrg_vocab *v, const uint64_t *d_post_of
                      const uint32_t *d_tf, uint64_t n_entries, const uint32_t *d_doc_len, uint32_t n_docs,
                      uint32_t doc_base, const uint32_t *d_q_ids, const uint64_t *h_q_off, uint32_t n_queries,
                      float k1, float b, uint32_t k, uint32_t *d_top_docs, float *d_top_scores, uint32_t *h_top_n);
+
+/* ---- search over a sharded index (6, additive) ----
+ * An index built batch by batch (mrg_vocab_postings with doc_base), or on the GPUs of one job, is a set of shards:
+ * each holds all the postings of its own documents, and the shards partition the collection.  Three calls search
+ * them as one: mrg_vocab_stats_add gathers the collection's statistics, mrg_vocab_search_shard scores one shard
+ * with them, mrg_search_merge merges the shards' rows.  The result is, byte for byte, that of mrg_vocab_search
+ * over the index in one piece: a cell of a score row receives the same float additions in the same query order
+ * from the same idf and avgdl floats, a shard's selection is exact under the total order (score descending,
+ * document ascending), so the collection's top-k is a subset of the union of the shards' top-k.
+ *
+ * mrg_vocab_stats_add: one shard's part of the statistics.  d_df (device memory, the vocabulary's words uint64,
+ * 8-byte aligned, zeroed by the caller before the first shard) receives d_df[w] += d_post_off[w+1] -
+ * d_post_off[w]; h_coll (two host uint64 that the caller starts at 0) receives h_coll[0] += n_docs and
+ * h_coll[1] += the sum of d_doc_len (n_docs uint32 on the device, summed there in integers).  Integers only: the
+ * result does not depend on the order of the shards.  d_df is a plain array on purpose: the shards of a multi-GPU
+ * job add their arrays with whatever all-reduce the host has, or through host memory.
+ * Checked before any device work, MRG_EINVAL with nothing written: a NULL context, vocabulary, d_post_off, d_df
+ * or h_coll, NULL d_doc_len with n_docs > 0, misaligned pointers (8 bytes; d_doc_len 4), a vocabulary of another
+ * device.  Checked on the device: d_post_off[w+1] < d_post_off[w] is MRG_EINVAL, mrg_last_error names the
+ * smallest such word ("word N"), h_coll is untouched and d_df then unspecified.  An empty vocabulary or n_docs =
+ * 0 is valid.  Needs no job; runs on the context's stream with 16 bytes of pool scratch, returned on every exit. */
+int mrg_vocab_stats_add(mrg_ctx *ctx, const mrg_vocab *v, const uint64_t *d_post_off, const uint32_t *d_doc_len,
+                        uint32_t n_docs, uint64_t *d_df, uint64_t *h_coll);
+/* mrg_vocab_search_shard: mrg_vocab_search over one shard, scored with the collection's statistics.  Everything
+ * is as for mrg_vocab_search -- layout, validation, chunking by MRG_SEARCH_ACC_BYTES, output rows, the exact
+ * k-th place, the "index N" and "posting N" errors, scratch (8 more bytes per query id) -- except
+ *   N = coll_docs;  avgdl = coll_sum_len / coll_docs    (in double, rounded to float; 1 when every length is 0)
+ *   df(t) = d_df[t]
+ * with d_df, coll_docs = h_coll[0] and coll_sum_len = h_coll[1] as mrg_vocab_stats_add left them after the last
+ * shard.  The shard's own d_post_off still decides which postings are visited: a word with no postings in this
+ * shard counts nothing, whatever its d_df.  The documents of the rows carry the shard's doc_base.
+ * Refused in addition, MRG_EINVAL: before any device work a NULL or misaligned (8 bytes) d_df when the vocabulary
+ * has words, coll_docs < n_docs, coll_docs > 2^32; from the gathered values, before any accumulate launch, for a
+ * word the queries name that has postings in this shard: d_df[t] below the shard's own document frequency or
+ * above coll_docs ("d_df of word N").
+ * With the statistics of this one index the output is byte-identical to mrg_vocab_search. */
+int mrg_vocab_search_shard(mrg_ctx *ctx, const mrg_vocab *v, const uint64_t *d_post_off, const uint32_t *d_docs,
+                           const uint32_t *d_tf, uint64_t n_entries, const uint32_t *d_doc_len, uint32_t n_docs,
+                           uint32_t doc_base, const uint64_t *d_df, uint64_t coll_docs, uint64_t coll_sum_len,
+                           const uint32_t *d_q_ids, const uint64_t *h_q_off, uint32_t n_queries, float k1, float b,
+                           uint32_t k, uint32_t *d_top_docs, float *d_top_scores, uint32_t *h_top_n);
+/* mrg_search_merge: the result rows of n_shards searches over the same n_queries queries -> the collection's
+ * rows, on the device.  Row [s, q] of the input is d_in_docs[(s * n_queries + q) * k_in ..] with d_in_scores at
+ * the same positions and h_in_top_n[s * n_queries + q] entries: a shard's search with k = k_in writes its rows
+ * straight into its slice of the buffers and its counts into its slice of h_in_top_n; rows of other devices, at
+ * most 8 KiB per query, are the caller's to copy.  The output is laid out like the search's: row q of k_out
+ * slots, h_top_n[q] = min(k_out, the sum over s of the in-counts), by score descending, then document ascending,
+ * then shard ascending -- the last key makes the order total should a caller pass shards that overlap, which is
+ * neither checked nor an error.  The entries of a row from h_top_n[q] on are not written.  Two calls give
+ * identical bytes.
+ * When the shards partition the documents and every shard was searched with k >= k_out (documented, not
+ * checked), the merged rows equal those of mrg_vocab_search over the whole collection with k = k_out, byte for
+ * byte.  The output of a merge is a valid input row, so more than MRG_SEARCH_MAX_SHARDS shards merge in stages.
+ * Checked before any device work, MRG_EINVAL with every output untouched: NULL pointers, misaligned device
+ * pointers (4 bytes), n_shards outside 1..MRG_SEARCH_MAX_SHARDS, k_in or k_out outside 1..MRG_SEARCH_MAX_K, an
+ * in-count above k_in, n_shards * n_queries * k_in >= 2^32.  Checked in the kernel, MRG_EINVAL with the outputs
+ * unspecified: every used entry has a score that is positive and no NaN, and stands strictly after its
+ * predecessor in its row -- a lower score, or an equal score and a higher document (mrg_last_error names the
+ * smallest offending flat index in d_in_docs, "entry N").  The call never writes outside the output rows.
+ * n_queries = 0 or all counts 0: h_top_n all 0, MRG_OK.
+ * The call needs no job and touches no job state.  It runs on the context's stream with scratch from the
+ * context's pool (4 bytes per input row), returned before the call ends, on error exits too; on return the
+ * outputs are complete. */
+#define MRG_SEARCH_MAX_SHARDS 64u
+int mrg_search_merge(mrg_ctx *ctx, uint32_t n_shards, uint32_t n_queries, uint32_t k_in, const uint32_t *d_in_docs,
+                     const float *d_in_scores, const uint32_t *h_in_top_n, uint32_t k_out, uint32_t *d_top_docs,
+                     float *d_top_scores, uint32_t *h_top_n);
 
 /* ---- multi-GPU: one rank per GPU, the shuffle as an RCCL all-to-all over xGMI ----
  * The reference moves map output to the reduce workers through mr-{m}-{r}.txt files in a shared

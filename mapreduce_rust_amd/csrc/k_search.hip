@@ -52,13 +52,14 @@ inline unsigned grid_for(uint64_t n, uint64_t b = SRCH_WG) { return (unsigned)st
 // ---------------------------------------------------------------- plan
 
 __global__ __launch_bounds__(SRCH_WG) void k_srch_gather(const uint32_t *q_ids, uint64_t n_ids, const uint64_t *post_off,
-                                                        uint64_t n_words, uint64_t *po) {
+                                                        uint64_t n_words, uint64_t *po, const uint64_t *df, uint64_t *dfo) {
     const uint64_t i = (uint64_t)blockIdx.x * SRCH_WG + threadIdx.x;
     if (i >= n_ids) return;
     const uint32_t t = q_ids[i];
     const bool ok = (uint64_t)t < n_words;  // (post_off has n_words + 1 entries)
     po[2 * i] = ok ? post_off[t] : 0ull;
     po[2 * i + 1] = ok ? post_off[(uint64_t)t + 1u] : 0ull;
+    if (df) dfo[i] = ok ? df[t] : 0ull;  // (a sharded search: the collection's document frequency)
 }
 
 __global__ __launch_bounds__(SRCH_WG) void k_srch_sum(const uint32_t *doc_len, uint32_t n_docs, unsigned long long *sum) {
@@ -304,8 +305,10 @@ __global__ __launch_bounds__(SRCH_WG) void k_srch_order(SearchPlan A) {
 }  // namespace
 
 void mrg_search_launch_gather(const uint32_t *q_ids, uint64_t n_ids, const uint64_t *post_off, uint64_t n_words,
-                              uint64_t *po, hipStream_t s) {
-    if (n_ids) hipLaunchKernelGGL(k_srch_gather, dim3(grid_for(n_ids)), dim3(SRCH_WG), 0, s, q_ids, n_ids, post_off, n_words, po);
+                              uint64_t *po, hipStream_t s, const uint64_t *df, uint64_t *dfo) {
+    if (n_ids)
+        hipLaunchKernelGGL(k_srch_gather, dim3(grid_for(n_ids)), dim3(SRCH_WG), 0, s, q_ids, n_ids, post_off, n_words, po, df,
+                           dfo);
 }
 
 void mrg_search_launch_sum(const uint32_t *doc_len, uint32_t n_docs, unsigned long long *sum, hipStream_t s) {

@@ -711,15 +711,31 @@ struct SearchPlan {
     float *out_scores;
 };
 #define MRG_SEARCH_SEL_TILE 1024u
-// po[2 i], po[2 i + 1] = post_off[id], post_off[id + 1] of query id i (0, 0 for an id >= n_words)
+// po[2 i], po[2 i + 1] = post_off[id], post_off[id + 1] of query id i (0, 0 for an id >= n_words); with df
+// (mrg_vocab_search_shard: the collection's document frequencies) also dfo[i] = df[id] (0 likewise)
 void mrg_search_launch_gather(const uint32_t *q_ids, uint64_t n_ids, const uint64_t *post_off, uint64_t n_words,
-                              uint64_t *po, hipStream_t s);
+                              uint64_t *po, hipStream_t s, const uint64_t *df = nullptr, uint64_t *dfo = nullptr);
 void mrg_search_launch_sum(const uint32_t *doc_len, uint32_t n_docs, unsigned long long *sum, hipStream_t s);  // *sum zeroed
 // acc[row][doc - doc_base] += w for the n tiles at `tiles`, which belong to one position of the chunk's queries
 void mrg_search_launch_acc(const SearchPlan &p, const SearchTile *tiles, uint64_t n, hipStream_t s);
 // the chunk's rows -> top_n[q0 ..] and the candidates (select, ordered compaction) -> the output rows q0 ..
 void mrg_search_launch_select(const SearchPlan &p, hipStream_t s);
 void mrg_search_launch_order(const SearchPlan &p, hipStream_t s);
+
+// ---- k_merge.hip: the statistics and the merge of a sharded search
+// df[w] += post_off[w + 1] - post_off[w] for the n_words words; *err (all ones): the smallest word whose
+// offsets descend
+void mrg_stats_launch_df(const uint64_t *post_off, uint64_t n_words, unsigned long long *df, unsigned long long *err,
+                         hipStream_t s);
+// One mrg_search_merge call: row (s, q) of the input is in_docs / in_bits[(s * n_queries + q) * k_in ..] with
+// in_n[s * n_queries + q] <= k_in entries (a device copy of the host counts); row q of the output has k_out slots.
+struct MergePlan {
+    const uint32_t *in_docs, *in_bits, *in_n;
+    uint32_t n_shards, n_queries, k_in, k_out;
+    uint32_t *out_docs, *out_bits;
+    unsigned long long *err;     // all ones: smallest flat index of an entry that is no score or out of order
+};
+void mrg_merge_launch(const MergePlan &m, hipStream_t s);
 
 // ---- k_gen.hip
 int mrg_gen_zipf_impl(uint8_t *dst, uint64_t n, uint64_t seed, uint64_t file_index, uint32_t vocab, double s, uint32_t style,

@@ -1,6 +1,6 @@
 // mrg_vocab.cpp -- the vocabulary calls of libmrgpu.so (include/mrgpu.h): a vocabulary from a job's ranked keys
-// or from text, text -> ids, ids -> text, per-document term counts, the inverted index, BM25 search over it; and
-// their diagnostics.
+// or from text, text -> ids, ids -> text, per-document term counts, the inverted index, BM25 search over it -- in
+// one piece, or in shards with the collection's statistics and a merge of the shards' rows; and their diagnostics.
 // Apart from mrg_job_vocab, which ranks the job's keys through job_topk, no call touches job state: each uses the
 // context's device, stream, timing switch and pool, whose scratch goes back on every exit, and its own VocDiag.
 #include <math.h>
@@ -637,10 +637,16 @@ void vocab_postings(mrg_ctx *c, const mrg_vocab *v, const uint32_t *d_terms, con
 // lengths come back in one stream wait; the host validates, computes the idfs and cuts the segments into tiles.
 // Then the queries go in chunks of dense score rows: one accumulate launch per query position, the radix select
 // with the ordered compaction, the ordering of the candidates.
+// cs (mrg_vocab_search_shard): the index is one shard of a collection; N, avgdl and every df are the collection's.
+struct CollStats {
+    const uint64_t *d_df;
+    uint64_t docs, sum_len;
+};
 void vocab_search(mrg_ctx *c, const mrg_vocab *v, const uint64_t *d_post_off, const uint32_t *d_docs, const uint32_t *d_tf,
                   uint64_t n_entries, const uint32_t *d_doc_len, uint32_t n_docs, uint32_t doc_base, const uint32_t *d_q_ids,
                   const uint64_t *h_q_off, uint32_t n_queries, float k1, float b, uint32_t k, uint32_t *d_top_docs,
-                  float *d_top_scores, uint32_t *h_top_n) {
+                  float *d_top_scores, uint32_t *h_top_n, const CollStats *cs = nullptr) {
+    const char *fn = cs ? "mrg_vocab_search_shard" : "mrg_vocab_search";
     voc_args(c, v, n_queries);
     if (!d_post_off) raise(MRG_EINVAL, "null d_post_off (the vocabulary's words + 1 offsets of mrg_vocab_postings)");
     if (!h_q_off) raise(MRG_EINVAL, "null offsets (h_q_off needs n_queries + 1 entries)");
@@ -654,14 +660,21 @@ void vocab_search(mrg_ctx *c, const mrg_vocab *v, const uint64_t *d_post_off, co
     if ((uintptr_t)d_post_off & 7u) raise(MRG_EINVAL, "d_post_off must be 8-byte aligned");
     if ((uint64_t)doc_base + n_docs > (1ull << 32))
         raise(MRG_EINVAL, "doc_base + n_docs = %llu: documents are 32 bits", (unsigned long long)doc_base + n_docs);
-    if (n_entries > 0xFFFFFFFFull) raise(MRG_EINVAL, "mrg_vocab_search: %llu entries: at most 4294967295",
+    if (n_entries > 0xFFFFFFFFull) raise(MRG_EINVAL, "%s: %llu entries: at most 4294967295", fn,
                                          (unsigned long long)n_entries);
+    if (cs) {
+        if (v->n && !cs->d_df) raise(MRG_EINVAL, "null d_df (the collection's document frequencies: mrg_vocab_stats_add)");
+        if ((uintptr_t)cs->d_df & 7u) raise(MRG_EINVAL, "d_df must be 8-byte aligned");
+        if (cs->docs < n_docs) raise(MRG_EINVAL, "coll_docs = %llu: the shard alone has %u documents",
+                                     (unsigned long long)cs->docs, n_docs);
+        if (cs->docs > (1ull << 32)) raise(MRG_EINVAL, "coll_docs = %llu: documents are 32 bits", (unsigned long long)cs->docs);
+    }
     if (k < 1u || k > MRG_SEARCH_MAX_K) raise(MRG_EINVAL, "k = %u: 1 to %u", k, MRG_SEARCH_MAX_K);
     if (!(k1 >= 0.0f && k1 <= 1000.0f)) raise(MRG_EINVAL, "k1 = %g: 0 to 1000", (double)k1);
     if (!(b >= 0.0f && b <= 1.0f)) raise(MRG_EINVAL, "b = %g: 0 to 1", (double)b);
     voc_enter(c, h_q_off, n_queries, "query offsets must be non-decreasing (query %u)");
     const uint64_t qlo = h_q_off[0], n_ids = h_q_off[n_queries] - qlo;
-    if (n_ids > (1ull << 20)) raise(MRG_EINVAL, "mrg_vocab_search: %llu query ids in one call: at most 1048576",
+    if (n_ids > (1ull << 20)) raise(MRG_EINVAL, "%s: %llu query ids in one call: at most 1048576", fn,
                                     (unsigned long long)n_ids);
     if (n_ids && !d_q_ids) raise(MRG_EINVAL, "null query ids");
     c->srch.clear(4);
@@ -683,24 +696,35 @@ void vocab_search(mrg_ctx *c, const mrg_vocab *v, const uint64_t *d_post_off, co
     unsigned long long *d_small = sc.get<unsigned long long>(2);  // the sum of the lengths, the error position
     HIPCHK(hipMemsetAsync(d_small, 0, 8, s));
     HIPCHK(hipMemsetAsync(d_small + 1, 0xFF, 8, s));
-    mrg_search_launch_gather(d_q_ids + qlo, n_ids, d_post_off, n_words, d_po, s);
-    if (n_entries) mrg_search_launch_sum(d_doc_len, n_docs, d_small, s);
+    uint64_t *d_dfo = cs ? sc.get<uint64_t>(n_ids) : nullptr;  // the collection's df of every query position
+    mrg_search_launch_gather(d_q_ids + qlo, n_ids, d_post_off, n_words, d_po, s, cs ? cs->d_df : nullptr, d_dfo);
+    if (n_entries && !cs) mrg_search_launch_sum(d_doc_len, n_docs, d_small, s);
     HIPCHK(hipGetLastError());
     std::vector<uint32_t> ids(n_ids);
-    std::vector<uint64_t> po(2 * n_ids);
+    std::vector<uint64_t> po(2 * n_ids), dfc(cs ? n_ids : 0);
     unsigned long long sum_len = 0;
+    if (cs) HIPCHK(hipMemcpyAsync(dfc.data(), d_dfo, 8 * n_ids, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(ids.data(), d_q_ids + qlo, 4 * n_ids, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(po.data(), d_po, 16 * n_ids, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(&sum_len, d_small, 8, hipMemcpyDeviceToHost, s));
     sync(c);
     for (uint64_t i = 0; i < n_ids; ++i)
         if (ids[i] != MRG_ID_UNK && ids[i] >= n_words)
-            raise(MRG_EINVAL, "mrg_vocab_search: the id at index %llu is not in the vocabulary (%llu words)",
+            raise(MRG_EINVAL, "%s: the id at index %llu is not in the vocabulary (%llu words)", fn,
                   (unsigned long long)(qlo + i), (unsigned long long)n_words);
     for (uint64_t i = 0; i < n_ids; ++i)
         if (po[2 * i] > po[2 * i + 1] || po[2 * i + 1] > n_entries)
-            raise(MRG_EINVAL, "mrg_vocab_search: d_post_off of word %u: [%llu, %llu) is not a range of the %llu entries", ids[i],
+            raise(MRG_EINVAL, "%s: d_post_off of word %u: [%llu, %llu) is not a range of the %llu entries", fn, ids[i],
                   (unsigned long long)po[2 * i], (unsigned long long)po[2 * i + 1], (unsigned long long)n_entries);
+    if (cs) {  // a word with postings here: the collection has at least the shard's documents of it, at most all
+        sum_len = cs->sum_len;
+        for (uint64_t i = 0; i < n_ids; ++i) {
+            const uint64_t df = po[2 * i + 1] - po[2 * i];
+            if (df && (dfc[i] < df || dfc[i] > cs->docs))
+                raise(MRG_EINVAL, "%s: d_df of word %u: %llu, with %llu documents of it in this shard and %llu in the collection",
+                      fn, ids[i], (unsigned long long)dfc[i], (unsigned long long)df, (unsigned long long)cs->docs);
+        }
+    }
     std::vector<uint32_t> top(n_queries, 0u);
     uint64_t visited = 0;
     for (uint64_t i = 0; i < n_ids; ++i) visited += po[2 * i + 1] - po[2 * i];
@@ -727,7 +751,8 @@ void vocab_search(mrg_ctx *c, const mrg_vocab *v, const uint64_t *d_post_off, co
     P.k1 = k1;
     P.k1p1 = k1 + 1.0f;
     P.b = b;
-    const double avgdl = (double)sum_len / (double)n_docs;
+    const double n_coll = cs ? (double)cs->docs : (double)n_docs;  // N
+    const double avgdl = (double)sum_len / n_coll;
     P.avgdl = avgdl > 0.0 ? (float)avgdl : 1.0f;  // (every length is 0: dl / avgdl counts as 0)
     P.err = d_small + 1;
     P.k = k;
@@ -758,7 +783,11 @@ void vocab_search(mrg_ctx *c, const mrg_vocab *v, const uint64_t *d_post_off, co
                 const uint64_t a = po[2 * (at - qlo)], e = po[2 * (at - qlo) + 1], df = e - a;
                 if (!df) continue;  // MRG_ID_UNK, or a word with no postings
                 // (a df above N cannot ascend strictly inside the collection: the kernel reports it)
-                const double x = df <= n_docs ? ((double)n_docs - (double)df + 0.5) / ((double)df + 0.5) : 0.0;
+                double x = df <= n_docs ? ((double)n_docs - (double)df + 0.5) / ((double)df + 0.5) : 0.0;
+                if (cs) {  // (checked above: the shard's df <= the collection's <= N)
+                    const double dfn = (double)dfc[at - qlo];
+                    x = (n_coll - dfn + 0.5) / (dfn + 0.5);
+                }
                 const float idf = (float)log(1.0 + x);
                 for (uint64_t lo = a; lo < e;) {
                     const uint64_t hi = std::min(e, ((lo + P.shift) / MRG_SEARCH_TILE + 1u) * MRG_SEARCH_TILE - P.shift);
@@ -818,8 +847,98 @@ void vocab_search(mrg_ctx *c, const mrg_vocab *v, const uint64_t *d_post_off, co
     HIPCHK(hipMemcpyAsync(&herr, P.err, 8, hipMemcpyDeviceToHost, s));
     sync(c);  // (also: the pageable tiles have been read)
     if (herr != ~0ull)
-        raise(MRG_EINVAL, "mrg_vocab_search: posting %llu: its document is outside [doc_base, doc_base + n_docs), or not "
-                          "above the document before it in its word's postings", herr);
+        raise(MRG_EINVAL, "%s: posting %llu: its document is outside [doc_base, doc_base + n_docs), or not "
+                          "above the document before it in its word's postings", fn, herr);
+    std::copy(top.begin(), top.end(), h_top_n);
+}
+
+// One shard's part of the collection statistics (k_merge.hip): its document frequencies are
+// added to d_df on the device, its documents and the sum of their lengths to the host totals.
+void vocab_stats_add(mrg_ctx *c, const mrg_vocab *v, const uint64_t *d_post_off, const uint32_t *d_doc_len, uint32_t n_docs,
+                     uint64_t *d_df, uint64_t *h_coll) {
+    voc_args(c, v, n_docs, true);
+    if (!d_post_off) raise(MRG_EINVAL, "null d_post_off (the vocabulary's words + 1 offsets of mrg_vocab_postings)");
+    if (!d_df) raise(MRG_EINVAL, "null d_df (the vocabulary's words uint64, zeroed before the first shard)");
+    if (!h_coll) raise(MRG_EINVAL, "null h_coll (two uint64: the documents and the sum of their lengths)");
+    if (n_docs && !d_doc_len) raise(MRG_EINVAL, "null d_doc_len with %u documents", n_docs);
+    if (((uintptr_t)d_post_off | (uintptr_t)d_df) & 7u) raise(MRG_EINVAL, "d_post_off and d_df must be 8-byte aligned");
+    if ((uintptr_t)d_doc_len & 3u) raise(MRG_EINVAL, "d_doc_len must be 4-byte aligned");
+    HIPCHK(hipSetDevice(c->device));
+    if (!v->n && !n_docs) return;
+    hipStream_t s = c->stream;
+    Scratch sc(c->pool);
+    unsigned long long *d_small = sc.get<unsigned long long>(2);  // the sum of the lengths, the error word
+    HIPCHK(hipMemsetAsync(d_small, 0, 8, s));
+    HIPCHK(hipMemsetAsync(d_small + 1, 0xFF, 8, s));
+    if (v->n) mrg_stats_launch_df(d_post_off, v->n, (unsigned long long *)d_df, d_small + 1, s);
+    mrg_search_launch_sum(d_doc_len, n_docs, d_small, s);
+    HIPCHK(hipGetLastError());
+    unsigned long long h[2] = {};
+    HIPCHK(hipMemcpyAsync(h, d_small, sizeof h, hipMemcpyDeviceToHost, s));
+    sync(c);
+    if (h[1] != ~0ull) raise(MRG_EINVAL, "mrg_vocab_stats_add: d_post_off of word %llu: the offsets must be non-decreasing", h[1]);
+    h_coll[0] += n_docs;
+    h_coll[1] += h[0];
+}
+
+// The result rows of the shards of one collection -> the collection's rows (k_merge.hip).
+void search_merge(mrg_ctx *c, uint32_t n_shards, uint32_t n_queries, uint32_t k_in, const uint32_t *d_in_docs,
+                  const float *d_in_scores, const uint32_t *h_in_top_n, uint32_t k_out, uint32_t *d_top_docs,
+                  float *d_top_scores, uint32_t *h_top_n) {
+    if (!c) raise(MRG_EINVAL, "null context");
+    if (!d_in_docs || !d_in_scores || !h_in_top_n)
+        raise(MRG_EINVAL, "null input (d_in_docs and d_in_scores: n_shards * n_queries * k_in entries, h_in_top_n: n_shards * "
+                          "n_queries)");
+    if (!d_top_docs || !d_top_scores || !h_top_n)
+        raise(MRG_EINVAL, "null output (d_top_docs and d_top_scores need n_queries * k_out entries, h_top_n n_queries)");
+    if (((uintptr_t)d_in_docs | (uintptr_t)d_in_scores | (uintptr_t)d_top_docs | (uintptr_t)d_top_scores) & 3u)
+        raise(MRG_EINVAL, "d_in_docs, d_in_scores, d_top_docs and d_top_scores must be 4-byte aligned");
+    if (n_shards < 1u || n_shards > MRG_SEARCH_MAX_SHARDS)
+        raise(MRG_EINVAL, "n_shards = %u: 1 to %u (more shards merge in stages)", n_shards, MRG_SEARCH_MAX_SHARDS);
+    if (k_in < 1u || k_in > MRG_SEARCH_MAX_K) raise(MRG_EINVAL, "k_in = %u: 1 to %u", k_in, MRG_SEARCH_MAX_K);
+    if (k_out < 1u || k_out > MRG_SEARCH_MAX_K) raise(MRG_EINVAL, "k_out = %u: 1 to %u", k_out, MRG_SEARCH_MAX_K);
+    const uint64_t n_rows = (uint64_t)n_shards * n_queries;
+    if (n_rows * k_in > 0xFFFFFFFFull)
+        raise(MRG_EINVAL, "mrg_search_merge: %llu input entries: at most 4294967295", (unsigned long long)(n_rows * k_in));
+    for (uint64_t r = 0; r < n_rows; ++r)
+        if (h_in_top_n[r] > k_in)
+            raise(MRG_EINVAL, "mrg_search_merge: h_in_top_n[%llu] = %u is above k_in = %u", (unsigned long long)r, h_in_top_n[r],
+                  k_in);
+    HIPCHK(hipSetDevice(c->device));
+    std::vector<uint32_t> top(n_queries, 0u);
+    bool any = false;
+    for (uint32_t q = 0; q < n_queries; ++q) {
+        uint64_t sum = 0;
+        for (uint32_t sh = 0; sh < n_shards; ++sh) sum += h_in_top_n[(uint64_t)sh * n_queries + q];
+        top[q] = (uint32_t)std::min<uint64_t>(sum, k_out);
+        any = any || sum;
+    }
+    if (any) {
+        hipStream_t s = c->stream;
+        Scratch sc(c->pool);
+        MergePlan M{};
+        uint32_t *d_n = sc.get<uint32_t>(n_rows);
+        M.err = sc.get<unsigned long long>(1);
+        HIPCHK(hipMemcpyAsync(d_n, h_in_top_n, 4 * n_rows, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemsetAsync(M.err, 0xFF, 8, s));
+        M.in_docs = d_in_docs;
+        M.in_bits = (const uint32_t *)d_in_scores;
+        M.in_n = d_n;
+        M.n_shards = n_shards;
+        M.n_queries = n_queries;
+        M.k_in = k_in;
+        M.k_out = k_out;
+        M.out_docs = d_top_docs;
+        M.out_bits = (uint32_t *)d_top_scores;
+        mrg_merge_launch(M, s);
+        HIPCHK(hipGetLastError());
+        unsigned long long herr = 0;
+        HIPCHK(hipMemcpyAsync(&herr, M.err, 8, hipMemcpyDeviceToHost, s));
+        sync(c);  // (also: the pageable counts have been read)
+        if (herr != ~0ull)
+            raise(MRG_EINVAL, "mrg_search_merge: entry %llu: its score is not positive or a NaN, or it does not stand after the "
+                              "entry before it in its row (score descending, then document ascending)", herr);
+    }
     std::copy(top.begin(), top.end(), h_top_n);
 }
 
@@ -921,7 +1040,33 @@ int mrg_vocab_search(mrg_ctx *c, const mrg_vocab *v, const uint64_t *d_post_off,
     });
 }
 
-// Diagnostics of the last mrg_vocab_search (not in include/mrgpu.h; tools/time_search.py): h_info[0..6) =
+int mrg_vocab_stats_add(mrg_ctx *c, const mrg_vocab *v, const uint64_t *d_post_off, const uint32_t *d_doc_len, uint32_t n_docs,
+                        uint64_t *d_df, uint64_t *h_coll) {
+    return guard([&] { vocab_stats_add(c, v, d_post_off, d_doc_len, n_docs, d_df, h_coll); });
+}
+
+int mrg_vocab_search_shard(mrg_ctx *c, const mrg_vocab *v, const uint64_t *d_post_off, const uint32_t *d_docs,
+                           const uint32_t *d_tf, uint64_t n_entries, const uint32_t *d_doc_len, uint32_t n_docs,
+                           uint32_t doc_base, const uint64_t *d_df, uint64_t coll_docs, uint64_t coll_sum_len,
+                           const uint32_t *d_q_ids, const uint64_t *h_q_off, uint32_t n_queries, float k1, float b, uint32_t k,
+                           uint32_t *d_top_docs, float *d_top_scores, uint32_t *h_top_n) {
+    return guard([&] {
+        const CollStats cs{d_df, coll_docs, coll_sum_len};
+        vocab_search(c, v, d_post_off, d_docs, d_tf, n_entries, d_doc_len, n_docs, doc_base, d_q_ids, h_q_off, n_queries, k1, b,
+                     k, d_top_docs, d_top_scores, h_top_n, &cs);
+    });
+}
+
+int mrg_search_merge(mrg_ctx *c, uint32_t n_shards, uint32_t n_queries, uint32_t k_in, const uint32_t *d_in_docs,
+                     const float *d_in_scores, const uint32_t *h_in_top_n, uint32_t k_out, uint32_t *d_top_docs,
+                     float *d_top_scores, uint32_t *h_top_n) {
+    return guard([&] {
+        search_merge(c, n_shards, n_queries, k_in, d_in_docs, d_in_scores, h_in_top_n, k_out, d_top_docs, d_top_scores, h_top_n);
+    });
+}
+
+// Diagnostics of the last mrg_vocab_search or mrg_vocab_search_shard (not in include/mrgpu.h; tools/time_search.py,
+// tools/time_search_shards.py): h_info[0..6) =
 // queries, query positions, postings visited, chunks, accumulate launches, scratch bytes; h_ms[0..4) = plan,
 // accumulate, select (with the compaction), order, summed over the chunks (HIP events, with mrg_set_timing).
 int mrg_search_info(mrg_ctx *c, uint64_t *h_info, double *h_ms) { return voc_info(c, &mrg_ctx::srch, 4, h_info, h_ms); }

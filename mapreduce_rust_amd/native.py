@@ -33,6 +33,10 @@ POST_TILE = 2048
 # a query returns at most SEARCH_MAX_K documents (MRG_SEARCH_TILE, MRG_SEARCH_MAX_K of csrc/mrg_device.h)
 SEARCH_TILE = 4096
 SEARCH_MAX_K = 1024
+# search_merge: at most SEARCH_MAX_SHARDS rows per query; they are staged in LDS when n_shards * k_in is at most
+# MERGE_LDS_KEYS, and read from global memory otherwise (MRG_SEARCH_MAX_SHARDS, MRG_MERGE_LDS_KEYS of csrc/mrg_device.h)
+SEARCH_MAX_SHARDS = 64
+MERGE_LDS_KEYS = 8192
 
 
 def debug_hash_bits(n):
@@ -133,6 +137,10 @@ _SIGS = {
     "mrg_vocab_postings": (C.c_int, [_vp, _vp, _vp, _vp, _u64p, C.c_uint32, C.c_uint32, _vp, _vp, _vp, C.c_uint64, _u64p]),
     "mrg_vocab_search": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint64, _vp, C.c_uint32, C.c_uint32, _vp, _u64p, C.c_uint32,
                                    C.c_float, C.c_float, C.c_uint32, _vp, _vp, _u32p]),
+    "mrg_vocab_stats_add": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _u64p]),
+    "mrg_vocab_search_shard": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint64, _vp, C.c_uint32, C.c_uint32, _vp, C.c_uint64,
+                                         C.c_uint64, _vp, _u64p, C.c_uint32, C.c_float, C.c_float, C.c_uint32, _vp, _vp, _u32p]),
+    "mrg_search_merge": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _u32p, C.c_uint32, _vp, _vp, _u32p]),
     "mrg_map": (C.c_int, [_vp, C.c_int, C.c_char_p, C.c_size_t, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32,
                           C.POINTER(_vp)]),
     "mrg_parts_get": (C.c_int, [_vp, C.c_uint32, C.POINTER(_vp), _u64p, C.POINTER(_vp), _u64p]),
@@ -551,6 +559,42 @@ class Context:
         _check(load().mrg_vocab_search(self.h, vocab.h, post_off_ptr, docs_ptr, tf_ptr, n_entries, doc_len_ptr, n_docs,
                                        doc_base, q_ids_ptr, _u64arr(q_off), n, k1, b, k, top_docs_ptr, top_scores_ptr, top))
         return list(top)[:n]
+
+    def stats_add(self, vocab, post_off_ptr, doc_len_ptr, n_docs, df_ptr, coll=(0, 0)):
+        """mrg_vocab_stats_add: one shard's part of the collection statistics of a sharded search.  df_ptr (uint64,
+        the vocabulary's words, zeroed before the first shard) receives the shard's document frequencies added in;
+        coll = (documents, sum of the lengths) so far.  Returns the new coll."""
+        h = (C.c_uint64 * 2)(int(coll[0]), int(coll[1]))
+        _check(load().mrg_vocab_stats_add(self.h, vocab.h, post_off_ptr, doc_len_ptr, n_docs, df_ptr, h))
+        return h[0], h[1]
+
+    def search_shard(self, vocab, post_off_ptr, docs_ptr, tf_ptr, n_entries, doc_len_ptr, n_docs, q_ids_ptr, q_off, k,
+                     top_docs_ptr, top_scores_ptr, df_ptr, coll, k1=1.2, b=0.75, doc_base=0):
+        """mrg_vocab_search_shard: search() over one shard of a collection, scored with the collection's statistics:
+        df_ptr and coll = (documents, sum of the lengths) as stats_add left them after the last shard.  The rows
+        of the shards go through search_merge()."""
+        if len(q_off) < 1:
+            raise ValueError("q_off needs n_queries + 1 entries (at least [0])")
+        n = len(q_off) - 1
+        top = (C.c_uint32 * max(n, 1))()
+        _check(load().mrg_vocab_search_shard(self.h, vocab.h, post_off_ptr, docs_ptr, tf_ptr, n_entries, doc_len_ptr, n_docs,
+                                             doc_base, df_ptr, int(coll[0]), int(coll[1]), q_ids_ptr, _u64arr(q_off), n, k1, b,
+                                             k, top_docs_ptr, top_scores_ptr, top))
+        return list(top)[:n]
+
+    def search_merge(self, n_shards, n_queries, k_in, in_docs_ptr, in_scores_ptr, in_top_n, k_out, top_docs_ptr,
+                     top_scores_ptr):
+        """mrg_search_merge: the rows of n_shards searches over the same queries -> the collection's rows.  Row
+        (s, q) of the input is in_docs[(s * n_queries + q) * k_in:][:in_top_n[s * n_queries + q]] with in_scores at
+        the same positions.  Returns top_n: row q of the output is top_docs[q * k_out:q * k_out + top_n[q]], by
+        score descending, then document ascending, then shard ascending; the rest of a row is not written."""
+        in_top_n = [int(x) for x in in_top_n]
+        if len(in_top_n) != n_shards * n_queries:
+            raise ValueError("in_top_n needs n_shards * n_queries entries")
+        top = (C.c_uint32 * max(n_queries, 1))()
+        _check(load().mrg_search_merge(self.h, n_shards, n_queries, k_in, in_docs_ptr, in_scores_ptr,
+                                       (C.c_uint32 * max(len(in_top_n), 1))(*in_top_n), k_out, top_docs_ptr, top_scores_ptr, top))
+        return list(top)[:n_queries]
 
     def search_info(self):
         """Diagnostics of the last search(): queries, query positions, postings visited, chunks, accumulate
