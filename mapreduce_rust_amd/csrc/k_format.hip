@@ -241,16 +241,27 @@ uint64_t mrg_format(const FormatArgs &f, DevPool &pool, uint8_t **out_buf, uint6
     const uint64_t n = f.n;
     const uint32_t R = f.n_reduce;
     SortRec *recs = const_cast<SortRec *>(f.recs);
-    uint64_t *part_off = (uint64_t *)pool.get(sizeof(uint64_t) * (R + 1));
-    uint64_t *total_d = (uint64_t *)pool.get(sizeof(uint64_t) * 2);
+    mrg_host::Scratch sc(pool);  // every temporary of the call
+    // the caller's buffer grown to `bytes` (if the allocation fails the caller holds no buffer, never a returned one)
+    auto grow_out = [&](uint64_t bytes) {
+        if (bytes <= *out_cap) return;
+        uint8_t *old = *out_buf;
+        *out_buf = nullptr;
+        *out_cap = 0;
+        if (old) pool.put(old);
+        *out_buf = mrg_host::pget<uint8_t>(pool, bytes);
+        *out_cap = bytes;
+    };
+    uint64_t *part_off = sc.get<uint64_t>(R + 1);
+    uint64_t *total_d = sc.get<uint64_t>(2);
     // (no memset: k_part_off writes every entry 0..R, also for n == 0)
-    uint64_t *scantmp = (uint64_t *)pool.get(sizeof(uint64_t) * mrg_scan_tmp_elems(n + 1));
+    uint64_t *scantmp = sc.get<uint64_t>(mrg_scan_tmp_elems(n + 1));
     if (n && f.any_long) hipLaunchKernelGGL(k_fix_runs, grid_for(n), dim3(256), 0, s, recs, n, f.ks, f.heap);
 
     uint64_t total = 0;
     if (!f.indexer) {
-        uint64_t *L = (uint64_t *)pool.get(sizeof(uint64_t) * (n + 1));
-        uint64_t *O = (uint64_t *)pool.get(sizeof(uint64_t) * (n + 1));
+        uint64_t *L = sc.get<uint64_t>(n + 1);
+        uint64_t *O = sc.get<uint64_t>(n + 1);
         if (n) {
             hipLaunchKernelGGL(k_wc_len, grid_for(n), dim3(256), 0, s, recs, n, f.ks, f.drop_last, f.carried, L);
             mrg_scan_u64(L, O, n, scantmp, s);
@@ -258,27 +269,19 @@ uint64_t mrg_format(const FormatArgs &f, DevPool &pool, uint8_t **out_buf, uint6
         hipLaunchKernelGGL(k_total, dim3(1), dim3(1), 0, s, L, O, n, total_d);
         // no round trip for the byte count: the buffer is sized by a bound ("key count\n" with at most
         // 16 short-key bytes or the long key's heap bytes, and 20 digits), the count read with part_off
-        const uint64_t bound = n * (16u + 2u + 20u) + f.heap_bytes + 16u;
-        if (bound > *out_cap) {  // (if the allocation fails the caller holds no buffer, never a returned one)
-            uint8_t *old = *out_buf;
-            *out_buf = nullptr;
-            *out_cap = 0;
-            if (old) pool.put(old);
-            *out_buf = (uint8_t *)pool.get(bound);
-            *out_cap = bound;
-        }
+        grow_out(n * (16u + 2u + 20u) + f.heap_bytes + 16u);
         if (n)
             hipLaunchKernelGGL(k_wc_write, grid_for(n), dim3(256), 0, s, recs, n, f.ks, f.heap, L, O, f.carried, *out_buf);
         hipLaunchKernelGGL(k_part_off, grid_for(n + 1), dim3(256), 0, s, recs, O, n, R, (const uint64_t *)nullptr,
                            (const uint64_t *)total_d, part_off);
-        hipMemcpyAsync(&total, total_d, sizeof total, hipMemcpyDeviceToHost, s);
-        pool.put(L);
-        pool.put(O);
+        HIPCHK(hipMemcpyAsync(&total, total_d, sizeof total, hipMemcpyDeviceToHost, s));
+        sc.put(L);
+        sc.put(O);
     } else {
-        uint64_t *head = (uint64_t *)pool.get(sizeof(uint64_t) * (n + 1));
-        uint64_t *E = (uint64_t *)pool.get(sizeof(uint64_t) * (n + 1));
-        uint64_t *nl = (uint64_t *)pool.get(sizeof(uint64_t) * (n + 1));
-        uint64_t *P = (uint64_t *)pool.get(sizeof(uint64_t) * (n + 1));
+        uint64_t *head = sc.get<uint64_t>(n + 1);
+        uint64_t *E = sc.get<uint64_t>(n + 1);
+        uint64_t *nl = sc.get<uint64_t>(n + 1);
+        uint64_t *P = sc.get<uint64_t>(n + 1);
         uint64_t G = 0, Ptot = 0;
         if (n) {
             hipLaunchKernelGGL(k_idx_heads, grid_for(n), dim3(256), 0, s, recs, n, f.ks, f.heap, f.name_off, head, nl);
@@ -286,45 +289,38 @@ uint64_t mrg_format(const FormatArgs &f, DevPool &pool, uint8_t **out_buf, uint6
             mrg_scan_u64(nl, P, n, scantmp, s);
             hipLaunchKernelGGL(k_total, dim3(1), dim3(1), 0, s, head, E, n, total_d);
             hipLaunchKernelGGL(k_total, dim3(1), dim3(1), 0, s, nl, P, n, total_d + 1);
+            HIPCHK(hipGetLastError());
             uint64_t tt[2];
-            hipMemcpyAsync(tt, total_d, sizeof tt, hipMemcpyDeviceToHost, s);
-            hipStreamSynchronize(s);
+            HIPCHK(hipMemcpyAsync(tt, total_d, sizeof tt, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
             G = tt[0];
             Ptot = tt[1];
         }
-        uint64_t *H = (uint64_t *)pool.get(sizeof(uint64_t) * (G + 1));
-        uint64_t *GL = (uint64_t *)pool.get(sizeof(uint64_t) * (G + 1));
-        uint64_t *GO = (uint64_t *)pool.get(sizeof(uint64_t) * (G + 1));
-        SortRec *first = (SortRec *)pool.get(sizeof(SortRec) * (G + 1));
+        uint64_t *H = sc.get<uint64_t>(G + 1);
+        uint64_t *GL = sc.get<uint64_t>(G + 1);
+        uint64_t *GO = sc.get<uint64_t>(G + 1);
+        SortRec *first = sc.get<SortRec>(G + 1);
         if (G) {
             hipLaunchKernelGGL(k_idx_groups, grid_for(n), dim3(256), 0, s, head, E, n, H);
             hipLaunchKernelGGL(k_idx_glen, grid_for(G), dim3(256), 0, s, recs, n, G, f.ks, H, P, Ptot, f.drop_last, GL);
             mrg_scan_u64(GL, GO, G, scantmp, s);
         }
         hipLaunchKernelGGL(k_total, dim3(1), dim3(1), 0, s, GL, GO, G, total_d);
-        hipMemcpyAsync(&total, total_d, sizeof total, hipMemcpyDeviceToHost, s);
-        hipStreamSynchronize(s);
-        if (total + 16 > *out_cap) {
-            uint8_t *old = *out_buf;
-            *out_buf = nullptr;
-            *out_cap = 0;
-            if (old) pool.put(old);
-            *out_buf = (uint8_t *)pool.get(total + 16);
-            *out_cap = total + 16;
-        }
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(&total, total_d, sizeof total, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        grow_out(total + 16);
         if (n)
             hipLaunchKernelGGL(k_idx_write, grid_for(n), dim3(256), 0, s, recs, n, G, f.ks, f.heap, head, E, H, P, GL,
                                GO, f.names, f.name_off, *out_buf);
         if (G) hipLaunchKernelGGL(k_gather_first, grid_for(G), dim3(256), 0, s, recs, H, G, first);
         hipLaunchKernelGGL(k_part_off, grid_for(G + 1), dim3(256), 0, s, first, GO, G, R, (const uint64_t *)nullptr,
                            (const uint64_t *)total_d, part_off);
-        pool.put(head); pool.put(E); pool.put(nl); pool.put(P);
-        pool.put(H); pool.put(GL); pool.put(GO); pool.put(first);
+        sc.put(head); sc.put(E); sc.put(nl); sc.put(P);
+        sc.put(H); sc.put(GL); sc.put(GO); sc.put(first);
     }
-    hipMemcpyAsync(part_off_host, part_off, sizeof(uint64_t) * (R + 1), hipMemcpyDeviceToHost, s);
-    hipStreamSynchronize(s);
-    pool.put(part_off);
-    pool.put(total_d);
-    pool.put(scantmp);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(part_off_host, part_off, sizeof(uint64_t) * (R + 1), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
     return total;
 }

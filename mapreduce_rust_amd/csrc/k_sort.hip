@@ -245,8 +245,8 @@ typename TR::R *radix_sort_t(typename TR::R *a, typename TR::R *b, uint64_t n, c
         if (want[q]) qmask |= 1u << q;
     hipLaunchKernelGGL(k_all_hist<TR>, dim3(g), dim3(BS), 0, s, a, n, hist, qmask);
     unsigned long long h[TR::NPASS * 256];
-    hipMemcpyAsync(h, hist, sizeof h, hipMemcpyDeviceToHost, s);
-    hipStreamSynchronize(s);
+    HIPCHK(hipMemcpyAsync(h, hist, sizeof h, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
     for (int q = 0; q < TR::NPASS; ++q) {
         if (!want[q]) continue;
         bool trivial = false;
@@ -497,7 +497,7 @@ void mrg_msd_sort_launch(SortRec *a, SortRec *b, uint64_t n, uint32_t pbits, voi
     hipLaunchKernelGGL(k_msd_leaf_small, dim3((unsigned)((nsmall + MSD_WG / 64 - 1) / (MSD_WG / 64))), dim3(MSD_WG), 0, s,
                        b, t.off, t.list);
     hipLaunchKernelGGL(k_msd_leaf, dim3(MSD_GRID), dim3(MSD_WG), 0, s, b, t.off, t.list2, lcap, t.big);
-    hipMemcpyAsync(h_nbig, t.big, sizeof(uint32_t), hipMemcpyDeviceToHost, s);  // pinned: no wait here
+    HIPCHK(hipMemcpyAsync(h_nbig, t.big, sizeof(uint32_t), hipMemcpyDeviceToHost, s));  // pinned: no wait here
 }
 
 SortRec *mrg_msd_sort_finish(SortRec *a, SortRec *b, uint64_t n, const SortPlan &plan, void *tmp, hipStream_t s,
@@ -507,9 +507,9 @@ SortRec *mrg_msd_sort_finish(SortRec *a, SortRec *b, uint64_t n, const SortPlan 
     const MsdTmp t = msd_tmp(tmp, n);
     if (nb > MSD_MAX_BIG) return mrg_radix_sort(b, a, n, plan, t.ltmp, s, nullptr);  // skewed: all of it
     std::vector<uint32_t> bl(nb), o(MSD_NB + 1);
-    hipMemcpyAsync(bl.data(), t.big + 1, sizeof(uint32_t) * nb, hipMemcpyDeviceToHost, s);
-    hipMemcpyAsync(o.data(), t.off, sizeof(uint32_t) * (MSD_NB + 1), hipMemcpyDeviceToHost, s);
-    hipStreamSynchronize(s);
+    HIPCHK(hipMemcpyAsync(bl.data(), t.big + 1, sizeof(uint32_t) * nb, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(o.data(), t.off, sizeof(uint32_t) * (MSD_NB + 1), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
     for (uint32_t bk : bl) {  // each oversized bucket by the LSD sort on its segment (a: scratch)
         const uint64_t lo = o[bk], m = o[bk + 1] - lo;
         SortRec *r = mrg_radix_sort(b + lo, a + lo, m, plan, t.ltmp, s, nullptr);
@@ -521,7 +521,7 @@ SortRec *mrg_msd_sort_finish(SortRec *a, SortRec *b, uint64_t n, const SortPlan 
 SortRec *mrg_msd_sort(SortRec *a, SortRec *b, uint64_t n, uint32_t pbits, const SortPlan &plan, void *tmp,
                       hipStream_t s, uint32_t *n_big, uint32_t *h_pinned) {
     mrg_msd_sort_launch(a, b, n, pbits, tmp, s, h_pinned);
-    hipStreamSynchronize(s);
+    HIPCHK(hipStreamSynchronize(s));
     const uint32_t nb = *h_pinned;
     if (n_big) *n_big = nb;
     return mrg_msd_sort_finish(a, b, n, plan, tmp, s, nb);

@@ -43,7 +43,6 @@ constexpr uint32_t W_L2DS = 2048;         // SEG L2: sampled records (the digit 
 constexpr uint32_t W_SCS = 6144;          // SEG L2: scatter chunk (above the stage: the leaf map, the leaves' ends)
 constexpr uint32_t W_L2D_CNT = 32768;     // SEG L2: byte offset of the digit counts in the sample LDS
 constexpr uint32_t W_L2D_MAP = 16u * W_SCS;   // SEG L2: byte offset of the digit -> leaf map
-constexpr uint32_t W_L2D_END = W_L2D_MAP + 2u * W_L2D;   // SEG L2: byte offset of the leaves' region ends (u32)
 constexpr uint32_t W_SC = 8192;       // L2 scatter chunk (staged in the samples' LDS)
 constexpr int W_LWG = 256;            // leaf workgroup (four per CU: while one waits on memory, others work)
 constexpr int W_LNW = W_LWG / 64;
@@ -481,7 +480,6 @@ struct L2Args {
     uint32_t *nleaf;         // [B1]
     uint64_t *leaf_lo;       // [B1 * MAXB2 + 1] first record of each leaf in `out` (absolute)
     uint64_t *leaf_hi;       // [B1 * MAXB2] one past its last record in `out`
-    uint64_t *leaf_dlo;      // [B1 * MAXB2] its first record in the dense order (bstart-based): output slots
     uint64_t *leaf_lb;       // [B1 * MAXB2][2] lower key bound of each leaf
     uint16_t *sub;           // [n] leaf (inside its L1 bucket) of each record: histogram pass -> scatter
     // segmented input (the wide map's regions): L1 bucket b's records are segments w <= grid at
@@ -492,13 +490,6 @@ struct L2Args {
     const uint32_t *soff;
     uint32_t grid, wcap, w12, wl16cap;
     const uint64_t *wl16;
-    // sparse leaves (SEG only, r06): bucket b's leaves live in out [9 bstart[b] / 4, 9 bstart[b + 1] / 4);
-    // the histogram counts a quarter of each segment, leaf j gets capmul * (its sampled records) +
-    // capadd slots, and a bucket whose leaf overflows is redone with the exact histogram
-    uint32_t sparse, capmul, capadd;
-    uint32_t sample_min;      // buckets of fewer records take the exact histogram at once
-    uint32_t redo;            // the redo launch: only buckets with redo_flags[b] set, exact histogram
-    uint32_t *redo_flags;     // [B1] buckets whose sampled leaves overflowed (zeroed by the host)
 };
 
 // record r of segment w of bucket b (segmented input), as (k0, k1)
@@ -554,7 +545,7 @@ __global__ __launch_bounds__(W_WG, 1) void k_wl2(L2Args L) {
     __shared__ uint32_t s_bst[MRG_WIDE_MAXB2];      // scatter: a chunk's leaf starts
     static_assert(W_SC * sizeof(uint64_t) * 2 <= sizeof(s_smp) && W_SC * sizeof(uint16_t) <= sizeof(s_spl),
                   "the scatter's stage fits the sample and splitter arrays");
-    static_assert(16 * W_L2DS <= W_L2D_CNT && W_L2D_CNT + 4 * W_L2D <= W_L2D_MAP && W_L2D_END + 4 * MRG_WIDE_MAXB2 <= sizeof(s_smp) &&
+    static_assert(16 * W_L2DS <= W_L2D_CNT && W_L2D_CNT + 4 * W_L2D <= W_L2D_MAP && W_L2D_MAP + 2 * W_L2D <= sizeof(s_smp) &&
                   W_SCS * sizeof(uint16_t) <= sizeof(s_spl) && W_L2D % W_WG == 0,
                   "SEG L2: samples, digit counts, leaf map and stage fit the sample LDS");
     __shared__ uint32_t s_ws[W_NW];
@@ -563,7 +554,6 @@ __global__ __launch_bounds__(W_WG, 1) void k_wl2(L2Args L) {
     __shared__ uint32_t s_dnv[SEG ? 4 : 1];                // SEG: values present at the three digit bytes
     __shared__ uint16_t s_dcode[SEG ? 3 * 256 : 1];        // SEG: the digit bytes' codes (live through the scatter)
     const uint32_t tid = threadIdx.x, b = blockIdx.x;
-    if (SEG && L.redo && L.redo_flags[b] == 0u) return;   // (uniform) only flagged buckets are redone
 #ifdef MRG_WIDE_PROF
     uint64_t l2acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, l2t = clock64();
 #endif
@@ -728,22 +718,10 @@ __global__ __launch_bounds__(W_WG, 1) void k_wl2(L2Args L) {
         return B2 > 1 ? si.upper(k0, k1) : 0u;
     };
     L2P(3);
-    // sparse leaves (SEG, large buckets): the histogram counts a quarter of every segment and each leaf
-    // gets a region of capmul x its sampled records + capadd; a bucket whose leaf overflows its region
-    // (or whose capacities pass the bucket's budget) is flagged and redone with the exact histogram by
-    // a second launch (L.redo: the other buckets' workgroups return at once)
-    uint32_t *s_end = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(s_smp) + W_L2D_END);
-    __shared__ uint32_t s_ovf;
-    const bool sparse = SEG && L.sparse != 0u;
-    const uint64_t obase = sparse ? 9u * base / 4u : base;
-    const uint64_t obud = sparse ? 9u * (base + nb) / 4u - obase : nb;   // slots of this bucket in `out`
-    const bool samp = sparse && !L.redo && B2 > 1 && nb >= L.sample_min;
-    const uint64_t dtg = samp ? max<uint64_t>(1u, dtgt / 4u) : dtgt;
     for (uint32_t j = tid; j < MRG_WIDE_MAXB2; j += W_WG) {
         s_cnt[j] = 0;
         s_cur[j] = 0;
     }
-    if (tid == 0) s_ovf = 0u;
     lds_barrier();
     // ---- histogram (U records per thread in flight)
     constexpr int U = MRG_WIDE_L2U;
@@ -753,8 +731,7 @@ __global__ __launch_bounds__(W_WG, 1) void k_wl2(L2Args L) {
         const uint32_t *so = s_cseg;
         const uint32_t lane = tid & 63u;
         for (uint32_t w = tid >> 6; w <= L.grid; w += W_NW) {
-            const uint32_t o = so[w], nwa = so[w + 1] - o;
-            const uint32_t nw = samp ? (nwa + 3u) / 4u : nwa;   // sampled: the segment's first quarter
+            const uint32_t o = so[w], nw = so[w + 1] - o;
             for (uint32_t j0 = lane; j0 < nw; j0 += (uint32_t)U * 64u) {
                 v2 x[U];
 #pragma unroll
@@ -799,7 +776,7 @@ __global__ __launch_bounds__(W_WG, 1) void k_wl2(L2Args L) {
         uint32_t run = block_scan_excl(sum, s_ws, &tot);
 #pragma unroll
         for (uint32_t x = 0; x < PT; ++x) {
-            const uint32_t leaf = min((uint32_t)(run / dtg), B2 - 1u);
+            const uint32_t leaf = min((uint32_t)(run / dtgt), B2 - 1u);
             lmap[tid * PT + x] = (uint16_t)leaf;
             if (v[x]) atomicAdd(&s_cnt[leaf], v[x]);
             run += v[x];
@@ -807,18 +784,14 @@ __global__ __launch_bounds__(W_WG, 1) void k_wl2(L2Args L) {
         lds_barrier();
     }
     L2P(4);
-    {  // exclusive scan of the B2 <= 1024 counts (sampled: region capacities), one per thread
-        const uint32_t v = tid < B2 ? (samp ? L.capmul * s_cnt[tid] + L.capadd : s_cnt[tid]) : 0u;
+    {  // exclusive scan of the B2 <= 1024 counts, one per thread
+        const uint32_t v = tid < B2 ? s_cnt[tid] : 0u;
         uint32_t tot;
         const uint32_t ex = block_scan_excl(v, s_ws, &tot);
-        if (tid < B2) {
-            s_cur[tid] = ex;
-            if (SEG) s_end[tid] = ex + v;
-        }
-        if (tid == 0) s_ovf = samp && (uint64_t)tot > obud ? 1u : 0u;   // capacities past the budget: exact
+        if (tid < B2) s_cur[tid] = ex;
         const uint64_t lid = (uint64_t)b * MRG_WIDE_MAXB2 + tid;
         if (tid < B2) {
-            L.leaf_lo[lid] = obase + ex;
+            L.leaf_lo[lid] = base + ex;
             uint64_t a, c;
             if (SEG) {   // digit leaves have no key bound (the wide map's job has no weighted keys)
                 a = 0;
@@ -850,11 +823,7 @@ __global__ __launch_bounds__(W_WG, 1) void k_wl2(L2Args L) {
     static_assert(WSC % W_WG == 0, "a chunk is whole records per thread");
     v2 *stg = reinterpret_cast<v2 *>(s_smp);              // the chunk in leaf order (the sample's LDS)
     uint16_t *stl = reinterpret_cast<uint16_t *>(s_spl);  // its leaves (the splitters' LDS)
-    GASW v2 *outv = reinterpret_cast<GASW v2 *>(gw(L.out) + 2 * obase);
-    if (samp && s_ovf) {   // (uniform: read after the barrier above) capacities past the budget
-        if (tid == 0) L.redo_flags[b] = 1u;
-        return;
-    }
+    GASW v2 *outv = reinterpret_cast<GASW v2 *>(gw(L.out) + 2 * base);
     for (uint64_t c0 = 0; c0 < nb; c0 += WSC) {
         const uint32_t nc = (uint32_t)min<uint64_t>(WSC, nb - c0);
         v2 x[SU];
@@ -915,28 +884,14 @@ __global__ __launch_bounds__(W_WG, 1) void k_wl2(L2Args L) {
             if (p < nc) {
                 const uint32_t q = stl[p];
                 const uint32_t d = s_cur[q] + (p - s_bst[q]);
-                if (!SEG || d < s_end[q]) outv[d] = stg[p];
-                else s_ovf = 1u;   // a sampled leaf past its region: the bucket is redone exactly
+                outv[d] = stg[p];   // (exact counts: a record lands inside its leaf)
             }
         }
         lds_barrier();
         if (tid < B2) s_cur[tid] += s_cnt[tid];   // the thread that zeroes s_cnt[tid] next chunk
     }
     lds_barrier();
-    if (samp && s_ovf) {   // a leaf overflowed its region: the bucket is redone exactly
-        if (tid == 0) L.redo_flags[b] = 1u;
-        return;
-    }
-    {   // where each leaf ends in `out`, and its first slot in the dense order (exact counts, scanned)
-        const uint64_t lid = (uint64_t)b * MRG_WIDE_MAXB2 + tid;
-        const uint32_t cnt = tid < B2 ? s_cur[tid] - (uint32_t)(L.leaf_lo[lid] - obase) : 0u;
-        uint32_t tot;
-        const uint32_t ex = block_scan_excl(cnt, s_ws, &tot);
-        if (tid < B2) {
-            L.leaf_hi[lid] = obase + s_cur[tid];
-            L.leaf_dlo[lid] = base + ex;
-        }
-    }
+    if (tid < B2) L.leaf_hi[(uint64_t)b * MRG_WIDE_MAXB2 + tid] = base + s_cur[tid];   // where each leaf ends in `out`
     L2P(6);
 #ifdef MRG_WIDE_PROF
     if (tid == 0)
@@ -973,8 +928,7 @@ struct LeafArgs {
     unsigned long long *big_n;
     uint32_t *leaf_pk;       // 1: the leaf's counts sit in the low word of its key slots (no ocnt entry)
     uint32_t pack;           // packing allowed (every count fits 32 bits)
-    const uint64_t *leaf_hi;   // one past each leaf's last record in kin (L2 may leave gaps between leaves)
-    const uint64_t *leaf_dlo;  // each leaf's first record in the dense order: its output slots start there
+    const uint64_t *leaf_hi;   // one past each leaf's last record in kin
 };
 
 // first weighted key >= (p, a, b)
@@ -1099,7 +1053,7 @@ __global__ __launch_bounds__(W_LWG, 3) void k_wleaf(LeafArgs L) {
         leaf_at(i, lid, mlo, mhi);
         const uint64_t wlo = L.wr[2 * lid], whi = L.wr[2 * lid + 1];
         const uint64_t nm = mhi - mlo, nwk = whi - wlo;
-        const uint64_t out0 = L.leaf_dlo[lid] + wlo;
+        const uint64_t out0 = mlo + wlo;
         v2 cur[W_PF];
 #pragma unroll
         for (int u = 0; u < W_PF; ++u) cur[u] = pf[u];
@@ -1656,7 +1610,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MRG_WIDE_VWP
 #endif
             continue;
         }
-        const uint64_t out0 = L.leaf_dlo[lid] + wlo;
+        const uint64_t out0 = mlo + wlo;
         GASW v2 *ko = kout + out0;
         GASW uint64_t *co = cout + out0;
         v2 key[W_VIPL];
@@ -2426,20 +2380,11 @@ void mrg_wide_launch_bstart(const uint32_t *cnt, uint32_t B1, uint32_t ntiles, u
 }
 void mrg_wide_launch_l2(const uint64_t *in, uint64_t *out, const uint64_t *bstart, const uint64_t *spl1, uint32_t B1,
                         uint32_t B1r, uint32_t target, uint32_t *nleaf, uint64_t *leaf_lo, uint64_t *leaf_hi,
-                        uint64_t *leaf_dlo, uint64_t *leaf_lb, uint16_t *sub, hipStream_t s, const WmapIn &wm,
-                        const L2Sparse &sp) {
-    L2Args L{in, out, bstart, spl1, B1r, target, nleaf, leaf_lo, leaf_hi, leaf_dlo, leaf_lb, sub,
-             wm.rin, wm.soff, wm.grid, wm.wcap, wm.w12, wm.wl16cap, wm.wl16,
-             wm.rin && sp.on ? 1u : 0u, sp.capmul, sp.capadd, sp.sample_min, 0u, sp.redo_flags};
-    if (wm.rin) {
-        hipLaunchKernelGGL(k_wl2<true>, dim3(B1), dim3(W_WG), 0, s, L);
-        if (L.sparse) {  // the buckets whose sampled leaves overflowed, with the exact histogram
-            L.redo = 1u;
-            hipLaunchKernelGGL(k_wl2<true>, dim3(B1), dim3(W_WG), 0, s, L);
-        }
-    } else {
-        hipLaunchKernelGGL(k_wl2<false>, dim3(B1), dim3(W_WG), 0, s, L);
-    }
+                        uint64_t *leaf_lb, uint16_t *sub, hipStream_t s, const WmapIn &wm) {
+    L2Args L{in, out, bstart, spl1, B1r, target, nleaf, leaf_lo, leaf_hi, leaf_lb, sub,
+             wm.rin, wm.soff, wm.grid, wm.wcap, wm.w12, wm.wl16cap, wm.wl16};
+    if (wm.rin) hipLaunchKernelGGL(k_wl2<true>, dim3(B1), dim3(W_WG), 0, s, L);
+    else hipLaunchKernelGGL(k_wl2<false>, dim3(B1), dim3(W_WG), 0, s, L);
 }
 // diagnostic builds (-DMRG_WIDE_PROF): the L2 phase clocks summed so far (else zeros)
 void mrg_wide_l2_prof(unsigned long long out[8]) {
@@ -2456,7 +2401,7 @@ void mrg_wide_launch_weights(const SortRec *r, uint64_t n, KeySet ks, uint64_t *
 void mrg_wide_launch_leaf(const WideLeafArgs &w, uint32_t B1, hipStream_t s) {
     LeafArgs L{w.kin, w.kout, w.bstart, w.nleaf, w.leaf_lo, w.leaf_lb, w.B1r, w.R, w.wk0, w.wk1, w.wcnt, w.wpart, w.nw,
                w.maxd ? min(w.maxd, W_MAXD) : W_MAXD, w.ocnt, w.leaf_out, w.leaf_nd, w.leaf_bytes, w.leaf_last, w.ovf_list,
-               w.ovf_n, w.nkeys, w.wr, w.prof, w.big_list, w.big_n, w.leaf_pk, w.pack, w.leaf_hi, w.leaf_dlo};
+               w.ovf_n, w.nkeys, w.wr, w.prof, w.big_list, w.big_n, w.leaf_pk, w.pack, w.leaf_hi};
     hipLaunchKernelGGL(k_wranges, gridw((uint64_t)B1 * MRG_WIDE_MAXB2), dim3(256), 0, s, L, B1);
     hipLaunchKernelGGL(k_wleafw, dim3(B1 * W_VQ), dim3(64), 0, s, L);
     // the passed-on leaves: a fixed grid loops over the list (its length is read on the device)
@@ -2466,19 +2411,21 @@ void mrg_wide_launch_fallback(const WideLeafArgs &w, const uint32_t *list, uint3
                               hipStream_t s) {
     LeafArgs L{w.kin, w.kout, w.bstart, w.nleaf, w.leaf_lo, w.leaf_lb, w.B1r, w.R, w.wk0, w.wk1, w.wcnt, w.wpart, w.nw,
                w.maxd ? min(w.maxd, W_MAXD) : W_MAXD, w.ocnt, w.leaf_out, w.leaf_nd, w.leaf_bytes, w.leaf_last, w.ovf_list,
-               w.ovf_n, w.nkeys, w.wr, w.prof, w.big_list, w.big_n, w.leaf_pk, w.pack, w.leaf_hi, w.leaf_dlo};
-    uint64_t *wrange = (uint64_t *)pool.get(16ull * nlist);
-    uint64_t *cnt = (uint64_t *)pool.get(8ull * (nlist + 1)), *off = (uint64_t *)pool.get(8ull * (nlist + 1));
-    uint64_t *scantmp = (uint64_t *)pool.get(8ull * mrg_scan_tmp_elems(nlist + 1));
+               w.ovf_n, w.nkeys, w.wr, w.prof, w.big_list, w.big_n, w.leaf_pk, w.pack, w.leaf_hi};
+    mrg_host::Scratch sc(pool);  // every temporary of the call
+    uint64_t *wrange = sc.get<uint64_t>(2ull * nlist);
+    uint64_t *cnt = sc.get<uint64_t>(nlist + 1), *off = sc.get<uint64_t>(nlist + 1);
+    uint64_t *scantmp = sc.get<uint64_t>(mrg_scan_tmp_elems(nlist + 1));
     hipLaunchKernelGGL(k_wfb_wrange, gridw(nlist), dim3(256), 0, s, L, list, nlist, wrange);
-    hipMemsetAsync(cnt + nlist, 0, 8, s);
+    HIPCHK(hipMemsetAsync(cnt + nlist, 0, 8, s));
     hipLaunchKernelGGL(k_wfb_count, gridw(nlist), dim3(256), 0, s, list, nlist, w.leaf_lo, w.leaf_hi, wrange, cnt);
     mrg_scan_u64(cnt, off, nlist + 1, scantmp, s);
+    HIPCHK(hipGetLastError());
     uint64_t n = 0;
-    hipMemcpyAsync(&n, off + nlist, 8, hipMemcpyDeviceToHost, s);
-    hipStreamSynchronize(s);
-    SortRec *a = (SortRec *)pool.get(sizeof(SortRec) * (n + 1)), *b = (SortRec *)pool.get(sizeof(SortRec) * (n + 1));
-    uint64_t *rcnt = (uint64_t *)pool.get(8ull * (n + 1));
+    HIPCHK(hipMemcpyAsync(&n, off + nlist, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    SortRec *a = sc.get<SortRec>(n + 1), *b = sc.get<SortRec>(n + 1);
+    uint64_t *rcnt = sc.get<uint64_t>(n + 1);
     hipLaunchKernelGGL(k_wfb_gather, dim3(nlist), dim3(256), 0, s, list, off, w.leaf_lo, w.leaf_hi, wrange,
                        w.kin, w.wk0, w.wk1, w.wcnt, a, rcnt);
     SortPlan plan{};
@@ -2487,27 +2434,27 @@ void mrg_wide_launch_fallback(const WideLeafArgs &w, const uint32_t *list, uint3
     for (uint32_t v = nlist - 1; v; v >>= 8) ++pb;
     plan.part_bytes = pb;
     plan.use_k0 = plan.use_k1 = true;
-    void *stmp = pool.get(mrg_sort_tmp_bytes(n));
+    void *stmp = sc.get<uint8_t>(mrg_sort_tmp_bytes(n));
     int passes = 0;
     SortRec *srt = mrg_radix_sort(a, b, n, plan, stmp, s, &passes);
-    uint64_t *head = (uint64_t *)pool.get(8ull * (n + 1)), *E = (uint64_t *)pool.get(8ull * (n + 1));
-    uint64_t *lfirst = (uint64_t *)pool.get(8ull * (nlist + 1));
-    uint64_t *scantmp2 = (uint64_t *)pool.get(8ull * mrg_scan_tmp_elems(n + 1));
+    uint64_t *head = sc.get<uint64_t>(n + 1), *E = sc.get<uint64_t>(n + 1);
+    uint64_t *lfirst = sc.get<uint64_t>(nlist + 1);
+    uint64_t *scantmp2 = sc.get<uint64_t>(mrg_scan_tmp_elems(n + 1));
     hipLaunchKernelGGL(k_wfb_heads, gridw(n), dim3(256), 0, s, srt, n, head);
     mrg_scan_u64(head, E, n, scantmp2, s);
     hipLaunchKernelGGL(k_wfb_lfirst, gridw(n), dim3(256), 0, s, srt, n, head, E, lfirst);
+    HIPCHK(hipGetLastError());
     uint64_t tail[2] = {0, 0};
-    hipMemcpyAsync(&tail[0], E + (n - 1), 8, hipMemcpyDeviceToHost, s);
-    hipMemcpyAsync(&tail[1], head + (n - 1), 8, hipMemcpyDeviceToHost, s);
-    hipStreamSynchronize(s);
+    HIPCHK(hipMemcpyAsync(&tail[0], E + (n - 1), 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&tail[1], head + (n - 1), 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
     const uint64_t runs = tail[0] + tail[1];
     hipLaunchKernelGGL(k_wfb_emit, gridw(n), dim3(256), 0, s, srt, n, head, E, rcnt, list, lfirst, w.leaf_out, w.kout,
                        w.ocnt);
     hipLaunchKernelGGL(k_wfb_stats, dim3(nlist), dim3(256), 0, s, list, nlist, lfirst, runs, w.kout, w.ocnt, w.leaf_out,
                        w.leaf_nd, w.leaf_bytes, w.leaf_last, w.nkeys);
-    hipStreamSynchronize(s);
-    pool.put(wrange); pool.put(cnt); pool.put(off); pool.put(scantmp); pool.put(a); pool.put(b); pool.put(rcnt);
-    pool.put(stmp); pool.put(head); pool.put(E); pool.put(lfirst); pool.put(scantmp2);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s));
 }
 void mrg_wide_launch_drop(const uint32_t *nleaf, uint32_t B1r, uint32_t R, const uint32_t *leaf_nd, uint64_t *leaf_bytes,
                           const uint32_t *leaf_last, uint32_t *leaf_drop, hipStream_t s) {

@@ -1,5 +1,7 @@
-// mrg_host.h -- what the host units of libmrgpu.so share (mrgpu.cpp, mrg_vocab.cpp): the error path of the
-// C ABI, the device-block pool with its scope guard, the context and the vocabulary, and a few helpers.
+// mrg_host.h -- what the host units of libmrgpu.so share (mrgpu.cpp, mrg_vocab.cpp): the guard that ends the
+// error path at the C ABI, the device-block pool, the context and the vocabulary, and a few helpers.  The
+// error path itself (MrgError, raise, HIPCHK) and the pool's scope guard (Scratch) live in mrg_internal.h,
+// because the .hip files' host functions use them too.
 // Host only: no .hip file includes it.  Nothing here joins the library's exported symbols.
 #pragma once
 #include <stdarg.h>
@@ -22,26 +24,6 @@
 namespace mrg_host __attribute__((visibility("hidden"))) {
 
 extern thread_local std::string g_err;  // mrg_last_error() of this thread (defined in mrgpu.cpp)
-
-struct MrgError {
-    int code;
-    std::string msg;
-};
-
-[[noreturn]] inline void raise(int code, const char *fmt, ...) {
-    char buf[1024];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    throw MrgError{code, buf};
-}
-
-#define HIPCHK(x)                                                                      \
-    do {                                                                               \
-        hipError_t e_ = (x);                                                           \
-        if (e_ != hipSuccess) raise(MRG_EHIP, "%s: %s", #x, hipGetErrorString(e_));    \
-    } while (0)
 
 template <class F>
 int guard(F &&f) {
@@ -135,6 +117,7 @@ class Pool : public DevPool {
    public:
     void set_device(int dev) { dev_ = dev; }
     void *get(size_t bytes) override {
+        if (fail_in_ && --fail_in_ == 0) raise(MRG_ENOMEM, "injected allocation failure");
         const size_t c = cls(bytes ? bytes : 1);
         // smallest free block of this class or up to two classes above (record counts drift by a few
         // between jobs over the same input: an exact-class pool would then miss, run out of device
@@ -211,6 +194,7 @@ class Pool : public DevPool {
         if (ms) *ms = alloc_ms_;
     }
     uint64_t reused() const { return reused_; }  // blocks taken from the process-wide device cache
+    void fail_in(uint64_t k) { fail_in_ = k; }   // mrg_test_pool_fail: the k-th get from now throws, once (0: none)
     ~Pool() override {  // (the caller has made dev_ current)
         (void)hipDeviceSynchronize();
         for (auto &kv : size_) {
@@ -230,60 +214,9 @@ class Pool : public DevPool {
     std::multimap<size_t, void *> free_;
     std::unordered_map<void *, size_t> size_;
     bool debug_ = getenv("MRG_DEBUG") != nullptr;
-    uint64_t allocs_ = 0, alloc_bytes_ = 0, reused_ = 0;
+    uint64_t allocs_ = 0, alloc_bytes_ = 0, reused_ = 0, fail_in_ = 0;
     int dev_ = -1;
     double alloc_ms_ = 0.0;
-};
-
-template <class T>
-T *pget(Pool &p, uint64_t n) {
-    return (T *)p.get(sizeof(T) * (n ? n : 1));
-}
-
-// The pool blocks of one scope, returned on every exit from it, an exception included.  A block goes
-// back at the point the host reaches, while kernels that use it may still be queued on the context's
-// stream: every later user of the block runs on that same stream, behind them.  put() returns one block
-// early, so the allocations that follow can reuse it; release() hands one to an owner that outlives
-// the scope (c->keys, c->wide, c->d_out, another Scratch).
-struct Scratch {
-    Pool &p;
-    std::vector<void *> b;
-    explicit Scratch(Pool &pool) : p(pool) {}
-    Scratch(const Scratch &) = delete;
-    Scratch &operator=(const Scratch &) = delete;
-    Scratch(Scratch &&o) : p(o.p), b(std::move(o.b)) { o.b.clear(); }
-    Scratch &operator=(Scratch &&o) {  // (of the same pool)
-        put_all();
-        b = std::move(o.b);
-        o.b.clear();
-        return *this;
-    }
-    template <class T>
-    T *get(uint64_t n) {
-        b.push_back(nullptr);
-        return (T *)(b.back() = pget<T>(p, n));
-    }
-    template <class T>
-    T *adopt(T *q) {
-        if (q) b.push_back((void *)q);
-        return q;
-    }
-    template <class T>
-    T *release(T *q) {
-        auto it = std::find(b.begin(), b.end(), (void *)q);
-        if (it != b.end()) b.erase(it);
-        return q;
-    }
-    template <class T>
-    void put(T *q) {
-        if (q) p.put((void *)release(q));
-    }
-    void put_all() {
-        for (void *q : b) p.put(q);
-        b.clear();
-    }
-    void keep() { b.clear(); }  // every block has found its longer-lived owner
-    ~Scratch() { put_all(); }
 };
 
 struct KeysBuf {

@@ -1,8 +1,18 @@
-// mrg_internal.h -- host-side declarations shared by the kernel files and the C-ABI layer.
+// mrg_internal.h -- host-side declarations shared by the kernel files and the C-ABI layer: the kernels'
+// argument records and launchers, and what every host function that takes pool blocks or waits for the
+// device needs -- the error path (MrgError, raise, HIPCHK), the pool interface and its scope guard (Scratch).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stdarg.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <stdio.h>
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "mrgpu.h"
 
 #ifndef MRG_MAP_WAVES  // (timing variants override it: the r06 occupancy sweep)
 #define MRG_MAP_WAVES 16        // waves per map workgroup (one workgroup per CU, one shared LDS table)
@@ -50,6 +60,83 @@ struct DevPool {
     virtual void put(void *p) = 0;
     virtual ~DevPool() {}
 };
+
+namespace mrg_host __attribute__((visibility("hidden"))) {
+
+// The error path of the C ABI: host code throws, the entry points turn it into a code (guard, mrg_host.h).
+struct MrgError {
+    int code;
+    std::string msg;
+};
+
+[[noreturn]] inline void raise(int code, const char *fmt, ...) {
+    char buf[1024];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    throw MrgError{code, buf};
+}
+
+#define HIPCHK(x)                                                                                \
+    do {                                                                                         \
+        hipError_t e_ = (x);                                                                     \
+        if (e_ != hipSuccess) ::mrg_host::raise(MRG_EHIP, "%s: %s", #x, hipGetErrorString(e_));  \
+    } while (0)
+
+// a block the caller owns from here on: only the context's long-lived members take blocks this way
+template <class T>
+T *pget(DevPool &p, uint64_t n) {
+    return (T *)p.get(sizeof(T) * (n ? n : 1));
+}
+
+// The pool blocks of one scope, returned on every exit from it, an exception included.  A block goes
+// back at the point the host reaches, while kernels that use it may still be queued on the context's
+// stream: every later user of the block runs on that same stream, behind them.  put() returns one block
+// early, so the allocations that follow can reuse it; release() hands one to an owner that outlives
+// the scope (c->keys, c->wide, c->d_out, another Scratch).
+struct Scratch {
+    DevPool &p;
+    std::vector<void *> b;
+    explicit Scratch(DevPool &pool) : p(pool) {}
+    Scratch(const Scratch &) = delete;
+    Scratch &operator=(const Scratch &) = delete;
+    Scratch(Scratch &&o) : p(o.p), b(std::move(o.b)) { o.b.clear(); }
+    Scratch &operator=(Scratch &&o) {  // (of the same pool)
+        put_all();
+        b = std::move(o.b);
+        o.b.clear();
+        return *this;
+    }
+    template <class T>
+    T *get(uint64_t n) {
+        b.push_back(nullptr);
+        return (T *)(b.back() = pget<T>(p, n));
+    }
+    template <class T>
+    T *adopt(T *q) {
+        if (q) b.push_back((void *)q);
+        return q;
+    }
+    template <class T>
+    T *release(T *q) {
+        auto it = std::find(b.begin(), b.end(), (void *)q);
+        if (it != b.end()) b.erase(it);
+        return q;
+    }
+    template <class T>
+    void put(T *q) {
+        if (q) p.put((void *)release(q));
+    }
+    void put_all() {
+        for (void *q : b) p.put(q);
+        b.clear();
+    }
+    void keep() { b.clear(); }  // every block has found its longer-lived owner
+    ~Scratch() { put_all(); }
+};
+
+}  // namespace mrg_host
 
 struct MapArgs {
     const uint8_t *in;
@@ -421,8 +508,7 @@ struct WideLeafArgs {
     unsigned long long *big_n;   // their count (zeroed by the caller)
     uint32_t *leaf_pk;           // [B1 * MRG_WIDE_MAXB2] 1: the leaf's counts are packed into its key slots (zeroed by the caller)
     uint32_t pack;               // packing allowed: every count fits 32 bits (fewer than 2^32 tokens)
-    const uint64_t *leaf_hi;     // [B1 * MAXB2] one past each leaf's last record in kin (L2 may leave gaps)
-    const uint64_t *leaf_dlo;    // [B1 * MAXB2] each leaf's first record in the dense order (its output slots)
+    const uint64_t *leaf_hi;     // [B1 * MAXB2] one past each leaf's last record in kin
 };
 void mrg_wide_launch_counts(const BucketArgs &a, uint64_t *cnt_main, uint64_t *segptr, uint64_t *cnt_flush,
                             hipStream_t s);
@@ -445,18 +531,9 @@ struct WmapIn {
     const uint64_t *wl16 = nullptr;
 };
 void mrg_wide_l2_prof(unsigned long long out[8]);
-// sparse L2 leaves (the wide map's buckets only): out must hold 9 n / 4 + 16 records (bucket b's leaves in
-// [9 bstart[b] / 4, 9 bstart[b + 1] / 4)); capacities capmul x sampled records + capadd (test knobs)
-struct L2Sparse {
-    bool on = false;
-    uint32_t capmul = 6, capadd = 64;   // (r06 v11: 6 x the sampled records + 64, leaf target 256)
-    uint32_t sample_min = 65536;      // records: smaller buckets histogram exactly
-    uint32_t *redo_flags = nullptr;   // [B1], zeroed: buckets the exact second launch redoes
-};
 void mrg_wide_launch_l2(const uint64_t *in, uint64_t *out, const uint64_t *bstart, const uint64_t *spl1, uint32_t B1,
                         uint32_t B1r, uint32_t target, uint32_t *nleaf, uint64_t *leaf_lo, uint64_t *leaf_hi,
-                        uint64_t *leaf_dlo, uint64_t *leaf_lb, uint16_t *sub, hipStream_t s,
-                        const WmapIn &wm = WmapIn{}, const L2Sparse &sp = L2Sparse{});
+                        uint64_t *leaf_lb, uint16_t *sub, hipStream_t s, const WmapIn &wm = WmapIn{});
 // wide map (near-unique input): a sample of the input text's tokens (k_wsample_text), adjacent
 // duplicates of the sorted sample, the L1 splitter index, the regions' per-bucket segment starts
 void mrg_wide_launch_sample_text(const uint8_t *in, const uint64_t *doc_off, uint32_t n_docs, uint64_t total,

@@ -541,6 +541,51 @@ void wide_densify(mrg_ctx *c, uint64_t extra) {
     w.release(c->pool);
 }
 
+// MRG_DEBUG: the HIP-event time of the phases of one wide aggregation.  The first mark starts the clock; every
+// later one ends a phase and names it.  The events are the clock's own and go with it on every exit.
+struct PhaseClock {
+    const bool on = getenv("MRG_DEBUG") != nullptr;
+    hipStream_t s;
+    std::vector<std::pair<hipEvent_t, const char *>> ev;
+    explicit PhaseClock(hipStream_t st) : s(st) {}
+    PhaseClock(const PhaseClock &) = delete;
+    PhaseClock &operator=(const PhaseClock &) = delete;
+    ~PhaseClock() {
+        for (auto &m : ev) (void)hipEventDestroy(m.first);
+    }
+    void mark(const char *name) {
+        if (!on) return;
+        hipEvent_t e = nullptr;
+        HIPCHK(hipEventCreate(&e));
+        ev.push_back({e, name});
+        HIPCHK(hipEventRecord(e, s));
+    }
+    void report() {  // (the stream has reached the last mark)
+        fprintf(stderr, "[mrgpu] wide phases (ms):");
+        for (size_t i = 1; i < ev.size(); ++i) {
+            float ms = 0;
+            HIPCHK(hipEventElapsedTime(&ms, ev[i - 1].first, ev[i].first));
+            fprintf(stderr, " %s %.2f", ev[i].second, ms);
+        }
+        fprintf(stderr, "\n");
+    }
+};
+
+// What the first level hands to wide_finish: n records in L1 buckets, bucket b = partition * B1r + key
+// range (bstart[b] .. bstart[b + 1]) -- L1's output K1, or (wm.rin) the wide map's regions -- the
+// splitters that cut them, and the nw weighted keys (the flushed map tables, aggregated and sorted).
+struct WideL1 {
+    uint64_t n = 0, nw = 0;
+    uint32_t B1 = 0, B1r = 0;
+    uint64_t *K1 = nullptr;      // [2 (n + nw) + 2] L1's output, then the leaves' output keys
+    uint64_t *bstart = nullptr;  // [B1 + 1]
+    uint64_t *spl1 = nullptr;
+    uint16_t *bid = nullptr;     // [n] L1 bucket, then L2 leaf, of each record
+    uint64_t *wk0 = nullptr, *wk1 = nullptr, *wcnt = nullptr;
+    uint32_t *wpart = nullptr;
+    WmapIn wm;
+};
+
 // Wide aggregation by the two-level sample sort (k_wide.hip): the map's count-1 records go through
 // L1 (partition + global quantile splitters) and L2 (per-bucket splitters) into leaves; the flushed
 // map-table entries (weighted) are aggregated apart, sorted, and merged into their leaves.
@@ -549,47 +594,25 @@ void wide_densify(mrg_ctx *c, uint64_t extra) {
 // overflowing leaves' fallback, then the long keys.  K1 becomes the output key array; bid holds the
 // L2 leaf id of every record.  `own` holds K1 (kept in c->wide), bstart, spl1, bid and wk*; the blocks
 // taken here join them, and all go back before the long keys' blocks are taken.
-void wide_finish(mrg_ctx *c, Scratch &own, LongItems li, uint64_t n, uint64_t nw, uint32_t B1, uint32_t B1r,
-                 uint64_t *K1, uint64_t *bstart, uint64_t *spl1, uint16_t *bid, uint64_t *wk0, uint64_t *wk1,
-                 uint64_t *wcnt, uint32_t *wpart, bool dbg, hipEvent_t *pe, int &npe, const WmapIn &wm) {
+void wide_finish(mrg_ctx *c, Scratch &own, const WideL1 &l1, LongItems li, PhaseClock &clock) {
     hipStream_t s = c->stream;
-    const uint32_t R = c->R;
-    auto mark = [&]() {
-        if (!dbg || npe >= 8) return;
-        HIPCHK(hipEventCreate(&pe[npe]));
-        HIPCHK(hipEventRecord(pe[npe++], s));
-    };
+    const uint32_t R = c->R, B1 = l1.B1, B1r = l1.B1r;
+    const uint64_t n = l1.n, nw = l1.nw;
+    uint64_t *K1 = l1.K1;
+    const WmapIn &wm = l1.wm;
     // ---- L2: leaves inside every L1 bucket
     const uint64_t NL = (uint64_t)B1 * MRG_WIDE_MAXB2;
-    // the wide map's buckets: with MRG_WIDE_L2_SAMPLED=1, sparse leaves in K2 from a sampled histogram
-    // (-1 % of C5's step for 1.6x its device memory, so not the default);
-    // MRG_TEST_L2_CAP=<mul>,<add> sets the leaf capacities (small ones force the exact redo),
-    // MRG_TEST_L2_MIN the smallest bucket that samples
-    L2Sparse sp;
-    sp.on = wm.rin != nullptr && env_u64("MRG_WIDE_L2_SAMPLED", 0) != 0;
-    if (const char *e = getenv("MRG_TEST_L2_CAP")) {
-        unsigned a = 8, d = 64;
-        if (sscanf(e, "%u,%u", &a, &d) >= 1) { sp.capmul = a; sp.capadd = d; }
-    }
-    sp.sample_min = (uint32_t)env_u64("MRG_TEST_L2_MIN", sp.sample_min);  // (tests: sample small buckets)
-    if (sp.on) {
-        sp.redo_flags = own.get<uint32_t>(B1);
-        HIPCHK(hipMemsetAsync(sp.redo_flags, 0, 4ull * B1, s));
-    }
-    const uint64_t nrec2 = sp.on ? 9 * n / 4 + 16 : n + 1;  // K2 records
-    uint64_t *K2 = own.get<uint64_t>(2 * nrec2 + 2);
+    uint64_t *K2 = own.get<uint64_t>(2 * (n + 1) + 2);
     uint32_t *nleaf = own.get<uint32_t>(B1);
     uint64_t *leaf_lo = own.get<uint64_t>(NL + 1), *leaf_lb = own.get<uint64_t>(2 * NL + 2);
-    uint64_t *leaf_hi = own.get<uint64_t>(NL + 1), *leaf_dlo = own.get<uint64_t>(NL + 1);
-    // records per leaf: the wide map's digit leaves come out near the target (320: r05 v61; 256 when cut
-    // from the sampled histogram, whose leaves vary more: r06 v09, v11), the sampled splitters' leaves
-    // vary like 8-sample gaps (256 keeps most under the one-wave capacity)
-    const uint32_t target = (uint32_t)env_u64("MRG_TEST_LEAF_TARGET", wm.rin ? (sp.on ? 256 : 320) : 256);
-    mrg_wide_launch_l2(wm.rin ? nullptr : K1, K2, bstart, spl1, B1, B1r, target, nleaf, leaf_lo, leaf_hi, leaf_dlo, leaf_lb,
-                       bid, s, wm, sp);
-    own.put(sp.redo_flags);
-    own.put(bid);
-    mark();  // 4: L2
+    uint64_t *leaf_hi = own.get<uint64_t>(NL + 1);
+    // records per leaf: the wide map's digit leaves come out near the target (320: r05 v61), the sampled
+    // splitters' leaves vary like 8-sample gaps (256 keeps most under the one-wave capacity)
+    const uint32_t target = (uint32_t)env_u64("MRG_TEST_LEAF_TARGET", wm.rin ? 320 : 256);
+    mrg_wide_launch_l2(wm.rin ? nullptr : K1, K2, l1.bstart, l1.spl1, B1, B1r, target, nleaf, leaf_lo, leaf_hi, leaf_lb,
+                       l1.bid, s, wm);
+    own.put(l1.bid);
+    clock.mark("L2");
     // ---- leaves: aggregate + sort + line bytes (K1 becomes the output key array)
     WideRes &w = c->wide;
     Pool &p = c->pool;
@@ -611,9 +634,9 @@ void wide_finish(mrg_ctx *c, Scratch &own, LongItems li, uint64_t n, uint64_t nw
     HIPCHK(hipMemsetAsync(&c->d_cnt[CNT_KEYS], 0, 8, s));
     HIPCHK(hipMemsetAsync(&c->d_cnt[CNT_OVF2], 0, 8, s));
     WideLeafArgs L{};
-    L.kin = K2; L.kout = K1; L.bstart = bstart; L.nleaf = nleaf; L.leaf_lo = leaf_lo; L.leaf_lb = leaf_lb;
-    L.leaf_hi = leaf_hi; L.leaf_dlo = leaf_dlo;
-    L.B1r = B1r; L.R = R; L.wk0 = wk0; L.wk1 = wk1; L.wcnt = wcnt; L.wpart = wpart; L.nw = nw;
+    L.kin = K2; L.kout = K1; L.bstart = l1.bstart; L.nleaf = nleaf; L.leaf_lo = leaf_lo; L.leaf_lb = leaf_lb;
+    L.leaf_hi = leaf_hi;
+    L.B1r = B1r; L.R = R; L.wk0 = l1.wk0; L.wk1 = l1.wk1; L.wcnt = l1.wcnt; L.wpart = l1.wpart; L.nw = nw;
     L.maxd = (uint32_t)env_u64("MRG_TEST_LEAF_CAP", 0);
     L.ocnt = w.ocnt; L.leaf_out = w.leaf_out; L.leaf_nd = w.leaf_nd; L.leaf_bytes = w.leaf_bytes;
     L.leaf_last = w.leaf_last; L.ovf_list = ovf_list; L.ovf_n = &c->d_cnt[CNT_OVF2]; L.nkeys = &c->d_cnt[CNT_KEYS];
@@ -628,24 +651,16 @@ void wide_finish(mrg_ctx *c, Scratch &own, LongItems li, uint64_t n, uint64_t nw
     L.pack = (c->h_cnt[CNT_TOKENS] < 0xFFFFFFFFull && !getenv("MRG_TEST_NO_PACK")) ? 1u : 0u;
     HIPCHK(hipMemsetAsync(L.big_n, 0, 8, s));
     mrg_wide_launch_leaf(L, B1, s);
-    mark();  // 5: leaves
+    clock.mark("leaves");
     read_counters(c);
     const uint64_t novf = c->h_cnt[CNT_OVF2];
     if (novf) mrg_wide_launch_fallback(L, ovf_list, (uint32_t)novf, p, s);
-    mark();  // 6: fallback
+    clock.mark("fallback");
     read_counters(c);
     w.distinct = c->h_cnt[CNT_KEYS];
     w.ready = true;
-    if (dbg) {
-        static const char *nm[] = {"weights", "splitters", "L1", "L2", "leaves", "fallback"};
-        fprintf(stderr, "[mrgpu] wide phases (ms):");
-        for (int i = 1; i < npe; ++i) {
-            float ms = 0;
-            HIPCHK(hipEventElapsedTime(&ms, pe[i - 1], pe[i]));
-            fprintf(stderr, " %s %.2f", nm[i - 1], ms);
-        }
-        fprintf(stderr, "\n");
-        for (int i = 0; i < npe; ++i) (void)hipEventDestroy(pe[i]);
+    if (clock.on) {
+        clock.report();
         unsigned long long pr[16], nbig = 0;
         HIPCHK(hipMemcpy(pr, L.prof, sizeof pr, hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(&nbig, L.big_n, 8, hipMemcpyDeviceToHost));
@@ -708,7 +723,7 @@ void wide_finish(mrg_ctx *c, Scratch &own, LongItems li, uint64_t n, uint64_t nw
 
 void wide_aggregate(mrg_ctx *c, const MapArgs &A, uint32_t nreg, uint32_t regcap, LongItems li) {
     const uint32_t R = c->R;
-    if (R > 4096 || getenv("MRG_WIDE_RADIX")) {  // the L1 histogram holds R x B1r buckets in LDS
+    if (R > 4096) {  // the L1 histogram holds R x B1r buckets in LDS
         wide_aggregate_radix(c, A, nreg, regcap, li);
         return;
     }
@@ -716,16 +731,8 @@ void wide_aggregate(mrg_ctx *c, const MapArgs &A, uint32_t nreg, uint32_t regcap
     Scratch fin(c->pool);  // what wide_finish takes over
     hipStream_t s = c->stream;
     const BucketArgs B = map_output(A, nreg, regcap);
-    // MRG_DEBUG: HIP-event time of each phase
-    const bool dbg = getenv("MRG_DEBUG") != nullptr;
-    hipEvent_t pe[8] = {};
-    int npe = 0;
-    auto mark = [&]() {
-        if (!dbg || npe >= 8) return;
-        HIPCHK(hipEventCreate(&pe[npe]));
-        HIPCHK(hipEventRecord(pe[npe++], s));
-    };
-    mark();
+    PhaseClock clock(s);
+    clock.mark("start");
     // ---- segment sizes: main (count 1) and flushed tables (weighted)
     const uint64_t nsm = 2ull * nreg * MRG_NBUCKET + MRG_NBUCKET;  // 12-byte regions, overflow lists, 16-byte regions
     uint64_t *cm = sc.get<uint64_t>(nsm + 1), *om = sc.get<uint64_t>(nsm + 1), *segptr = sc.get<uint64_t>(nsm);
@@ -775,7 +782,7 @@ void wide_aggregate(mrg_ctx *c, const MapArgs &A, uint32_t nreg, uint32_t regcap
         mrg_wide_launch_weights(srt, nw, ks, wk0, wk1, wcnt, wpart, s);
         sync(c);
     }
-    mark();  // 1: weighted keys done
+    clock.mark("weights");
     // ---- L1 buckets: R partitions x B1r quantile ranges of about 2^18 records
     uint32_t B1r = (uint32_t)std::min<uint64_t>((n + ((uint64_t)R << 18) - 1) / ((uint64_t)R << 18), 64);
     B1r = std::max<uint32_t>(1, std::min<uint32_t>(B1r, std::max<uint32_t>(1, 4096 / R)));
@@ -792,14 +799,14 @@ void wide_aggregate(mrg_ctx *c, const MapArgs &A, uint32_t nreg, uint32_t regcap
         mrg_wide_launch_split1(srt, S1, R, B1r, spl1, s);
         sync(c);
     }
-    mark();  // 2: splitters
+    clock.mark("splitters");
     const uint32_t ntiles = (uint32_t)std::max<uint64_t>(1, (n + MRG_WIDE_T1 - 1) / MRG_WIDE_T1);
     uint32_t *cnt1 = sc.get<uint32_t>((uint64_t)B1 * ntiles + 1);
     uint32_t *st2 = sc.get<uint32_t>(mrg_scan_tmp_elems((uint64_t)B1 * ntiles + 1));
     uint64_t *K1 = fin.get<uint64_t>(2 * (n + nw) + 2);
     uint64_t *bstart = fin.get<uint64_t>(B1 + 1);
     uint16_t *bid = fin.get<uint16_t>(std::max<uint64_t>(n, 1));   // L1 bucket, then L2 leaf, of each record
-    uint8_t *ix1 = getenv("MRG_TEST_NO_L1IX") ? nullptr : sc.get<uint8_t>(260ull * R);
+    uint8_t *ix1 = sc.get<uint8_t>(260ull * R);
     if (n) {
         mrg_wide_launch_l1(B, om, segptr, nsm, n, spl1, R, B1r, cnt1, ntiles, K1, bid, ix1, false, s);
         mrg_scan_u32(cnt1, cnt1, (uint64_t)B1 * ntiles, st2, s);
@@ -809,8 +816,12 @@ void wide_aggregate(mrg_ctx *c, const MapArgs &A, uint32_t nreg, uint32_t regcap
     }
     mrg_wide_launch_bstart(cnt1, B1, ntiles, n, bstart, s);
     sc.put_all();
-    mark();  // 3: L1
-    wide_finish(c, fin, li, n, nw, B1, B1r, K1, bstart, spl1, bid, wk0, wk1, wcnt, wpart, dbg, pe, npe, WmapIn{});
+    clock.mark("L1");
+    WideL1 l1;
+    l1.n = n; l1.nw = nw; l1.B1 = B1; l1.B1r = B1r;
+    l1.K1 = K1; l1.bstart = bstart; l1.spl1 = spl1; l1.bid = bid;
+    l1.wk0 = wk0; l1.wk1 = wk1; l1.wcnt = wcnt; l1.wpart = wpart;
+    wide_finish(c, fin, l1, li, clock);
 }
 
 void job_begin(mrg_ctx *c, int app, uint32_t R, uint32_t flags) {
@@ -1168,6 +1179,8 @@ void job_map_wide(mrg_ctx *c, Scratch &sc, const WideMapPlan &wp, const MapIn &i
     ev_rec(c, c->ev, 2);
     const LongItems li = long_items(c, att, A, grid);
     // ---- the regions as L1 buckets: per-bucket segment starts, bucket offsets, then L2 and the leaves
+    PhaseClock clock(s);
+    clock.mark("start");
     Scratch fin(c->pool);  // what wide_finish takes over
     uint32_t *soff = att.get<uint32_t>((uint64_t)B1 * (grid + 2));
     uint64_t *nbk = att.get<uint64_t>((uint64_t)B1 + 1);
@@ -1181,20 +1194,21 @@ void job_map_wide(mrg_ctx *c, Scratch &sc, const WideMapPlan &wp, const MapIn &i
     sync(c);
     if (n >= 0xFFFFFFF0ull) raise(MRG_ENOMEM, "wide aggregation: %llu records exceed one GPU's 32-bit record index",
                                   (unsigned long long)n);
-    uint64_t *K1 = fin.get<uint64_t>(2 * n + 2);  // the leaves' output keys
-    uint16_t *bid = fin.get<uint16_t>(std::max<uint64_t>(n, 1));
-    uint64_t *wk0 = fin.get<uint64_t>(1), *wk1 = fin.get<uint64_t>(1), *wk = fin.get<uint64_t>(1);
-    uint32_t *wpart = fin.get<uint32_t>(1);
-    fin.adopt(sc.release(wp.spl1));
-    const bool dbg = getenv("MRG_DEBUG") != nullptr;
-    hipEvent_t pe[8] = {};
-    int npe = 0;
+    WideL1 l1;
+    l1.n = n; l1.B1 = B1; l1.B1r = wp.B1r;
+    l1.bstart = bstart;
+    l1.K1 = fin.get<uint64_t>(2 * n + 2);  // the leaves' output keys
+    l1.bid = fin.get<uint16_t>(std::max<uint64_t>(n, 1));
+    l1.wk0 = fin.get<uint64_t>(1); l1.wk1 = fin.get<uint64_t>(1); l1.wcnt = fin.get<uint64_t>(1);  // (no weighted keys)
+    l1.wpart = fin.get<uint32_t>(1);
+    l1.spl1 = fin.adopt(sc.release(wp.spl1));
     c->st.agg_path = 2;
     c->spec_agg = false;
-    WmapIn wm;
+    WmapIn &wm = l1.wm;
     wm.rin = A.wrec; wm.soff = soff; wm.grid = (uint32_t)grid; wm.wcap = (uint32_t)wcap;
     wm.w12 = w12 ? 1u : 0u; wm.wl16cap = (uint32_t)wl16cap; wm.wl16 = A.wl16;
-    wide_finish(c, fin, li, n, 0, B1, wp.B1r, K1, bstart, wp.spl1, bid, wk0, wk1, wk, wpart, dbg, pe, npe, wm);
+    clock.mark("segments");
+    wide_finish(c, fin, l1, li, clock);
     c->st.map_kind = 1;
     ev_rec(c, c->ev, 3);
     c->st.ms_aggregate = ev_ms(c, c->ev, 2, 3);
@@ -3486,6 +3500,16 @@ int mrg_run_get_stream_stats(uint32_t *batches, uint64_t *peak_input_bytes) {
     if (batches) *batches = g_stream_batches;
     if (peak_input_bytes) *peak_input_bytes = g_stream_peak;
     return MRG_OK;
+}
+
+// Fault injection for the tests of the error exits (not in include/mrgpu.h; tests/test_gpu_pool_errors.py):
+// the k-th block this context's pool is asked for from now on fails with MRG_ENOMEM ("injected allocation
+// failure") before anything is taken, once; k = 0 disarms.
+int mrg_test_pool_fail(mrg_ctx *c, uint64_t k) {
+    return guard([&] {
+        if (!c) raise(MRG_EINVAL, "null context");
+        c->pool.fail_in(k);
+    });
 }
 
 // Diagnostics of the accumulator (not in include/mrgpu.h; tools/time_stream.py): h_info[0..6) = table

@@ -330,6 +330,14 @@ class Context:
     def set_timing(self, on=True):
         _check(load().mrg_set_timing(self.h, 1 if on else 0))
 
+    def pool_fail(self, k):
+        """mrg_test_pool_fail (tests of the error exits): the k-th device block this context asks its pool
+        for from now on fails with ENOMEM, once; 0 disarms."""
+        f = load().mrg_test_pool_fail
+        f.restype = C.c_int
+        f.argtypes = [_vp, C.c_uint64]
+        _check(f(self.h, k))
+
     def stats(self):
         s = Stats()
         _check(load().mrg_get_stats(self.h, C.byref(s)))

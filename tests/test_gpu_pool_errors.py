@@ -4,7 +4,11 @@
 Every forced failure is a host-side range check of a test knob (MRG_TEST_TAIL_CAP, MRG_TEST_OVF_CAP,
 MRG_TEST_LONG_PER, MRG_TEST_WMAP_CAP = 2^32 - 1: no region of that size is asked for and no map kernel
 of that attempt is launched) or invalid UTF-8 in the input, which the map reports.  The inputs are three
-documents of the bundled corpus cut to 64 KiB; every expected output comes from the C oracle."""
+documents of the bundled corpus cut to 64 KiB; every expected output comes from the C oracle.
+
+The last test injects the failure instead (mrg_test_pool_fail: the k-th allocation of the context's pool throws)
+and sweeps k over every allocation of map, reduce, final and top-k, the .hip-side callers of the pool included
+(mrg_format, the wide aggregation's fallback)."""
 import collections
 import gzip
 import os
@@ -163,3 +167,103 @@ def test_vocabulary_calls_after_failed_map(ctx, env, docs, expect):
     ctx.job_begin(M.APP_WC, R)
     assert ctx.pool_stats()[0] == before, "scratch not returned"
     clean_job(ctx, docs, expect, M.APP_WC)
+
+
+# ---- every allocation of a job fails once (mrg_test_pool_fail): nothing stays out, the context stays usable
+
+SWEEP_NAMES = NAMES + ["d.txt"]
+STAGES = ("map", "reduce", "final", "topk")
+MAX_K = 2000
+INJECTED = "injected allocation failure"
+
+
+@pytest.fixture(scope="module")
+def sweep_docs(docs):
+    """The module's documents and one with keys of more than 16 bytes (the long-key path, k_fix_runs)."""
+    return docs + [b"x" * 40 + b" y " + b"z" * 23]
+
+
+@pytest.fixture(scope="module")
+def sweep_expect(sweep_docs):
+    """Per app, the oracle's (mr-{r}.txt contents, final.txt, the 5 most frequent lines) of the clean job."""
+    import mapreduce_rust_amd as M
+    import oracle_lib as O
+    exp = {}
+    for app, outs in ((M.APP_WC, O.wc(sweep_docs, R, O.FAST)), (M.APP_INDEXER, O.indexer(sweep_docs, SWEEP_NAMES, R))):
+        lines = sorted(l for o in outs for l in o.split(b"\n") if l)
+        top = b""
+        if app == M.APP_WC:
+            def order(ln):
+                key, c = ln.rsplit(b" ", 1)
+                return (-int(c), key)
+            top = b"".join(l + b"\n" for l in sorted(lines, key=order)[:5])
+        exp[app] = (outs, b"".join(l + b"\n" for l in lines), top)
+    return exp
+
+
+@pytest.mark.parametrize("app,knobs", [
+    ("wc", {}),
+    ("indexer", {}),
+    ("wc", dict(MRG_WIDE=1, MRG_TEST_LEAF_CAP=8)),   # the wide aggregation, its leaves overflowing into the fallback
+], ids=["wc", "indexer", "wc_wide_fallback"])
+def test_every_allocation_failure_returns_scratch(ctx, env, sweep_docs, sweep_expect, app, knobs):
+    """For each stage of a job (map, reduce, final, topk) the k-th pool allocation of the stage fails, k = 1, 2, ...
+    until the stage succeeds.  After every failure a clean job gives the oracle's outputs, and the blocks out after
+    it are those of the first clean job: a block stranded by the failed call would show as baseline + n (d_out,
+    d_final and d_top are context members: a failed regrow leaves one null and the clean job takes it again)."""
+    import time
+    import mapreduce_rust_amd as M
+    import torch
+    from gpu_util import to_device
+    app = M.APP_WC if app == "wc" else M.APP_INDEXER
+    stages = STAGES if app == M.APP_WC else STAGES[:3]
+    outs, final, top = sweep_expect[app]
+    env(**knobs)
+    t, off = to_device(sweep_docs)
+    call = {"map": ctx.map, "reduce": ctx.reduce, "final": ctx.final, "topk": lambda: ctx.topk(5)}
+
+    def begin():
+        ctx.job_begin(app, R)
+        if app == M.APP_INDEXER:
+            ctx.set_doc_names(SWEEP_NAMES)
+        ctx.set_input(t.data_ptr(), off)
+
+    def clean_job():
+        begin()
+        ctx.map()
+        ctx.reduce()
+        assert ctx.outputs() == outs
+        assert ctx.final() == final
+        if app == M.APP_WC:
+            assert ctx.topk(5) == top
+
+    clean_job()
+    if knobs:
+        assert ctx.stats()["overflow_keys"] > 0, "the fallback did not run"
+    ctx.job_begin(app, R)
+    baseline = ctx.pool_stats()[0]
+    failures = {}
+    for si, stage in enumerate(stages):
+        t0 = time.perf_counter()
+        for k in range(1, MAX_K + 2):
+            assert k <= MAX_K, f"{stage}: still failing at k = {k}"
+            begin()
+            for earlier in stages[:si]:
+                call[earlier]()
+            ctx.pool_fail(k)
+            try:
+                call[stage]()
+            except M.MrgError as e:
+                ctx.pool_fail(0)
+                assert e.code == M.native.ENOMEM and INJECTED in str(e), (stage, k, str(e))
+            else:
+                ctx.pool_fail(0)
+                break
+            clean_job()
+            ctx.job_begin(app, R)
+            assert ctx.pool_stats()[0] == baseline, f"{stage}: allocation {k} failed and blocks stayed out"
+        failures[stage] = k - 1
+        print(f"{stage}: {k - 1} injected failures, {time.perf_counter() - t0:.2f} s")
+    assert all(failures[s] >= 1 for s in stages), failures
+    torch.cuda.synchronize()
+    del t

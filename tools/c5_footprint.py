@@ -1,5 +1,5 @@
 """Device footprint of one C5 job on a fresh context: hipMalloc bytes of the pool (mrg_pool_alloc_stats),
-for the sampled (MRG_WIDE_L2_SAMPLED=1) and the exact (default) wide-map L2, on FILES x 256 MiB of near-unique keys.
+on FILES x 256 MiB of near-unique keys (the wide map and its L2), two fresh contexts of two jobs each.
 MRG_POOL_KEEP_GIB=0 so no context inherits another's blocks."""
 import os, sys
 os.environ["MRG_POOL_KEEP_GIB"] = "0"
@@ -15,8 +15,7 @@ with M.Context(0) as g:
         g.gen_unique(buf.data_ptr() + i * fb, fb, 0xC5, i)
 torch.cuda.synchronize()
 doc_off = [i * fb for i in range(files + 1)]
-for sampled in ("1", "0", "1", "0"):
-    os.environ["MRG_WIDE_L2_SAMPLED"] = sampled
+for ctx_no in range(2):
     with M.Context(0) as c:
         for rep in range(2):
             c.job_begin(M.APP_WC, 64)
@@ -25,4 +24,4 @@ for sampled in ("1", "0", "1", "0"):
             c.reduce()
             n, b, ms = c.pool_alloc_stats()
             st = c.stats()
-            print(f"L2_SAMPLED={sampled} job {rep}: {n} hipMalloc, {b / 2**30:.2f} GiB, {ms:.1f} ms; map_kind {st['map_kind']} keys {st['distinct_keys']}", flush=True)
+            print(f"context {ctx_no} job {rep}: {n} hipMalloc, {b / 2**30:.2f} GiB, {ms:.1f} ms; map_kind {st['map_kind']} keys {st['distinct_keys']}", flush=True)

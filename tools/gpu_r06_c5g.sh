@@ -4,7 +4,7 @@
 # per SIMD) vs lib_variants/lv512 (512 digits, 3 waves), alternated.
 mkdir -p gpurun_out/c5g
 timeout -k 10 500 python -u -m pytest tests/test_gpu_scale.py tests/test_gpu_ranks.py -m gpu -x -q --timeout 300 --timeout-method thread \
-  -k "l2_sampled or c5_slice or wide_map_forced or wide_packed or wide_many or rare_byte or wide_sample_sort or forced_collisions or cold_context or closed_context" \
+  -k "wide_map_l2 or c5_slice or wide_map_forced or wide_packed or wide_many or rare_byte or wide_sample_sort or forced_collisions or cold_context or closed_context" \
   > gpurun_out/c5g/tests.log 2>&1
 rc=$?; echo "tests rc=$rc: $(tail -1 gpurun_out/c5g/tests.log)"
 [ $rc -ne 0 ] && { grep -E "^E |FAILED" gpurun_out/c5g/tests.log | head -20; exit $rc; }
