@@ -124,7 +124,8 @@ typedef struct {
  * (6, additive): mrg_vocab_term_counts
  * (6, additive): mrg_vocab_postings
  * (6, additive): mrg_vocab_search
- * (6, additive): mrg_vocab_stats_add, mrg_vocab_search_shard, mrg_search_merge, MRG_SEARCH_MAX_SHARDS */
+ * (6, additive): mrg_vocab_stats_add, mrg_vocab_search_shard, mrg_search_merge, MRG_SEARCH_MAX_SHARDS
+ * (6, additive): mrg_vocab_postings_merge */
 #define MRG_ABI_VERSION 6
 
 const char *mrg_last_error(void);
@@ -456,6 +457,47 @@ int mrg_vocab_search_shard(mrg_ctx *ctx, const mrg_vocab *v, const uint64_t *d_p
 int mrg_search_merge(mrg_ctx *ctx, uint32_t n_shards, uint32_t n_queries, uint32_t k_in, const uint32_t *d_in_docs,
                      const float *d_in_scores, const uint32_t *h_in_top_n, uint32_t k_out, uint32_t *d_top_docs,
                      float *d_top_scores, uint32_t *h_top_n);
+
+/* (6, additive): mrg_vocab_postings_merge.  The indexes of the shards of one collection -> one index, on the
+ * device; the merged index is searched with the plain mrg_vocab_search.  Shard s is what mrg_vocab_postings wrote
+ * for this vocabulary: h_post_off[s] (device memory, words + 1 offsets), h_docs[s] and h_tf[s] (device memory, the
+ * documents carrying their doc_base, the term frequencies) and h_entries[s], its E.  The three tables are host
+ * arrays of n_shards device pointers.  The shards hold ascending document ranges in the order passed.
+ * d_post_off (device memory, 8-byte aligned, words + 1) receives d_post_off[w] = the sum over the shards of
+ * their offset of w: d_post_off[0] = 0 and d_post_off[words] = the sum of h_entries.  The postings of word w in
+ * d_docs are those of shard 0, then shard 1, ..., each shard's in its own order, with d_tf at the same positions.
+ * h_total may be NULL; otherwise it receives the sum of h_entries.  When the shards are consecutive row ranges
+ * of one CSR, in order, the three outputs equal those of mrg_vocab_postings over the whole CSR byte for byte,
+ * and are valid input of mrg_vocab_search with d_doc_len the caller's concatenation and doc_base the first
+ * shard's.  A merged index is a valid shard, so more than MRG_SEARCH_MAX_SHARDS shards merge in stages of
+ * adjacent shards.  The output is fully determined by the input: two calls give identical bytes; no atomic
+ * writes an offset or a posting.
+ * d_docs = NULL and d_tf = NULL: only the summed offsets are written, h_docs and h_tf may be NULL and no posting
+ * is read.  d_tf = NULL: documents only, h_tf may be NULL.  d_tf with h_tf = NULL or with d_docs = NULL:
+ * MRG_EINVAL.  A shard with 0 entries may have NULL document and term-frequency pointers.
+ * Refused before any device work, MRG_EINVAL with every output untouched: a NULL context, vocabulary,
+ * h_post_off, h_entries or d_post_off; a NULL h_post_off[s]; a vocabulary of another device; n_shards outside
+ * 1..MRG_SEARCH_MAX_SHARDS; misaligned pointers (4 bytes; offsets 8); a sum of h_entries >= 2^32; d_docs != NULL
+ * with cap (entries of d_docs and of d_tf) below that sum ("too small"); the NULL combinations above; entries in
+ * an empty vocabulary; an output range (d_post_off over words + 1 offsets, d_docs and d_tf over the sum of
+ * h_entries) that overlaps an input range of any shard.
+ * Checked on the device, MRG_EINVAL with the outputs unspecified; mrg_last_error names "shard S word N", the
+ * smallest word and for it the smallest shard.  The offsets of a shard: the first is 0, none is below the one
+ * before it (N: the word whose end is below its start), the last is h_entries[s] (N: the last word); these are
+ * checked before any posting is read or written, so the copy never leaves a shard's arrays or the sum of
+ * h_entries entries of the output.  The seams, when documents are merged: for a word, the last document of a
+ * non-empty shard list is strictly below the first document of the next non-empty one (S: the later shard), which
+ * makes the merged word ascend strictly, as mrg_vocab_search requires.  The order inside a shard's list is not
+ * checked here: the search checks what it visits.  After every error the context and the vocabulary stay usable.
+ * An empty vocabulary (every h_entries[s] must be 0) or all shards empty: all-zero offsets, MRG_OK.
+ * The call needs no job and touches no job state.  It runs on the context's stream with scratch from the
+ * context's pool, all returned before the call ends, on error exits too; on return the outputs are complete.
+ * Scratch: 40 bytes per shard and the scan's 8 bytes per 2048 words; when documents are merged, 4 bytes per
+ * (shard, word): the place of every list in the output.  Nothing per entry. */
+int mrg_vocab_postings_merge(mrg_ctx *ctx, const mrg_vocab *v, uint32_t n_shards, const uint64_t *const *h_post_off,
+                             const uint32_t *const *h_docs, const uint32_t *const *h_tf, const uint64_t *h_entries,
+                             uint64_t *d_post_off, uint32_t *d_docs, uint32_t *d_tf, uint64_t cap,
+                             uint64_t *h_total);
 
 /* ---- multi-GPU: one rank per GPU, the shuffle as an RCCL all-to-all over xGMI ----
  * The reference moves map output to the reduce workers through mr-{m}-{r}.txt files in a shared

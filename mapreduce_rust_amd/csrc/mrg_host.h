@@ -266,6 +266,7 @@ struct Acc {
 //   mrg_vocab_decode        info and ms[0..2]; ms[3], the time of the last mrg_vocab_from_text, stays
 //   mrg_vocab_term_counts, mrg_vocab_postings, mrg_vocab_search   everything (they write ms[0..3], ms[0..4], ms[0..3])
 //   mrg_vocab_search_shard  as mrg_vocab_search, in the same record; mrg_vocab_stats_add and mrg_search_merge keep none
+//   mrg_vocab_postings_merge  everything (it writes ms[0..2])
 struct VocDiag {
     uint64_t info[8] = {};
     double ms[5] = {};
@@ -339,8 +340,9 @@ struct mrg_ctx {
     uint64_t top_pass_bytes[MRG_TOPK_DIGITS] = {};  // bytes each of its select passes read (0: pass not run)
     uint64_t extra_first = 0;       // text reduce: values of empty-key lines, folded into the first group
     mrg_stats st{};
-    // last mrg_vocab_encode, _decode, _term_counts, _postings, _search (the slots: mrg_*_info in mrg_vocab.cpp)
-    mrg_host::VocDiag enc, dec, terms, post, srch;
+    // last mrg_vocab_encode, _decode, _term_counts, _postings, _search, _postings_merge (the slots: mrg_*_info in
+    // mrg_vocab.cpp)
+    mrg_host::VocDiag enc, dec, terms, post, srch, pmrg;
 };
 
 // A vocabulary (mrg_job_vocab, mrg_vocab_from_text): one device allocation of its own -- the "word count\n"

@@ -814,6 +814,30 @@ struct MergePlan {
 };
 void mrg_merge_launch(const MergePlan &m, hipStream_t s);
 
+// ---- k_postings_merge.hip: the indexes of the shards of one collection -> one index
+struct PMergeShard {  // 40 bytes; a device table of n_shards
+    const uint64_t *off;         // [n_words + 1] the shard's offsets
+    const uint32_t *docs, *tf;   // its n entries (null where they are not merged, or n = 0)
+    uint64_t n;
+    uint64_t tile0;              // the copy grid's first tile of this shard: the tiles of the lower shards
+};
+// One mrg_vocab_postings_merge call.
+struct PMergePlan {
+    const PMergeShard *sh;
+    uint32_t n_shards;
+    uint64_t n_words;
+    uint64_t n_tiles;            // of MRG_PMERGE_TILE source entries, over all shards
+    uint64_t *post_off;          // [n_words + 1] the output: summed frequencies, then (scanned in place) offsets
+    uint32_t *docs, *tf;         // the outputs (tf may be null)
+    uint32_t *dst;               // [n_shards * n_words]: the output position of shard s's first posting of word w
+    // [2]: all ones, then the smallest word * 64 + shard that fails a check (atomicMin); zero, then the tiles that
+    // lie inside one word
+    unsigned long long *stat;
+};
+void mrg_pmerge_launch_sum(const PMergePlan &p, hipStream_t s);    // checks the offsets, fills post_off (unscanned)
+void mrg_pmerge_launch_place(const PMergePlan &p, hipStream_t s);  // needs the scanned post_off; fills dst, checks the seams
+void mrg_pmerge_launch_copy(const PMergePlan &p, hipStream_t s);   // needs dst
+
 // ---- k_gen.hip
 int mrg_gen_zipf_impl(uint8_t *dst, uint64_t n, uint64_t seed, uint64_t file_index, uint32_t vocab, double s, uint32_t style,
                       hipStream_t st);

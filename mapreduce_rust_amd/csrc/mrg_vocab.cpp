@@ -942,6 +942,122 @@ void search_merge(mrg_ctx *c, uint32_t n_shards, uint32_t n_queries, uint32_t k_
     std::copy(top.begin(), top.end(), h_top_n);
 }
 
+// The indexes of the shards of one collection -> the index of the whole (k_postings_merge.hip, DESIGN.md section
+// 31): the shards' offsets are checked and summed per word, a scan gives the merged offsets; then every (shard,
+// word) list gets its place in the output, the seams between the shards are checked, and the lists are copied.
+void vocab_postings_merge(mrg_ctx *c, const mrg_vocab *v, uint32_t n_shards, const uint64_t *const *h_post_off,
+                          const uint32_t *const *h_docs, const uint32_t *const *h_tf, const uint64_t *h_entries,
+                          uint64_t *d_post_off, uint32_t *d_docs, uint32_t *d_tf, uint64_t cap, uint64_t *h_total) {
+    const char *fn = "mrg_vocab_postings_merge";
+    voc_args(c, v, 0);
+    if (!h_post_off || !h_entries) raise(MRG_EINVAL, "null h_post_off or h_entries (n_shards entries each)");
+    if (!d_post_off) raise(MRG_EINVAL, "null d_post_off (it receives the vocabulary's words + 1 offsets)");
+    if (n_shards < 1u || n_shards > MRG_SEARCH_MAX_SHARDS)
+        raise(MRG_EINVAL, "n_shards = %u: 1 to %u (more shards merge in stages)", n_shards, MRG_SEARCH_MAX_SHARDS);
+    if (d_tf && !d_docs) raise(MRG_EINVAL, "d_tf without d_docs");
+    if (d_tf && !h_tf) raise(MRG_EINVAL, "d_tf without h_tf");
+    if (d_docs && !h_docs) raise(MRG_EINVAL, "d_docs without h_docs");
+    if (((uintptr_t)d_docs | (uintptr_t)d_tf) & 3u) raise(MRG_EINVAL, "d_docs and d_tf must be 4-byte aligned");
+    if ((uintptr_t)d_post_off & 7u) raise(MRG_EINVAL, "d_post_off must be 8-byte aligned");
+    const uint64_t n_words = v->n;
+    uint64_t total = 0;
+    for (uint32_t s = 0; s < n_shards; ++s) {
+        if (!h_post_off[s]) raise(MRG_EINVAL, "%s: shard %u: null offsets (h_post_off[s]: the vocabulary's words + 1)", fn, s);
+        if ((uintptr_t)h_post_off[s] & 7u) raise(MRG_EINVAL, "%s: shard %u: the offsets must be 8-byte aligned", fn, s);
+        if (h_entries[s] > 0xFFFFFFFFull || (total += h_entries[s]) > 0xFFFFFFFFull)
+            raise(MRG_EINVAL, "%s: more than 4294967295 entries in the shards up to shard %u", fn, s);
+        if (!n_words && h_entries[s]) raise(MRG_EINVAL, "%s: shard %u: %llu entries of an empty vocabulary", fn, s,
+                                            (unsigned long long)h_entries[s]);
+        if (d_docs && h_entries[s] && !h_docs[s]) raise(MRG_EINVAL, "%s: shard %u: null documents with %llu entries", fn, s,
+                                                        (unsigned long long)h_entries[s]);
+        if (d_tf && h_entries[s] && !h_tf[s]) raise(MRG_EINVAL, "%s: shard %u: null term frequencies with %llu entries", fn,
+                                                    s, (unsigned long long)h_entries[s]);
+        if (((d_docs ? (uintptr_t)h_docs[s] : 0u) | (d_tf ? (uintptr_t)h_tf[s] : 0u)) & 3u)
+            raise(MRG_EINVAL, "%s: shard %u: the documents and term frequencies must be 4-byte aligned", fn, s);
+    }
+    if (d_docs && cap < total) raise(MRG_EINVAL, "destination too small (%llu entries < %llu postings)", (unsigned long long)cap,
+                                     (unsigned long long)total);
+    // no output range may overlap an input range (the copy reads while others write)
+    struct Range {
+        uintptr_t a, e;
+        const char *what;
+    };
+    const Range outs[3] = {{(uintptr_t)d_post_off, (uintptr_t)d_post_off + 8 * (n_words + 1), "d_post_off"},
+                           {(uintptr_t)d_docs, (uintptr_t)d_docs + (d_docs ? 4 * total : 0), "d_docs"},
+                           {(uintptr_t)d_tf, (uintptr_t)d_tf + (d_tf ? 4 * total : 0), "d_tf"}};
+    for (uint32_t s = 0; s < n_shards; ++s) {
+        const Range ins[3] = {{(uintptr_t)h_post_off[s], (uintptr_t)h_post_off[s] + 8 * (n_words + 1), "offsets"},
+                              {d_docs ? (uintptr_t)h_docs[s] : 0u, (d_docs ? (uintptr_t)h_docs[s] + 4 * h_entries[s] : 0u), "documents"},
+                              {d_tf ? (uintptr_t)h_tf[s] : 0u, (d_tf ? (uintptr_t)h_tf[s] + 4 * h_entries[s] : 0u), "term frequencies"}};
+        for (const Range &o : outs)
+            for (const Range &i : ins)
+                if (o.a < o.e && i.a < i.e && o.a < i.e && i.a < o.e)
+                    raise(MRG_EINVAL, "%s: %s overlaps the %s of shard %u", fn, o.what, i.what, s);
+    }
+    HIPCHK(hipSetDevice(c->device));
+    c->pmrg.clear(3);
+    c->pmrg.info[0] = total;
+    c->pmrg.info[1] = n_words;
+    c->pmrg.info[2] = n_shards;
+    hipStream_t s = c->stream;
+    Scratch sc(c->pool);
+    c->pmrg.make(c);
+    std::vector<PMergeShard> tab(n_shards);
+    PMergePlan P{};
+    for (uint32_t i = 0; i < n_shards; ++i) {
+        tab[i] = PMergeShard{h_post_off[i], d_docs && h_entries[i] ? h_docs[i] : nullptr,
+                             d_tf && h_entries[i] ? h_tf[i] : nullptr, h_entries[i], P.n_tiles};
+        P.n_tiles += (h_entries[i] + MRG_PMERGE_TILE - 1u) / MRG_PMERGE_TILE;
+    }
+    PMergeShard *d_tab = sc.get<PMergeShard>(n_shards);
+    P.sh = d_tab;
+    P.n_shards = n_shards;
+    P.n_words = n_words;
+    P.post_off = d_post_off;
+    P.stat = sc.get<unsigned long long>(2);
+    uint64_t *stmp = sc.get<uint64_t>(mrg_scan_tmp_elems(n_words + 1));
+    uint64_t scratch = sizeof(PMergeShard) * n_shards + 16 + 8 * mrg_scan_tmp_elems(n_words + 1);
+    c->pmrg.info[5] = scratch;
+    HIPCHK(hipMemcpyAsync(d_tab, tab.data(), sizeof(PMergeShard) * n_shards, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(P.stat, 0xFF, 8, s));
+    HIPCHK(hipMemsetAsync(P.stat + 1, 0, 8, s));
+    // ---- check and sum the offsets, then the merged offsets
+    c->pmrg.rec(c, 0);
+    mrg_pmerge_launch_sum(P, s);
+    mrg_scan_u64(d_post_off, d_post_off, n_words + 1, stmp, s);  // d_post_off[n_words] = total
+    c->pmrg.rec(c, 1);
+    HIPCHK(hipGetLastError());
+    unsigned long long hstat[2] = {};
+    HIPCHK(hipMemcpyAsync(hstat, P.stat, 8, hipMemcpyDeviceToHost, s));
+    sync(c);  // (also: the pageable table has been read)
+    c->pmrg.ms[0] = c->pmrg.elapsed(c, 0, 1);
+    if (hstat[0] != ~0ull)
+        raise(MRG_EINVAL, "%s: shard %llu word %llu: the offsets of a shard must start at 0, not decrease, and end at its "
+                          "h_entries", fn, hstat[0] & 63u, hstat[0] >> 6);
+    if (h_total) *h_total = total;
+    if (!d_docs || !total) return;
+    // ---- the place of every (shard, word) list with the seams, then the copy
+    P.docs = d_docs;
+    P.tf = d_tf;
+    P.dst = sc.get<uint32_t>((uint64_t)n_shards * n_words);
+    c->pmrg.info[3] = P.n_tiles;
+    c->pmrg.info[5] = scratch + 4 * (uint64_t)n_shards * n_words;
+    c->pmrg.rec(c, 2);
+    mrg_pmerge_launch_place(P, s);
+    c->pmrg.rec(c, 3);
+    mrg_pmerge_launch_copy(P, s);
+    c->pmrg.rec(c, 4);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(hstat, P.stat, sizeof hstat, hipMemcpyDeviceToHost, s));
+    sync(c);
+    c->pmrg.ms[1] = c->pmrg.elapsed(c, 2, 3);
+    c->pmrg.ms[2] = c->pmrg.elapsed(c, 3, 4);
+    c->pmrg.info[4] = hstat[1];
+    if (hstat[0] != ~0ull)
+        raise(MRG_EINVAL, "%s: shard %llu word %llu: the shard's first document of the word is not above the last document "
+                          "of the word in the shards before it", fn, hstat[0] & 63u, hstat[0] >> 6);
+}
+
 // one of the mrg_*_info entry points: all of the record's info, the first n_ms of its milliseconds
 int voc_info(mrg_ctx *c, VocDiag mrg_ctx::*diag, int n_ms, uint64_t *h_info, double *h_ms) {
     return guard([&] {
@@ -1064,6 +1180,19 @@ int mrg_search_merge(mrg_ctx *c, uint32_t n_shards, uint32_t n_queries, uint32_t
         search_merge(c, n_shards, n_queries, k_in, d_in_docs, d_in_scores, h_in_top_n, k_out, d_top_docs, d_top_scores, h_top_n);
     });
 }
+
+int mrg_vocab_postings_merge(mrg_ctx *c, const mrg_vocab *v, uint32_t n_shards, const uint64_t *const *h_post_off,
+                             const uint32_t *const *h_docs, const uint32_t *const *h_tf, const uint64_t *h_entries,
+                             uint64_t *d_post_off, uint32_t *d_docs, uint32_t *d_tf, uint64_t cap, uint64_t *h_total) {
+    return guard([&] {
+        vocab_postings_merge(c, v, n_shards, h_post_off, h_docs, h_tf, h_entries, d_post_off, d_docs, d_tf, cap, h_total);
+    });
+}
+
+// Diagnostics of the last mrg_vocab_postings_merge (not in include/mrgpu.h; tools/time_postings_merge.py):
+// h_info[0..6) = entries, words, shards, copy tiles, copy tiles inside one word, scratch bytes; h_ms[0..3) = sum
+// with the scan, place (with the seams), copy (HIP events, with mrg_set_timing).
+int mrg_postings_merge_info(mrg_ctx *c, uint64_t *h_info, double *h_ms) { return voc_info(c, &mrg_ctx::pmrg, 3, h_info, h_ms); }
 
 // Diagnostics of the last mrg_vocab_search or mrg_vocab_search_shard (not in include/mrgpu.h; tools/time_search.py,
 // tools/time_search_shards.py): h_info[0..6) =

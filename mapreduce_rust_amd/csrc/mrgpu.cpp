@@ -2535,7 +2535,7 @@ int mrg_close(mrg_ctx *c) {
         (void)hipSetDevice(c->device);
         (void)hipStreamSynchronize(c->stream);
         for (auto &e : c->ev) (void)hipEventDestroy(e);
-        for (VocDiag *d : {&c->enc, &c->dec, &c->terms, &c->post, &c->srch}) d->destroy();
+        for (VocDiag *d : {&c->enc, &c->dec, &c->terms, &c->post, &c->srch, &c->pmrg}) d->destroy();
         (void)hipFree(c->d_cnt);
         (void)hipHostFree(c->h_cnt);
         if (c->h_stage) (void)hipHostFree(c->h_stage);

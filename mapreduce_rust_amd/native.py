@@ -37,6 +37,9 @@ SEARCH_MAX_K = 1024
 # MERGE_LDS_KEYS, and read from global memory otherwise (MRG_SEARCH_MAX_SHARDS, MRG_MERGE_LDS_KEYS of csrc/mrg_device.h)
 SEARCH_MAX_SHARDS = 64
 MERGE_LDS_KEYS = 8192
+# postings_merge: one workgroup copies PMERGE_TILE consecutive entries of one shard (MRG_PMERGE_TILE of
+# csrc/mrg_device.h)
+PMERGE_TILE = 2048
 
 
 def debug_hash_bits(n):
@@ -141,6 +144,8 @@ _SIGS = {
     "mrg_vocab_search_shard": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint64, _vp, C.c_uint32, C.c_uint32, _vp, C.c_uint64,
                                          C.c_uint64, _vp, _u64p, C.c_uint32, C.c_float, C.c_float, C.c_uint32, _vp, _vp, _u32p]),
     "mrg_search_merge": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _u32p, C.c_uint32, _vp, _vp, _u32p]),
+    "mrg_vocab_postings_merge": (C.c_int, [_vp, _vp, C.c_uint32, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _u64p, _vp, _vp,
+                                           _vp, C.c_uint64, _u64p]),
     "mrg_map": (C.c_int, [_vp, C.c_int, C.c_char_p, C.c_size_t, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32,
                           C.POINTER(_vp)]),
     "mrg_parts_get": (C.c_int, [_vp, C.c_uint32, C.POINTER(_vp), _u64p, C.POINTER(_vp), _u64p]),
@@ -603,6 +608,29 @@ class Context:
         _check(load().mrg_search_merge(self.h, n_shards, n_queries, k_in, in_docs_ptr, in_scores_ptr,
                                        (C.c_uint32 * max(len(in_top_n), 1))(*in_top_n), k_out, top_docs_ptr, top_scores_ptr, top))
         return list(top)[:n_queries]
+
+    def postings_merge(self, vocab, shards, post_off_ptr, docs_ptr=None, tf_ptr=None, cap=0):
+        """mrg_vocab_postings_merge: the indexes of the shards of one collection -> one index, which search() takes.
+        shards is a sequence of (post_off_ptr, docs_ptr, tf_ptr, n_entries), what postings() wrote and returned for
+        consecutive document ranges, in order (docs_ptr and tf_ptr may be None where they are not merged, or with 0
+        entries).  post_off_ptr (uint64, the vocabulary's words + 1) receives the summed offsets; docs_ptr and tf_ptr
+        (cap uint32 each) the postings of every word: shard 0's, then shard 1's, ...  docs_ptr and tf_ptr None:
+        offsets only; tf_ptr None: documents only.  Returns the number of entries."""
+        shards = list(shards)
+        n = len(shards)
+        col = lambda j: (_vp * max(n, 1))(*[s[j] for s in shards])
+        total = C.c_uint64()
+        _check(load().mrg_vocab_postings_merge(self.h, vocab.h, n, col(0), col(1), col(2),
+                                               _u64arr([int(s[3]) for s in shards]), post_off_ptr, docs_ptr, tf_ptr, cap,
+                                               C.byref(total)))
+        return total.value
+
+    def postings_merge_info(self):
+        """Diagnostics of the last postings_merge(): entries, words, shards, copy tiles, copy tiles inside one word,
+        scratch bytes; HIP-event ms per phase (with set_timing)."""
+        return _voc_info("mrg_postings_merge_info", self, ("entries", "words", "shards", "tiles", "single_word_tiles",
+                                                           "scratch_bytes"),
+                         ("ms_sum", "ms_place", "ms_copy"))
 
     def search_info(self):
         """Diagnostics of the last search(): queries, query positions, postings visited, chunks, accumulate
