@@ -14,7 +14,7 @@
 //                 that walks the table).
 //   k_acc_emit    the full slots as a dense KeySet (len from the packed key, hoff = MRG_NO_HEAP).
 //   k_acc_long    the batch's long keys (> 16 bytes) as long items over the concatenated heap; they are
-//                 kept beside the table and re-grouped by the existing long-key path (mrgpu.cpp).
+//                 kept beside the table and re-grouped by the existing long-key path (mrg_agg.cpp acc_fold).
 // Conventions (as k_topk.hip): wave64; every ballot / workgroup barrier is reached by all lanes -- lanes
 // out of range are predicated off, never returned early; probe loops diverge per lane and reconverge
 // before the next cross-lane operation; no scratch.

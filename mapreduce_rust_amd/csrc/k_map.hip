@@ -427,7 +427,7 @@ __device__ __forceinline__ bool walk_token(const RD &rd, uint64_t a, uint64_t do
 }
 
 // Tail regions of this workgroup, one per hash bucket b and record class.  Two forms, chosen by the
-// host per launch (mrgpu.cpp map_tail_packed) and compiled as the kernel's T64 flag:
+// host per launch (mrg_map.cpp map_tail_packed) and compiled as the kernel's T64 flag:
 //   packed (T64 = false): cur[b] is ONE word per (bucket, class): low 32 bits = the pool record index
 //     of the next append (starts at the region's first record), high 32 bits = one past the region's
 //     last record.  An append is one 64-bit LDS add of 0 or 1 that returns index and end together;
@@ -1038,7 +1038,7 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
                             sizeof(s_wix) == MRG_WMAP_IXR * MRG_WIDE_IX1 && MRG_WIDE_IX1 % 4 == 0),
                   "wide map: cursors, splitters and index rows as the host plan sizes them");
     // the wide map's run-time sizes against those arrays (the host plan keeps R * B1r <= MRG_WMAP_MAXB1
-    // and passes an index only when R <= MRG_WMAP_IXR, mrgpu.cpp wide_map_plan; job_map_wide refuses
+    // and passes an index only when R <= MRG_WMAP_IXR, mrg_map.cpp wide_map_plan; job_map_wide refuses
     // a plan that breaks them before the launch): a launch that still did would return here, uniformly,
     // instead of indexing past LDS
     if constexpr (WIDE) {

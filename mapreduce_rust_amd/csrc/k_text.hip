@@ -235,7 +235,7 @@ __global__ void k_utf8_check(const uint8_t *in, uint64_t n, unsigned long long *
 // (out == null) or emit one exchange record per non-empty line with a non-empty key.  A line must
 // have exactly one ' ' (worker.rs:100 assert!); a key with a NUL byte has no packed form (the
 // reference's map never writes one): both are reported in err[1].  Lines with an empty key are
-// counted in nempty (the reduce loop folds them into the next group, see mrgpu.cpp).
+// counted in nempty (the reduce loop folds them into the next group, see mrg_reduce.cpp job_reduce).
 __global__ void k_text_lines(const uint8_t *in, const uint64_t *fo, const uint64_t *fe, uint32_t nf, uint64_t nseg,
                              const uint64_t *base, uint64_t *cnt, LRec *out, unsigned long long *err,
                              unsigned long long *nempty) {

@@ -15,7 +15,7 @@
 //            the byte-largest candidate of a partition can be that key, and it is iff no key of the
 //            partition exceeds it: one streaming pass over (part, k0), no sort.
 // The candidates are then ordered by the existing sorts and formatted by the existing line writer
-// (mrgpu.cpp job_topk).  Every ballot / shuffle below runs in loops whose trip count is uniform per
+// (mrg_reduce.cpp job_topk).  Every ballot / shuffle below runs in loops whose trip count is uniform per
 // workgroup, with out-of-range lanes predicated off, never returned early.
 #include <algorithm>
 

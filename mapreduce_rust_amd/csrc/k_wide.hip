@@ -18,7 +18,7 @@
 //       to the last non-empty leaf of each partition), one workgroup per L1 bucket formats its
 //       leaves' lines through LDS and stores them as whole dwords.
 // Leaves whose distinct keys do not fit the LDS table (sample outliers, adversarial key sets) are
-// listed and finished by a global radix sort of their records (mrgpu.cpp).
+// listed and finished by a global radix sort of their records (mrg_agg.cpp wide_finish).
 // Order within a leaf: (k0, k1) unsigned = key bytes (mrg_device.h), one partition per L1 bucket.
 #include "mrg_device.h"
 #include "mrg_internal.h"
@@ -1272,7 +1272,7 @@ __global__ __launch_bounds__(W_LWG, 3) void k_wleaf(LeafArgs L) {
         }
         lds_barrier();
         WP(1);
-        if (s_ovf) {  // finished by the global fallback (mrgpu.cpp)
+        if (s_ovf) {  // finished by the global fallback (mrg_agg.cpp wide_finish)
             if (tid == 0) {
                 const unsigned long long k = atomicAdd(L.ovf_n, 1ull);
                 L.ovf_list[k] = (uint32_t)lid;
@@ -2339,7 +2339,7 @@ inline dim3 gridw(uint64_t n, int b = 256) { return dim3((unsigned)((n + b - 1) 
 
 }  // namespace
 
-// ================================================================ host launchers (mrgpu.cpp)
+// ================================================================ host launchers (mrg_map.cpp, mrg_agg.cpp, mrg_reduce.cpp)
 void mrg_wide_launch_counts(const BucketArgs &a, uint64_t *cnt_main, uint64_t *segptr, uint64_t *cnt_flush,
                             hipStream_t s) {
     const uint64_t nsm = 2ull * a.nreg * MRG_NBUCKET + MRG_NBUCKET;

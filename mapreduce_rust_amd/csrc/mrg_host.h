@@ -1,7 +1,10 @@
-// mrg_host.h -- what the host units of libmrgpu.so share (mrgpu.cpp, mrg_vocab.cpp): the guard that ends the
-// error path at the C ABI, the device-block pool, the context and the vocabulary, and a few helpers.  The
-// error path itself (MrgError, raise, HIPCHK) and the pool's scope guard (Scratch) live in mrg_internal.h,
-// because the .hip files' host functions use them too.
+// mrg_host.h -- what the host units of libmrgpu.so share (mrgpu.cpp, mrg_map.cpp, mrg_agg.cpp, mrg_reduce.cpp,
+// mrg_exchange.cpp, mrg_plugin.cpp, mrg_run.cpp, mrg_vocab.cpp): the guard that ends the error path at the C ABI,
+// the device-block pool, the context and the vocabulary, a few helpers, and -- at the end, one block per defining
+// unit -- the functions of the job side that another unit calls, with the structs their signatures need.  A unit's
+// other helpers stay in its own anonymous namespace.  The error path itself (MrgError, raise, HIPCHK) and the
+// pool's scope guard (Scratch) live in mrg_internal.h, because the .hip files' host functions use them too; the
+// RCCL communicator is mrg_comm.h, for the two units that need it.
 // Host only: no .hip file includes it.  Nothing here joins the library's exported symbols.
 #pragma once
 #include <stdarg.h>
@@ -394,11 +397,126 @@ inline uint32_t bytes_for(uint64_t maxval) {
     return b;
 }
 
-// the job side, as far as mrg_job_vocab needs it (job_topk: mrgpu.cpp)
 inline void need_job(mrg_ctx *c) {
     if (!c) raise(MRG_EINVAL, "null context");
     if (!c->job) raise(MRG_EINVAL, "no job: call mrg_job_begin first");
 }
+
+// ---------------------------------------------------------------- the job side: what one unit calls of another
+
+// the context's pinned staging region and its device copy (made by mrg_open, filled by mrg_map.cpp)
+constexpr size_t MRG_STAGE_BYTES = 256u << 10;
+
+// ---- mrgpu.cpp
+void check_sort_n(uint64_t n, const char *what);
+uint64_t env_u64(const char *name, uint64_t dflt);
+void job_begin(mrg_ctx *c, int app, uint32_t R, uint32_t flags);
+
+// ---- mrg_map.cpp
+void flush_stage(mrg_ctx *c);
+void read_counters(mrg_ctx *c);
+void job_map(mrg_ctx *c);
+
+// ---- mrg_agg.cpp
+void keysbuf_release(Pool &p, KeysBuf &k);
+void acc_release(mrg_ctx *c);
+
+struct ShortSrc {
+    const uint64_t *k0 = nullptr, *k1 = nullptr;
+    const uint32_t *cnt = nullptr, *doc = nullptr;
+    const XRec *x = nullptr;   // exchange records (short form only; long ones take the long path)
+    const LRec *lx = nullptr;  // text-reduce line records
+    uint64_t n = 0;
+};
+void aggregate(mrg_ctx *c, const ShortSrc &src, LongItems li);
+
+// One launch of the per-bucket aggregation; owns its overflow list (B.ok0, ok1, ocnt, odoc).
+struct AggLaunch {
+    BucketArgs B{};
+    uint64_t nlong = 0;  // long keys the launch reserved key slots for
+    bool c32 = false;
+    Scratch own;
+    explicit AggLaunch(Pool &p) : own(p) {}
+    AggLaunch(AggLaunch &&) = default;
+    AggLaunch &operator=(AggLaunch &&) = default;
+    bool live() const { return !own.b.empty(); }
+    void drop() { own.put_all(); }  // the overflow list back to the pool
+};
+uint64_t agg_ocap(mrg_ctx *c);
+AggLaunch agg_launch(mrg_ctx *c, const MapArgs &A, uint32_t nreg, uint32_t regcap, uint64_t ocap, uint32_t nsub,
+                     uint64_t nlong, bool c32, bool zero);
+bool bucket_aggregate(mrg_ctx *c, const MapArgs &A, uint32_t nreg, uint32_t regcap, LongItems li,
+                      AggLaunch *pre = nullptr);
+
+SortPlan part_key_plan(uint32_t R);
+void wide_aggregate(mrg_ctx *c, const MapArgs &A, uint32_t nreg, uint32_t regcap, LongItems li);
+void wide_densify(mrg_ctx *c, uint64_t extra);
+
+// MRG_DEBUG: the HIP-event time of the phases of one wide aggregation.  The first mark starts the clock; every
+// later one ends a phase and names it.  The events are the clock's own and go with it on every exit.
+struct PhaseClock {
+    const bool on = getenv("MRG_DEBUG") != nullptr;
+    hipStream_t s;
+    std::vector<std::pair<hipEvent_t, const char *>> ev;
+    explicit PhaseClock(hipStream_t st) : s(st) {}
+    PhaseClock(const PhaseClock &) = delete;
+    PhaseClock &operator=(const PhaseClock &) = delete;
+    ~PhaseClock() {
+        for (auto &m : ev) (void)hipEventDestroy(m.first);
+    }
+    void mark(const char *name) {
+        if (!on) return;
+        hipEvent_t e = nullptr;
+        HIPCHK(hipEventCreate(&e));
+        ev.push_back({e, name});
+        HIPCHK(hipEventRecord(e, s));
+    }
+    void report() {  // (the stream has reached the last mark)
+        fprintf(stderr, "[mrgpu] wide phases (ms):");
+        for (size_t i = 1; i < ev.size(); ++i) {
+            float ms = 0;
+            HIPCHK(hipEventElapsedTime(&ms, ev[i - 1].first, ev[i].first));
+            fprintf(stderr, " %s %.2f", ev[i].second, ms);
+        }
+        fprintf(stderr, "\n");
+    }
+};
+
+// What the first level hands to wide_finish: n records in L1 buckets, bucket b = partition * B1r + key
+// range (bstart[b] .. bstart[b + 1]) -- L1's output K1, or (wm.rin) the wide map's regions -- the
+// splitters that cut them, and the nw weighted keys (the flushed map tables, aggregated and sorted).
+struct WideL1 {
+    uint64_t n = 0, nw = 0;
+    uint32_t B1 = 0, B1r = 0;
+    uint64_t *K1 = nullptr;      // [2 (n + nw) + 2] L1's output, then the leaves' output keys
+    uint64_t *bstart = nullptr;  // [B1 + 1]
+    uint64_t *spl1 = nullptr;
+    uint16_t *bid = nullptr;     // [n] L1 bucket, then L2 leaf, of each record
+    uint64_t *wk0 = nullptr, *wk1 = nullptr, *wcnt = nullptr;
+    uint32_t *wpart = nullptr;
+    WmapIn wm;
+};
+void wide_finish(mrg_ctx *c, Scratch &own, const WideL1 &l1, LongItems li, PhaseClock &clock);
+
+void acc_emit(mrg_ctx *c);
+void job_map_add(mrg_ctx *c);
+
+// ---- mrg_reduce.cpp
+void job_reduce(mrg_ctx *c);
+void job_final(mrg_ctx *c);
 SortRec *job_topk(mrg_ctx *c, uint64_t k, Scratch *keep = nullptr);
+
+// ---- mrg_exchange.cpp (its communicator side: mrg_comm.h)
+void export_sizes(mrg_ctx *c, uint32_t n_owners, uint64_t *h_rec, uint64_t *h_heap);
+void export_pack(mrg_ctx *c, void *d_rec, void *d_heap, bool wait = true);
+void import_recs(mrg_ctx *c, const XRec *xr, const LRec *lr, uint64_t n_rec, const void *d_heap, uint64_t heap_bytes,
+                 const uint64_t *seg_recs, const uint64_t *seg_heap, uint32_t n_segs);
+void job_import(mrg_ctx *c, const void *d_rec, uint64_t n_rec, const void *d_heap, uint64_t heap_bytes,
+                const uint64_t *seg_recs, const uint64_t *seg_heap, uint32_t n_segs);
+void job_shuffle(mrg_ctx *c, mrg_comm *m);
+void test_fail(const char *stage, int rank);
+
+// ---- mrg_plugin.cpp
+void check_names(const char *const *names, uint32_t n);
 
 }  // namespace mrg_host

@@ -209,20 +209,20 @@ struct MapArgs {
     uint32_t w12, wl16cap;
     uint64_t *wl16;
     uint32_t *wl16n;
-    // load balance (mrgpu.cpp map_steal): blocks [0, n_static) are split into
+    // load balance (mrg_map.cpp map_steal): blocks [0, n_static) are split into
     // equal workgroup shares; blocks [n_static, n_chunks) are a pool in 8 parts, part j's next block at
     // pool_ctr[16 * j] (zeroed per launch), that a wave takes MRG_MAP_STEAL_K blocks at a time once its
     // workgroup's share is done, at most steal_max blocks per workgroup: a claim that would pass the
     // budget is not made (the per-workgroup capacities are sized for share + steal_max + one claim).
     // n_static = n_chunks: static shares only.  run: consecutive blocks of its workgroup's share a wave
-    // claims per LDS atomic (MRG_MAP_RUN where a share is long enough, else shorter: mrgpu.cpp map_steal;
+    // claims per LDS atomic (MRG_MAP_RUN where a share is long enough, else shorter: mrg_map.cpp map_steal;
     // 1 = one block per claim).
     uint64_t n_static;
     uint32_t steal_max;
     uint32_t run;
     unsigned long long *pool_ctr;
 };
-// One staged small write of a job's setup (mrgpu.cpp stage_h2d / stage_fill): `n` bytes to `dst`, from
+// One staged small write of a job's setup (mrg_map.cpp stage_h2d / stage_fill): `n` bytes to `dst`, from
 // offset `src` of the device copy of the pinned staging buffer, or the byte `fill` when src == ~0u.
 // A batch of them is one host-to-device copy and one k_stage_scatter launch (was one copy or memset
 // each, ~8 us apiece on the stream).
@@ -295,7 +295,7 @@ struct LongItems {
 // `dev_args` is device memory for one MapArgs (the kernel reads its arguments from there)
 // h: the args to copy to dev_args first (nullptr: already there)
 // tail64: the 64-bit tail cursors; false: the packed ones, valid only for a launch that passes
-// map_tail_packed (mrgpu.cpp).  The wide map has neither.
+// map_tail_packed (mrg_map.cpp).  The wide map has neither.
 void mrg_launch_map(const MapArgs *h, MapArgs *dev_args, int app, int grid, int lds_cap, hipStream_t s,
                     bool wide = false, bool tail64 = true);
 uint64_t mrg_map_tiles(uint64_t doc_lo, uint64_t doc_hi);  // wave blocks (NSUB KiB) of a document (16-B grid)

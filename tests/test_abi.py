@@ -57,7 +57,7 @@ def test_record_layout_constant():
 
 
 def test_merge_sorted_lines_host():
-    """The host k-way merge of the GPUs' sorted final.txt runs (mrgpu.cpp merge_sorted_lines, the
+    """The host k-way merge of the GPUs' sorted final.txt runs (mrg_run.cpp merge_sorted_lines, the
     multi-GPU half of run.sh:16-20 `cat mr-* | sort`): equals sorted() of all lines, byte order (C
     locale), with runs lacking a final newline, equal prefixes, duplicates across runs and empty runs."""
     import random

@@ -169,7 +169,7 @@ def test_codepoint_density_sweep_vs_oracle(ctx, gap):
 
 @pytest.mark.parametrize("steal", ["2", "16"])
 def test_map_block_pool_vs_oracle(ctx, corpus, steal):
-    """k_map's pool of blocks (mrgpu.cpp map_steal) on inputs below its size
+    """k_map's pool of blocks (mrg_map.cpp map_steal) on inputs below its size
     floor (MRG_TEST_STEAL_MIN=0): half (steal = 2) or 1/16 of the blocks taken from the 8 part counters
     by workgroups done with their share -- C1 golden digests, the indexer golden, Unicode and long
     tokens, deferred (invalid) UTF-8 and a near-unique document through the wide map, against the

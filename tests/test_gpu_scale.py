@@ -147,7 +147,7 @@ def test_cold_context_zipf_takes_bucket_path_vs_oracle(ctx):
 
 
 def test_closed_context_blocks_reused_by_the_next(ctx):
-    """The process-wide device cache (mrgpu.cpp DeviceCache): a context closed after a 256 MiB Zipf job
+    """The process-wide device cache (mrg_host.h DeviceCache): a context closed after a 256 MiB Zipf job
     leaves its device blocks behind, and the next context's first job over the same input allocates
     fewer of them (hipMalloc calls counted by mrg_pool_alloc_stats) and writes the same bytes; every
     job's output against the oracle."""
@@ -297,7 +297,7 @@ def test_map_spill_and_rerun_vs_oracle(ctx, corpus, knobs, wide):
 
 def test_speculative_aggregation_paths_vs_oracle(ctx, corpus, knobs):
     """The bucket aggregation queued behind the map before the host has read the map's counters
-    (mrgpu.cpp job_map): on a context whose previous job took the bucket path it is launched, then
+    (mrg_map.cpp job_map): on a context whose previous job took the bucket path it is launched, then
     reused (spec_agg 1) or dropped (spec_agg 2) -- with MRG_WIDE unset, on the map-rerun path
     (tail regions of 1 record, 16-record overflow lists), the aggregation-regrow path (overflow list of
     1000 records, 4-bit hashes) and with sub-ranges; every output against the oracle."""

@@ -1,5 +1,5 @@
 """CPU tests of the batched map's host side (no GPU): the batch planner of MRG_FLAG_STREAM
-(mrgpu.cpp stream_plan, through mrg_test_stream_plan), the new entry points' behaviour without a
+(mrg_run.cpp stream_plan, through mrg_test_stream_plan), the new entry points' behaviour without a
 device, and the constants the three bindings share."""
 import ctypes as C
 import os

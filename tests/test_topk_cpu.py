@@ -1,4 +1,4 @@
-"""CPU tests of the top-k surface: the host merge of per-GPU top-k runs (mrgpu.cpp merge_top_lines,
+"""CPU tests of the top-k surface: the host merge of per-GPU top-k runs (mrg_run.cpp merge_top_lines,
 the multi-GPU half of top.txt) against a Python sort, and the MRG_FLAG_TOP flag / symbol plumbing.
 Expected values never come from the library."""
 import os
