@@ -144,9 +144,6 @@ __device__ __forceinline__ bool ba_add(BaKey *key, CT *cnt, unsigned int *doc, u
     return ba_add_from<IDX, C32>(key, cnt, doc, a, b, d, c, h, key[ba_slot<IDX, C32>(h)]);
 }
 
-#ifndef MRG_AGG_XCD
-#define MRG_AGG_XCD 1
-#endif
 static_assert(MRG_NBUCKET % 8 == 0, "buckets spread over the 8 XCDs");
 template <bool IDX, bool C32>
 __global__ __launch_bounds__(BA_WG, 1) void k_bucket_agg(BucketArgs A) {
@@ -169,15 +166,11 @@ __global__ __launch_bounds__(BA_WG, 1) void k_bucket_agg(BucketArgs A) {
     // table holds is summed by nsub workgroups, each reading all of its records and keeping its range)
     // With sub-ranges, the nsub workgroups of a bucket run side by side on ONE XCD (workgroups go to the
     // XCDs round-robin by blockIdx), so the second and third reads of the bucket's records come from
-    // that XCD's L2 instead of HBM (MRG_AGG_XCD; 0 = bucket-major, the r05 order)
+    // that XCD's L2 instead of HBM
     const uint32_t nsub = A.nsub;
-#if MRG_AGG_XCD
     const uint32_t g = blockIdx.x, slot = g / 8u;
     const uint32_t b = nsub > 1u ? (slot / nsub) * 8u + g % 8u : g % MRG_NBUCKET;
     const uint32_t jsub = nsub > 1u ? slot % nsub : g / MRG_NBUCKET;
-#else
-    const uint32_t b = blockIdx.x % MRG_NBUCKET, jsub = blockIdx.x / MRG_NBUCKET;
-#endif
     auto mine = [&](uint32_t h) { return nsub <= 1u || (((h & 0xFFu) * nsub) >> 8) == jsub; };
     constexpr uint32_t RW = IDX ? 3u : 2u;
     const uint32_t cap = gk(A.bcap)[b];
@@ -250,9 +243,8 @@ __global__ __launch_bounds__(BA_WG, 1) void k_bucket_agg(BucketArgs A) {
         if (IDX)
             for (int k = 0; k < BA_U; ++k) asm volatile("" : "+v"(X.d[k]));
     };
-    uint64_t abl_acc = 0;  // MRG_AGG_ABLATE (timing only): what the skipped work would have consumed
-    uint32_t qn = 0;       // records in this wave's miss queue (wave-uniform)
-    auto drain = [&]() {   // the queued records, one per lane, through the full probe
+    uint32_t qn = 0;      // records in this wave's miss queue (wave-uniform)
+    auto drain = [&]() {  // the queued records, one per lane, through the full probe
         if (!ba_queue<IDX, C32>() || qn == 0) return;
         const bool act = (uint32_t)lane < qn;
         const BaKey r = s_mq[ba_queue<IDX, C32>() ? wv : 0][act ? lane : 0];
@@ -268,16 +260,6 @@ __global__ __launch_bounds__(BA_WG, 1) void k_bucket_agg(BucketArgs A) {
     // record k is added, so the probe chains of neighbouring records overlap by one LDS round trip
     auto sum_chunk = [&](uint32_t r, uint32_t off, const Chunk &X) {
         const uint32_t n = s_rn[r];
-        if (A.ablate) {
-#pragma unroll
-            for (int k = 0; k < BA_U; ++k) {
-                const bool ok = off + 64u * k + (uint32_t)lane < n;
-                const uint64_t a = X.k[k].x, c = X.k[k].y;
-                const uint32_t d = IDX ? X.d[k] : MRG_EMPTY_DOC;
-                abl_acc += ok ? ((A.ablate & 2u) ? (a ^ c) : (uint64_t)ba_hash(a, c, d, A.hash_bits)) : 0u;
-            }
-            return;
-        }
         uint32_t hk[BA_U];
 #pragma unroll
         for (int k = 0; k < BA_U; ++k) hk[k] = ba_hash(X.k[k].x, X.k[k].y, IDX ? X.d[k] : MRG_EMPTY_DOC, A.hash_bits);
@@ -319,7 +301,7 @@ __global__ __launch_bounds__(BA_WG, 1) void k_bucket_agg(BucketArgs A) {
             if (__any(ovf)) overflow(ovf, a, c, d, 1);
         }
     };
-    if (!(A.ablate & 4u)) {
+    {
         Chunk XA, XB;
         uint32_t kA = (uint32_t)wv, rA = 0, oA = 0;
         if (kA < NC) {
@@ -345,7 +327,6 @@ __global__ __launch_bounds__(BA_WG, 1) void k_bucket_agg(BucketArgs A) {
     }
     drain();  // the rest of the miss queue
 
-    if (A.ablate && abl_acc == 0x9E3779B97F4A7C15ull) atomicAdd(&A.counters[CNT_OVF2], 1ull);
     // ---- 2. this bucket's slice of every map workgroup's flushed table (a few entries each): the
     // wave's regions (wv, wv + 16, ...) one per lane, their slices flattened over the lanes (an
     // exclusive scan of the slice sizes, each entry finds its region by binary search), four entries

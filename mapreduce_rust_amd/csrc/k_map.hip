@@ -247,28 +247,6 @@ __device__ __forceinline__ TileInfo sub_tile(const BlkInfo &b, uint32_t j) {
     return t;
 }
 
-// timing variants only: an ablation compiled in as a constant (the product build: 0)
-#ifndef MRG_MAP_ABL_CONST
-#define MRG_MAP_ABL_CONST 0u
-#endif
-#ifndef MRG_MAP_CMPT  // compacted codepoint decode for blocks with a lane of 2+ leads (A/B switch)
-#define MRG_MAP_CMPT 1
-#endif
-// per-wave dedup of a round's repeated keys (timing variant, MRG_MAP_DEDUP = leader rounds; 0 = off):
-// see emit_fastN
-#ifndef MRG_MAP_DEDUP
-#define MRG_MAP_DEDUP 0
-#endif
-
-__device__ __forceinline__ uint32_t map_ablate(const MapArgs &A) {
-#ifdef MRG_MAP_ABLATION
-    return A.ablate;
-#else
-    (void)A;
-    return MRG_MAP_ABL_CONST;
-#endif
-}
-
 __device__ __forceinline__ void report_error(unsigned long long *counters, uint64_t pos) {
     __hip_atomic_fetch_min(gp(&counters[CNT_ERRPOS]), (unsigned long long)pos, __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_AGENT);
@@ -309,14 +287,8 @@ struct alignas(16) KeyPair {
 // fills with whatever the first few thousand tokens hold, singletons included; with it, mostly with
 // repeated (frequent) keys.  Exactness is untouched: a token either adds to its key's slot or is
 // appended to the tail, and both are summed.
-#ifndef MRG_MAP_DOOR
-#define MRG_MAP_DOOR 1
-#endif
 #ifndef MRG_MAP_DOOR_WORDS
 #define MRG_MAP_DOOR_WORDS 2048  // 64 Kibit (128 Kibit measured the same; the block queue's LDS comes from here)
-#endif
-#ifndef MRG_MAP_DOOR_LEVELS
-#define MRG_MAP_DOOR_LEVELS 1
 #endif
 static_assert(MRG_MAP_DOOR_WORDS >= 32 && (MRG_MAP_DOOR_WORDS & (MRG_MAP_DOOR_WORDS - 1)) == 0,
               "doorkeeper bit index is masked with DW * 32 - 1");
@@ -330,25 +302,16 @@ struct LdsTable {
     unsigned int *door;
     unsigned int *fill;  // slots claimed so far (never decreases: a claimed slot keeps its key)
 
-    // seen before in this workgroup?  (records this sighting; collisions only admit early).  With
-    // two levels, entries are 2-bit: admitted from the third sighting on.
+    // seen before in this workgroup?  (records this sighting; collisions only admit early)
     __device__ __forceinline__ bool admitted(uint32_t h) {
-        if (!MRG_MAP_DOOR) return true;
-        if (MRG_MAP_DOOR_LEVELS == 1) {
-            // a two-position Bloom filter: hash bits 11.. and a multiplicative remix of the hash
-            // (fewer false "seen before" while the table fills: simulated on the C3 stream, hits
-            // 72.2 -> 72.9 %); both atomics in flight together, and only on the claim path
-            const uint32_t di = (h >> 11) & (DW * 32u - 1u);
-            const uint32_t dj = ((h * 0x9E3779B1u) >> 15) & (DW * 32u - 1u);
-            const uint32_t bi = 1u << (di & 31u), bj = 1u << (dj & 31u);
-            const uint32_t oi = atomicOr(&door[di >> 5], bi), oj = atomicOr(&door[dj >> 5], bj);
-            return (oi & bi) != 0u && (oj & bj) != 0u;
-        }
-        const uint32_t di = (h >> 11) & (DW * 16u - 1u);
-        const uint32_t lo = 1u << (2u * (di & 15u)), hi = lo << 1;
-        unsigned int *w = &door[di >> 4];
-        if (!(atomicOr(w, lo) & lo)) return false;
-        return (atomicOr(w, hi) & hi) != 0u;
+        // a two-position Bloom filter: hash bits 11.. and a multiplicative remix of the hash
+        // (fewer false "seen before" while the table fills: simulated on the C3 stream, hits
+        // 72.2 -> 72.9 %); both atomics in flight together, and only on the claim path
+        const uint32_t di = (h >> 11) & (DW * 32u - 1u);
+        const uint32_t dj = ((h * 0x9E3779B1u) >> 15) & (DW * 32u - 1u);
+        const uint32_t bi = 1u << (di & 31u), bj = 1u << (dj & 31u);
+        const uint32_t oi = atomicOr(&door[di >> 5], bi), oj = atomicOr(&door[dj >> 5], bj);
+        return (oi & bi) != 0u && (oj & bj) != 0u;
     }
 
     __device__ __forceinline__ bool matches(uint32_t s, uint64_t a, uint64_t b, uint32_t d) const {
@@ -358,7 +321,7 @@ struct LdsTable {
 
     // claim an empty way of set s0 (ways seen empty: e0, e1); true if the key got a slot and its count
     __device__ __forceinline__ bool claim(uint32_t s0, bool e0, bool e1, uint64_t a, uint64_t b, uint32_t d,
-                                          uint32_t h, uint32_t add = 1u) {
+                                          uint32_t h) {
         if (!admitted(h)) return false;
         for (uint32_t w = 0; w < 2; ++w) {
             if (!(w ? e1 : e0)) continue;
@@ -367,7 +330,7 @@ struct LdsTable {
             if (old == MRG_EMPTY_K0) {
                 key[s].b = b;
                 if (IDX) doc[s] = d;
-                atomicAdd(&cnt[s], add);
+                atomicAdd(&cnt[s], 1u);
                 atomicAdd(fill, 1u);
                 return true;
             }
@@ -377,14 +340,13 @@ struct LdsTable {
     }
 
     // one probe per lane (slow path: one token per lane)
-    __device__ __forceinline__ bool insert_wave(bool act, uint64_t a, uint64_t b, uint32_t d, uint32_t h,
-                                                uint32_t abl = 0) {
+    __device__ __forceinline__ bool insert_wave(bool act, uint64_t a, uint64_t b, uint32_t d, uint32_t h) {
         const uint32_t s0 = act ? (h & (NS - 1)) : 0u;
         const KeyPair k0 = key[s0], k1 = key[s0 + NS];
         const bool m0 = act & (((k0.a ^ a) | (k0.b ^ b)) == 0) & (!IDX || doc[s0] == d);
         const bool m1 = act & !m0 & (((k1.a ^ a) | (k1.b ^ b)) == 0) & (!IDX || doc[s0 + NS] == d);
         bool hit = m0 | m1;
-        if (hit && !(abl & 16u)) atomicAdd(&cnt[m0 ? s0 : s0 + NS], 1u);
+        if (hit) atomicAdd(&cnt[m0 ? s0 : s0 + NS], 1u);
         const bool e0 = k0.a == MRG_EMPTY_K0, e1 = k1.a == MRG_EMPTY_K0;
         const bool need = act && !hit && (e0 || e1);
         if (__any(need)) {
@@ -486,22 +448,13 @@ __device__ __forceinline__ void wide_store(const MapArgs &A, const TailRegions &
         return;
     }
     const uint32_t pos = atomicAdd(&R.wcur[b], 1u);
-    if ((MRG_MAP_ABL_CONST & 4096u) && pos != 0xFFFFFFFFu) return;   // timing variant only: no record store
     if (pos < A.wcap) {
         const uint64_t i = ((uint64_t)b * gridDim.x + blockIdx.x) * A.wcap + pos;
-#if MRG_MAP_ABL_CONST & 8192u   // timing variant: non-temporal record stores
-        if (A.w12)
-            __builtin_nontemporal_store(u32x3a{(uint32_t)k0, (uint32_t)(k0 >> 32), (uint32_t)(k1 >> 32)},
-                                        reinterpret_cast<GAS u32x3a *>(reinterpret_cast<GAS uint8_t *>(gp(A.wrec)) + 12u * i));
-        else
-            __builtin_nontemporal_store(u64x2{k0, k1}, reinterpret_cast<GAS u64x2 *>(gp(A.wrec) + 2u * i));
-#else
         if (A.w12)
             *reinterpret_cast<GAS u32x3a *>(reinterpret_cast<GAS uint8_t *>(gp(A.wrec)) + 12u * i) =
                 u32x3a{(uint32_t)k0, (uint32_t)(k0 >> 32), (uint32_t)(k1 >> 32)};
         else
             *reinterpret_cast<GAS u64x2 *>(gp(A.wrec) + 2u * i) = u64x2{k0, k1};
-#endif
     }
 }
 
@@ -577,7 +530,7 @@ __device__ __forceinline__ void tail16_append(const MapArgs &A, const TailRegion
 // tail-cursor adds of all N are issued back to back, so every LDS round trip is paid once for N
 // independent chains.  Same semantics as emit() applied to token 0, then 1, ...
 template <int N, int CAP, bool IDX, bool T64>
-__device__ __forceinline__ void emit_fastN(const MapArgs &A, uint32_t abl, uint32_t hbits, LdsTable<CAP, IDX> &T,
+__device__ __forceinline__ void emit_fastN(const MapArgs &A, uint32_t hbits, LdsTable<CAP, IDX> &T,
                                            TailRegions R, GAS uint64_t *pool, GAS uint64_t *pool16,
                                            const uint64_t (&hasm)[N], const uint64_t (&k0)[N], const uint64_t (&k1)[N],
                                            const uint32_t (&klen)[N], uint32_t docid, bool may_claim) {
@@ -593,73 +546,8 @@ __device__ __forceinline__ void emit_fastN(const MapArgs &A, uint32_t abl, uint3
 #pragma unroll
     for (int t = 0; t < N; ++t) {
         h[t] = key_hash(k0[t], k1[t], dkey, hbits);
-        actm[t] = (abl & 2u) ? 0ull : hasm[t];
+        actm[t] = hasm[t];  // the probing lanes, by value (through the reference the round gets other registers)
     }
-#if MRG_MAP_DEDUP
-    bool act[N], hit[N];
-#pragma unroll
-    for (int t = 0; t < N; ++t) act[t] = lane_of(actm[t]);
-    // Per-wave dedup (timing variant): MRG_MAP_DEDUP leader rounds over the round's N x 64 tokens.  A
-    // leader is the first token still pending; every token with the leader's key joins its group,
-    // skips the probe and the count add, and the leader adds the group's size.  When the leader
-    // misses the table, the members go to the tail with it (one record each, as without dedup).
-    uint32_t gadd[N], grp[N];
-    bool pend[N];
-#pragma unroll
-    for (int t = 0; t < N; ++t) {
-        gadd[t] = 1u;
-        grp[t] = 0xFFu;
-        pend[t] = act[t] && !IDX;
-    }
-    uint32_t gl_lane[MRG_MAP_DEDUP], gl_tok[MRG_MAP_DEDUP];
-#pragma unroll
-    for (int g = 0; g < MRG_MAP_DEDUP; ++g) {
-        gl_tok[g] = 0xFFu;
-        gl_lane[g] = 0;
-        uint64_t pm[N];
-#pragma unroll
-        for (int t = 0; t < N; ++t) pm[t] = __ballot(pend[t]);
-        int tl0 = -1;
-#pragma unroll
-        for (int t = N - 1; t >= 0; --t)
-            if (pm[t]) tl0 = t;
-        if (tl0 < 0) break;
-        uint64_t la = 0, lb = 0;
-        uint32_t src = 0;
-#pragma unroll
-        for (int t = 0; t < N; ++t)
-            if (t == tl0) {
-                src = (uint32_t)__builtin_ctzll(pm[t]);
-                la = __builtin_amdgcn_readlane(k0[t] & 0xFFFFFFFFull, src) |
-                     ((uint64_t)__builtin_amdgcn_readlane(k0[t] >> 32, src) << 32);
-                lb = __builtin_amdgcn_readlane(k1[t] & 0xFFFFFFFFull, src) |
-                     ((uint64_t)__builtin_amdgcn_readlane(k1[t] >> 32, src) << 32);
-            }
-        uint32_t gs = 0;
-        bool eq[N];
-#pragma unroll
-        for (int t = 0; t < N; ++t) {
-            eq[t] = pend[t] && k0[t] == la && k1[t] == lb;
-            gs += (uint32_t)__popcll(__ballot(eq[t]));
-        }
-        const uint32_t me = __lane_id();
-#pragma unroll
-        for (int t = 0; t < N; ++t) {
-            if (!eq[t]) continue;
-            pend[t] = false;
-            if (t == tl0 && me == src) {
-                gadd[t] = gs;
-            } else {
-                grp[t] = (uint32_t)g;
-                act[t] = false;   // a member: no probe, no count
-            }
-        }
-        gl_tok[g] = (uint32_t)tl0;
-        gl_lane[g] = src;
-    }
-#pragma unroll
-    for (int t = 0; t < N; ++t) actm[t] = wave_mask(act[t]);
-#endif
 #pragma unroll
     for (int t = 0; t < N; ++t) {
         s[t] = lane_of(actm[t]) ? (h[t] & (NS - 1)) : 0u;
@@ -687,15 +575,9 @@ __device__ __forceinline__ void emit_fastN(const MapArgs &A, uint32_t abl, uint3
         }
         hitm[t] = m0m[t] | m1m;
     }
-    if (!(abl & 16u)) {
 #pragma unroll
-        for (int t = 0; t < N; ++t)
-#if MRG_MAP_DEDUP
-            if (lane_of(hitm[t])) atomicAdd(&T.cnt[lane_of(m0m[t]) ? s[t] : s[t] + NS], gadd[t]);
-#else
-            if (lane_of(hitm[t])) atomicAdd(&T.cnt[lane_of(m0m[t]) ? s[t] : s[t] + NS], 1u);
-#endif
-    }
+    for (int t = 0; t < N; ++t)
+        if (lane_of(hitm[t])) atomicAdd(&T.cnt[lane_of(m0m[t]) ? s[t] : s[t] + NS], 1u);
     // empty ways exist only until the table has filled (wave-uniform: a stale count only means
     // an unneeded test); with the table full there is no claim side, and the probe's mask goes on as
     // it is
@@ -713,36 +595,14 @@ __device__ __forceinline__ void emit_fastN(const MapArgs &A, uint32_t abl, uint3
 #pragma unroll
             for (int t = 0; t < N; ++t) {
                 bool got = false;
-#if MRG_MAP_DEDUP
-                if (lane_of(needm[t])) got = T.claim(s[t], e0[t], e1[t], k0[t], k1[t], dkey, h[t], gadd[t]);
-#else
                 if (lane_of(needm[t])) got = T.claim(s[t], e0[t], e1[t], k0[t], k1[t], dkey, h[t]);
-#endif
                 hitm[t] |= wave_mask(got);
             }
         }
     }
-#if MRG_MAP_DEDUP
-#pragma unroll
-    for (int t = 0; t < N; ++t) hit[t] = lane_of(hitm[t]);
-    // members take their leader's outcome (a leader that missed: every member to the tail)
-#pragma unroll
-    for (int g = 0; g < MRG_MAP_DEDUP; ++g) {
-        if (gl_tok[g] == 0xFFu) break;
-        uint32_t lh = 0;
-#pragma unroll
-        for (int t = 0; t < N; ++t)
-            if ((uint32_t)t == gl_tok[g]) lh = __builtin_amdgcn_readlane(hit[t] ? 1u : 0u, gl_lane[g]);
-#pragma unroll
-        for (int t = 0; t < N; ++t)
-            if (grp[t] == (uint32_t)g) hit[t] = lh != 0u;
-    }
-#pragma unroll
-    for (int t = 0; t < N; ++t) hitm[t] = wave_mask(hit[t]);
-#endif
     uint64_t tlm[N];
 #pragma unroll
-    for (int t = 0; t < N; ++t) tlm[t] = (abl & 1u) ? 0ull : hasm[t] & ~hitm[t];
+    for (int t = 0; t < N; ++t) tlm[t] = hasm[t] & ~hitm[t];
     if constexpr (!T64) {
         // packed cursors: the round appends to the 12-byte class only (the indexer's one class); a key
         // of 13..16 bytes goes through the cold block below.  Every token's append in one LDS round
@@ -829,11 +689,8 @@ __device__ __forceinline__ void emit(const MapArgs &A, LdsTable<CAP, IDX> &table
     if (have && !is_long) {
         h = key_hash(tk0, tk1, dkey, T64 ? A.hash_bits : 0u);
     }
-    {
-        const bool act = have && !is_long && !(map_ablate(A) & 2u);
-        tail = (have && !is_long) && !table.insert_wave(act, tk0, tk1, dkey, h);
-    }
-    if (tail && !(map_ablate(A) & 1u)) {
+    tail = (have && !is_long) && !table.insert_wave(have && !is_long, tk0, tk1, dkey, h);
+    if (tail) {
         const uint32_t b = bucket_of(h);
         const bool w16 = !IDX && (T64 ? (uint32_t)tk1 != 0u : key_over12(tk1));
         if constexpr (!T64) {  // packed cursors: index and end in one word (see TailRegions)
@@ -1030,10 +887,10 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
     __shared__ uint32_t s_tot[3];                        // workgroup totals: tokens, tail records, 16-byte ones
     __shared__ unsigned int s_fill;                      // table slots claimed
     __shared__ unsigned int s_lcnt;                      // long-token records (region cursor)
-    __shared__ unsigned int s_door[(MRG_MAP_DOOR && !WIDE) ? LdsTable<CAP, IDX>::DW : 1];  // admission bitmap
+    __shared__ unsigned int s_door[WIDE ? 1 : LdsTable<CAP, IDX>::DW];  // admission bitmap
     static_assert(WIDE || sizeof(s_q) >= CAP * sizeof(uint16_t), "flush ranks reuse the queues");
     static_assert((CAP & (CAP - 1)) == 0 && CAP >= 64 && CAP <= 65536, "2-way sets: NS = CAP / 2 a power of two, ranks in u16");
-    static_assert(sizeof(s_door) / sizeof(s_door[0]) >= ((MRG_MAP_DOOR && !WIDE) ? LdsTable<CAP, IDX>::DW : 1u), "doorkeeper words");
+    static_assert(sizeof(s_door) / sizeof(s_door[0]) >= (WIDE ? 1u : LdsTable<CAP, IDX>::DW), "doorkeeper words");
     static_assert(!WIDE || (sizeof(s_wcur) / sizeof(s_wcur[0]) == MRG_WMAP_MAXB1 && sizeof(s_wspl) / sizeof(s_wspl[0]) == 2 * MRG_WMAP_MAXB1 &&
                             sizeof(s_wix) == MRG_WMAP_IXR * MRG_WIDE_IX1 && MRG_WIDE_IX1 % 4 == 0),
                   "wide map: cursors, splitters and index rows as the host plan sizes them");
@@ -1062,7 +919,7 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
         s_cnt[i] = 0;
         if (IDX) s_doc[i] = MRG_EMPTY_DOC;
     }
-    if (MRG_MAP_DOOR && !WIDE)
+    if (!WIDE)
         for (int i = tid; i < (int)LdsTable<CAP, IDX>::DW; i += WG) s_door[i] = 0;
     for (int b = tid; b < (WIDE ? 0 : MRG_NBUCKET); b += WG) {
         const uint32_t cap = gp(A.bcap)[b];
@@ -1126,13 +983,6 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
     const TailRegions tails{s_tcur, s_tend, s_tcur16, s_tend16, &s_lcnt, s_wcur, s_wspl, A.wix ? s_wix : nullptr};
     uint32_t my_tokens = 0;
     // uniform job parameters used in the hot loop, read once
-    // ablation knobs (MRG_ABLATE, timing only) exist in -DMRG_MAP_ABLATION builds; in the product
-    // build abl is the constant 0, so no branch, mask or SGPR of the hot loop is spent on them
-#ifdef MRG_MAP_ABLATION
-    const uint32_t abl = A.ablate;
-#else
-    constexpr uint32_t abl = MRG_MAP_ABL_CONST;
-#endif
     // the forced-collision hash mask (a test knob) exists in the general variant only (T64: the host launches
     // it whenever hash_bits is set); the packed variant hashes in full, with no mask in the token round
     const uint32_t hbits = T64 ? A.hash_bits : 0u;
@@ -1170,15 +1020,7 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
         uint64_t Ab;
         uint32_t v0, v1;
     };
-#ifdef MRG_MAP_ABLATION
-    BlkLoad first_blk{};  // ablate & 8 (timing only): every block re-reads the wave's first block
-#endif
-    auto load_blk = [&](const BlkLoad &b0, Blk &X) {
-#ifdef MRG_MAP_ABLATION
-        const BlkLoad &b = (abl & 8u) ? first_blk : b0;  // a real block: its own base and bounds
-#else
-        const BlkLoad &b = b0;
-#endif
+    auto load_blk = [&](const BlkLoad &b, Blk &X) {
         const GAS uint8_t *src = gp(A.in) + (b.Ab - (uint64_t)BEHIND);
         auto ld = [&](uint32_t idx) -> uint4 {
             const u32x4 t = __builtin_nontemporal_load(reinterpret_cast<const GAS u32x4 *>(src + 16u * min(max(idx, b.v0), b.v1 - 1u)));
@@ -1450,17 +1292,13 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
         // carries its class, so the W / S masks mean the same.  Invalid UTF-8 defers the block's tiles
         // to generic_tile after the main loop (which reports the first bad byte).
         bool defer_blk = false;
-        if (!(abl & 256u) && !(MRG_MAP_ABL_CONST & 0x20000u) &&
-            (wave_mask(n0) | wave_mask(n1) | (wave_mask(ln <= 1u) & wave_mask(ne))) != 0ull) {
-#ifdef MRG_MAP_NO_UNI
-            defer_blk = true;  // A/B builds only: every such block to the exact walker, as in r03
-#else
+        if ((wave_mask(n0) | wave_mask(n1) | (wave_mask(ln <= 1u) & wave_mask(ne))) != 0ull) {
             // UTF-8-exact classes in registers (r05): every lane decodes the codepoints whose leads lie
             // in its own segments, straight from the segment's four dwords and the next segment's first
             // (DPP) -- no LDS window.  One loop over the lane's leads, both segments per trip (the trip
             // count is the busiest lane's lead count: about 1.6 per block on English text, whose
             // non-ASCII codepoints are sparse), unless a lane holds two or more: then the compacted
-            // decode below takes one trip (MRG_MAP_CMPT).  A lead's bytes are checked by the
+            // decode below takes one trip.  A lead's bytes are checked by the
             // decode (continuation bytes, overlongs, surrogates, range); a codepoint's last bytes may lie in
             // the next segment (spilled by DPP).  Every non-ASCII byte must be covered by a decoded
             // codepoint, else the block holds invalid UTF-8 and is deferred.  (r04 compacted the leads
@@ -1533,8 +1371,7 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
                 S |= cl == MRG_CLS_S ? span : 0u;
             };
             uint32_t W0 = 0, S0 = 0, C0 = 0, W1 = 0, S1 = 0, C1 = 0;
-            uint32_t mAB0 = (MRG_MAP_ABL_CONST & 0x10000u) ? 0u : (ld0 | (ld1 << 16));
-#if MRG_MAP_CMPT
+            uint32_t mAB0 = ld0 | (ld1 << 16);
             // a lane with two or more leads (about 6 blocks in 10 of English text: one codepoint per
             // ~190 bytes, 32 bytes per lane) would cost the whole wave a second decode trip.  Instead
             // the block's leads are compacted, one per lane (a wave prefix sum of the lead counts):
@@ -1597,7 +1434,6 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
                     }
                 }
             }
-#endif
             // one codepoint per lane and trip, the lane's two segments' leads in one mask (non-ASCII
             // text is sparse: most lanes have none, a few one)
             for (uint32_t mAB = mAB0; __any(mAB != 0u);) {
@@ -1657,7 +1493,7 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
                 W = (W | ((in >> 4) & 0xFu)) & 0xFFFFu;
                 S = (S | ((in >> 8) & 0xFu)) & 0xFFFFu;
                 C = (C | (in & 0xFu)) & 0xFFFFu;
-                if (!(MRG_MAP_ABL_CONST & 0x10000u)) bad |= C != nam;   // (0x10000: timing only, no decode)
+                bad |= C != nam;
                 return ((m & 0xFFFFu & ~nam) | W) | ((((m >> 16) & ~nam) | S) << 16);
             };
             m0 = fix(m0, nam0, W0, S0, C0, in0);
@@ -1668,7 +1504,6 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
             prev_blk = lane_u32(pb_l, 0);
             defer_blk = __any(bad);
             if (!defer_blk && lane == 0) atomicAdd(&s_nuni, Ab + (uint64_t)TILE < doc_hi ? 2u : 1u);
-#endif
         }
         MRG_PT(1);
         // the next block's registers are waited for HERE, before this block's tail stores are
@@ -1688,10 +1523,6 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
             }
             return;
         }
-        if (abl & 32u) {  // timing only: classification alone
-            my_tokens += (m0 ^ m1 ^ mh ^ prev_blk) & 1u;
-            return;
-        }
 
         // tokens of the wave's queue (entries 0 .. total - 1), TWO per lane per round (entries q and
         // q + 64: two independent LDS dependency chains in one instruction stream, so each wait covers
@@ -1708,7 +1539,7 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
                 const uint32_t ra = queue[min(qa, (uint32_t)QROW - 1u)], rb = queue[min(qb, (uint32_t)QROW - 1u)];
                 uint32_t ga = extract(qa, ra, total, fa, ma, sA, a0, a1, la);
                 uint32_t gb = extract(qb, rb, total, fb, mb, sB, b0, b1, lb);
-                if (!(abl & 1024u) && __any((ga | gb) != 0u)) {
+                if (__any((ga | gb) != 0u)) {
                     la -= (uint32_t)__builtin_popcount(ga);  // the key loses the bytes squeezed out
                     lb -= (uint32_t)__builtin_popcount(gb);
                     squeeze(ga, a0, a1);
@@ -1733,7 +1564,7 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
                     wide_store(A, tails, lane_of(fa), a0, a1);
                     wide_store(A, tails, lane_of(fb), b0, b1);
                 } else {
-                    emit_fastN<2, CAP, IDX, T64>(A, abl, hbits, table, tails, pool, pool16, hv, kk0, kk1, kl, docid, may_claim);
+                    emit_fastN<2, CAP, IDX, T64>(A, hbits, table, tails, pool, pool16, hv, kk0, kk1, kl, docid, may_claim);
                 }
             }
             return nslow;
@@ -1742,7 +1573,7 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
         // the nseg segments' masks, or (a token running past the first halo segment) the exact
         // per-codepoint walker (forward reads only: the staged bytes are [At, whi))
         auto slow_tokens = [&](uint32_t nslow, uint64_t At, uint64_t whi, uint32_t nseg) {
-            if (!nslow || (abl & 512u)) return;
+            if (!nslow) return;
             const uint64_t wbase = At - (uint64_t)BEHIND;
             wave_sync_lds();
             auto rd = [&](uint64_t a) -> uint32_t {
@@ -1757,7 +1588,7 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
                 if (q < nslow) {
                     const uint32_t s = queue[q];
                     a = At + s;
-                    if (!(abl & 128u) && mask_walk(s, nseg, tk0, tk1, tlen, traw)) {
+                    if (mask_walk(s, nseg, tk0, tk1, tlen, traw)) {
                         have = tlen > 0;
                     } else {
                         uint64_t e2;
@@ -1802,12 +1633,6 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
             const uint32_t S0 = m0 >> 16, S1 = m1 >> 16;
             uint32_t st0 = ~S0 & ((S0 << 1) | pv0) & 0xFFFFu;
             uint32_t st1 = ~S1 & ((S1 << 1) | pv1) & 0xFFFFu;
-            if (abl & 64u) {  // timing only: no queue writes, no tokens
-                my_tokens += (st0 ^ st1) & 1u;
-                st0 = 0;
-                st1 = 0;
-            }
-            my_tokens += (abl & 4u) ? (uint32_t)__builtin_popcount(st0 | (st1 << 16)) : 0u;
             // every start gets a queue slot by ONE wave prefix sum over both counts (16 bits each: at
             // most 512 starts per tile); tile 0's starts first
             uint32_t pos0, pos1;
@@ -1817,7 +1642,7 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
                 const uint32_t tot = lane_u32(incl, 63);
                 pos0 = (incl & 0xFFFFu) - c0;
                 pos1 = (tot & 0xFFFFu) + (incl >> 16) - c1;
-                return (abl & 68u) ? 0u : (tot & 0xFFFFu) + (tot >> 16);
+                return (tot & 0xFFFFu) + (tot >> 16);
             };
             // the starts of segments [lo, hi) of the block
             auto in_range = [&](uint32_t lo, uint32_t hi, uint32_t &a0, uint32_t &a1) {
@@ -1888,19 +1713,14 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
             const uint32_t cnt = __builtin_popcount(st);
             const uint32_t incl = wave_incl_scan(cnt);
             uint32_t pos = incl - cnt;
-            if (abl & 64u) {  // timing only: no queue writes, no tokens
-                my_tokens += st & 1u;
-                st = 0;
-            }
             while (st) {
                 const uint32_t kb = (uint32_t)__builtin_ctz(st);
                 st &= st - 1u;
                 queue[pos++] = (uint16_t)(l16 + kb);
             }
-            const uint32_t total = (abl & 68u) ? 0u : lane_u32(incl, 63);
+            const uint32_t total = lane_u32(incl, 63);
             MRG_PT(2);
             const bool may_claim = table_open();
-            my_tokens += (abl & 4u) ? cnt : 0u;
             wave_sync_lds();
             const uint32_t nslow = rounds(total, may_claim);
             MRG_PT(3);
@@ -2031,9 +1851,6 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
         const BlkInfo b = locate_blk(A, c, dcur);
         I = cur_of(b);
         const BlkLoad L{b.Ab, b.v0, b.v1};
-#ifdef MRG_MAP_ABLATION
-        first_blk = L;
-#endif
         load_blk(L, XA);
         settle(XA);
     }

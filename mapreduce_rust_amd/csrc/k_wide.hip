@@ -1528,12 +1528,6 @@ constexpr uint32_t W_VIPL = W_VC / 64;
 #endif
 constexpr uint32_t W_VND = MRG_WIDE_VND;   // digits
 static_assert(W_VND % 64 == 0 && W_VND <= 0x10000u, "digit counts: whole wave rows; starts fit the LDS words");
-#ifndef MRG_WIDE_L2U
-#define MRG_WIDE_L2U 4
-#endif
-#ifndef MRG_WIDE_ABL
-#define MRG_WIDE_ABL 0
-#endif
 #ifndef MRG_WIDE_VRG
 #define MRG_WIDE_VRG 2
 #endif
@@ -1821,9 +1815,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MRG_WIDE_VWP
             uint32_t gmax = 0;
 #pragma unroll
             for (uint32_t k = g0; k < g0 + W_VRG && k < W_VIPL; ++k) gmax = max(gmax, bn[k]);
-#if MRG_WIDE_ABL & 1   // timing only: no rank loop
-            gmax = 0;
-#endif
             for (uint32_t q = 0; __any(q < gmax); ++q) {
                 v2 x[W_VRG];
 #pragma unroll
@@ -1921,23 +1912,6 @@ __global__ void k_wdrop(const uint32_t *nleaf, uint32_t B1r, uint32_t R, const u
 }
 
 // ---------------------------------------------------------------- lines
-// One workgroup per L1 bucket streams the bucket's distinct keys (all its leaves, the dropped last
-// key of a partition excluded) in chunks of W_WCH, one key per thread: key i of the bucket -> its
-// leaf by a search of the leaves' running key counts (LDS), the line built in registers as
-// little-endian words, OR-ed into a zeroed LDS stage at its offset from a block scan of the line
-// lengths (whole dwords: the first and last are shared with the neighbour lines), then the stage
-// is stored as aligned dwords (byte stores only at the two ends of a chunk) and zeroed on the way.
-// 512-thread workgroups, several per CU: while one formats, the others load and store.
-#ifndef MRG_WIDE_WWAVE
-#define MRG_WIDE_WWAVE 1   // 1: one wave per leaf (k_wwritew, r06: C5 format -23 %), 0: one workgroup per L1 bucket (k_wwrite)
-#endif
-#ifndef MRG_WIDE_WST
-#define MRG_WIDE_WST 1   // r06: the stage stored as 16-byte vectors (was dwords)
-#endif
-constexpr uint32_t W_WWG = 512;
-constexpr uint32_t W_WCH = W_WWG;             // keys per chunk
-constexpr uint32_t W_STAGE = 40 * W_WCH;      // >= W_WCH lines of <= 16 + 1 + 20 + 1 bytes (+ 3 of shift)
-
 __device__ __forceinline__ uint64_t bswap64(uint64_t x) { return __builtin_bswap64(x); }
 
 // "key count\n" of a short key as little-endian bytes in w[0..4]; returns its length
@@ -1985,127 +1959,13 @@ __device__ __forceinline__ uint32_t line_words(uint64_t k0, uint64_t k1, uint64_
     return L + 2u + nd;
 }
 
-__global__ __launch_bounds__(W_WWG) void k_wwrite(const uint64_t *keys, const uint64_t *ocnt, const uint32_t *leaf_pk,
-                                                    const uint32_t *nleaf, const uint64_t *leaf_out,
-                                                    const uint32_t *leaf_nd, const uint32_t *leaf_drop,
-                                                    const uint64_t *leaf_off, uint8_t *out) {
-    __shared__ __attribute__((aligned(16))) uint32_t s_buf[W_STAGE / 4];
-    static_assert(W_STAGE >= 15 + 38 * W_WCH + 4 * 11, "a chunk's lines (<= 38 bytes each) at a 0..15-byte stage shift");
-    __shared__ uint32_t s_kst[MRG_WIDE_MAXB2 + 1];   // keys before leaf l (this bucket)
-    __shared__ uint64_t s_lout[MRG_WIDE_MAXB2];      // first key slot of leaf l; bit 63: counts packed
-    __shared__ uint32_t s_ws[W_WWG / 64];
-    const uint8_t *sb = reinterpret_cast<const uint8_t *>(s_buf);
-    const uint32_t tid = threadIdx.x, b = blockIdx.x;
-    const uint32_t nl = nleaf[b];
-    const uint64_t l0 = (uint64_t)b * MRG_WIDE_MAXB2;
-    for (uint32_t i = tid; i < W_STAGE / 4; i += W_WWG) s_buf[i] = 0;
-    {  // running key counts of the leaves (MAXB2 / W_WWG per thread)
-        constexpr uint32_t PT = MRG_WIDE_MAXB2 / W_WWG;
-        uint32_t v[PT], sum = 0;
-        for (uint32_t x = 0; x < PT; ++x) {
-            const uint32_t l = tid * PT + x;
-            v[x] = l < nl ? leaf_nd[l0 + l] - (leaf_drop[l0 + l] ? 1u : 0u) : 0u;
-            if (l < nl) s_lout[l] = leaf_out[l0 + l] | ((uint64_t)(leaf_pk[l0 + l] != 0u) << 63);
-            sum += v[x];
-        }
-        uint32_t tot;
-        uint32_t run = block_scan_excl<W_WWG / 64>(sum, s_ws, &tot);
-        for (uint32_t x = 0; x < PT; ++x) {
-            s_kst[tid * PT + x] = run;
-            run += v[x];
-        }
-        if (tid == 0) s_kst[MRG_WIDE_MAXB2] = tot;
-    }
-    lds_barrier();
-    const uint32_t K = s_kst[MRG_WIDE_MAXB2];
-    uint64_t dst = leaf_off[l0];
-    // this thread's key of chunk c0: leaf by a search of the running counts, then the key and count
-    // loads.  The next chunk's are fetched before this chunk is laid out and stored, so their leaf
-    // search and load latency overlap the current chunk's work.
-    struct One {
-        uint64_t a, c, n;
-    };
-    // leaf l of key i: s_kst[l] <= i < s_kst[l + 1] (the last such l).  A thread's keys only move
-    // forward (by W_WCH per chunk), so its leaf is found by a forward walk from its previous one:
-    // about two LDS reads per chunk for leaves of ~250 keys (a binary search over the bucket's up to
-    // 1024 leaves was ten dependent reads per key)
-    uint32_t lcur = 0;
-    auto fetch = [&](uint32_t c0, One &F) {
-        const uint32_t i = c0 + tid;
-        F.a = F.c = F.n = 0;
-        if (i < K) {
-            uint32_t lo = lcur;
-            while (lo + 1u < nl && s_kst[lo + 1u] <= i) ++lo;
-            lcur = lo;
-            const uint64_t lo_out = s_lout[lo];
-            const uint64_t slot = (lo_out & ~(1ull << 63)) + (i - s_kst[lo]);
-            F.a = keys[2 * slot];
-            F.c = keys[2 * slot + 1];
-            if (lo_out >> 63) {   // packed leaf: the count is the low word of k1
-                F.n = F.c & 0xFFFFFFFFull;
-                F.c &= ~0xFFFFFFFFull;
-            } else {
-                F.n = ocnt[slot];
-            }
-        }
-    };
-    One cur, nxt;
-    if (K) fetch(0, cur);
-    for (uint32_t c0 = 0; c0 < K; c0 += W_WCH) {
-        if (c0 + W_WCH < K) fetch(c0 + W_WCH, nxt);
-        uint64_t w[5];
-        const uint32_t ll = c0 + tid < K ? line_words(cur.a, cur.c, cur.n, w) : 0u;
-        uint32_t tot;
-        const uint32_t at = block_scan_excl<W_WWG / 64>(ll, s_ws, &tot);
-        // stage at the output's offset in its 16-byte (MRG_WIDE_WST; else 4-byte) unit: output vectors align in LDS
-        const uint32_t sh = (uint32_t)(dst & (MRG_WIDE_WST ? 15u : 3u));
-        if (ll) {
-            const uint32_t o = sh + at, base = o >> 2, bs = 8u * (o & 3u);
-            const uint32_t ndw = ((o & 3u) + ll + 3u) >> 2;
-            uint32_t prev = 0;
-#pragma unroll
-            for (uint32_t j = 0; j < 10; ++j) {
-                const uint32_t d = (uint32_t)(w[j >> 1] >> (32u * (j & 1u)));
-                const uint32_t e = (d << bs) | (bs ? prev >> (32u - bs) : 0u);
-                prev = d;
-                if (j < ndw) atomicOr(&s_buf[base + j], e);
-            }
-            if (10u < ndw) atomicOr(&s_buf[base + 10u], prev >> (32u - bs));
-        }
-        lds_barrier();
-        const uint64_t end = dst + tot;
-#if MRG_WIDE_WST
-        // whole 16-byte vectors (one dwordx4 store per lane: a 1 KiB wave store), bytes at the two ends
-        const uint64_t a16 = (dst + 15u) & ~15ull, e16 = end & ~15ull;
-        for (uint64_t x = dst + tid; x < min(a16, end); x += W_WWG) out[x] = sb[sh + (x - dst)];
-        for (uint64_t x = max(e16, a16) + tid; x < end; x += W_WWG) out[x] = sb[sh + (x - dst)];
-        for (uint64_t v = a16 / 16 + tid; v < e16 / 16; v += W_WWG) {
-            const uint32_t i = (sh + (uint32_t)(v * 16 - dst)) / 16;
-            reinterpret_cast<uint4 *>(out)[v] = reinterpret_cast<const uint4 *>(s_buf)[i];
-        }
-#else
-        const uint64_t a4 = (dst + 3u) & ~3ull, e4 = end & ~3ull;
-        for (uint64_t x = dst + tid; x < min(a4, end); x += W_WWG) out[x] = sb[sh + (x - dst)];
-        for (uint64_t x = max(e4, a4) + tid; x < end; x += W_WWG) out[x] = sb[sh + (x - dst)];
-        for (uint64_t w4 = a4 / 4 + tid; w4 < e4 / 4; w4 += W_WWG) {
-            const uint32_t i = (sh + (uint32_t)(w4 * 4 - dst)) / 4;
-            reinterpret_cast<uint32_t *>(out)[w4] = s_buf[i];
-        }
-#endif
-        lds_barrier();
-        // zero what this chunk used (its byte-stored ends included) for the next chunk's ORs
-        for (uint32_t i = tid; i < (sh + tot + 3u) / 4u; i += W_WWG) s_buf[i] = 0;
-        dst = end;
-        lds_barrier();
-        cur = nxt;
-    }
-}
-
-// r06: the same lines, one WAVE per leaf and no workgroup barrier.  A leaf's text starts at
-// leaf_off[leaf] (the scan of the leaves' line bytes after the drop), so waves write their leaves
-// independently: 64 keys per step, line lengths by a wave scan, the lines OR-ed into the wave's own LDS
-// stage, whole 16-byte vectors stored, the partial last vector carried to the next step at the
-// stage's start; bytes only at the leaf's two ends (the vectors it shares with its neighbours).
+// The distinct keys of every leaf (the dropped last key of a partition excluded) as "key count\n"
+// lines, one WAVE per leaf and no workgroup barrier.  A leaf's text starts at leaf_off[leaf] (the scan
+// of the leaves' line bytes after the drop), so waves write their leaves independently: 64 keys per
+// step, each line built in registers as little-endian words, line lengths by a wave scan, the lines
+// OR-ed into the wave's own zeroed LDS stage (whole dwords: the first and last are shared with the
+// neighbour lines), whole 16-byte vectors stored, the partial last vector carried to the next step at
+// the stage's start; bytes only at the leaf's two ends (the vectors it shares with its neighbours).
 constexpr uint32_t WW_WG = 256, WW_NW = WW_WG / 64;
 constexpr uint32_t WW_PER = 16;                          // workgroups per L1 bucket (64 waves stride its leaves)
 constexpr uint32_t WW_STGW = (16 + 64 * 38 + 64) / 4;   // stage dwords per wave: carried vector + 64 lines + slack
@@ -2137,9 +1997,9 @@ __global__ __launch_bounds__(WW_WG) void k_wwritew(const uint64_t *keys, const u
         uint64_t dst = lstart;                 // next output byte; the stage holds [dst - sh, ...)
         uint32_t sh = (uint32_t)(dst & 15u);
         for (uint32_t c0 = 0; c0 < K; c0 += 64u) {
-            // every lane formats a line (inactive lanes the leaf's first key, then ll = 0): an earlier
-            // version with the load and format inside `if (i < K)` wrote a stray 0x83 into 1 % of the
-            // lines (the compiled divergent block; found by byte comparison with k_wwrite, tools/dbg_ww.py)
+            // every lane formats a line (inactive lanes the leaf's first key, then ll = 0): with the
+            // load and format inside `if (i < K)`, the compiled divergent block wrote a stray 0x83 into
+            // 1 % of the lines (found by a byte-for-byte comparison of the output)
             const uint32_t i = c0 + lane;
             const bool act = i < K;
             const uint64_t slot = o0 + (act ? i : 0u);
@@ -2463,13 +2323,8 @@ void mrg_wide_launch_drop(const uint32_t *nleaf, uint32_t B1r, uint32_t R, const
 void mrg_wide_launch_write(const uint64_t *keys, const uint64_t *ocnt, const uint32_t *leaf_pk, const uint32_t *nleaf,
                            const uint64_t *leaf_out, const uint32_t *leaf_nd, const uint32_t *leaf_drop,
                            const uint64_t *leaf_off, uint32_t B1, uint8_t *out, hipStream_t s) {
-#if MRG_WIDE_WWAVE
     hipLaunchKernelGGL(k_wwritew, dim3(B1 * WW_PER), dim3(WW_WG), 0, s, keys, ocnt, leaf_pk, nleaf, leaf_out, leaf_nd,
                        leaf_drop, leaf_off, out);
-#else
-    hipLaunchKernelGGL(k_wwrite, dim3(B1), dim3(W_WWG), 0, s, keys, ocnt, leaf_pk, nleaf, leaf_out, leaf_nd, leaf_drop,
-                       leaf_off, out);
-#endif
 }
 void mrg_wide_launch_part_off(const uint64_t *leaf_off, uint32_t B1r, uint32_t R, uint64_t total, uint64_t *part_off,
                               hipStream_t s) {

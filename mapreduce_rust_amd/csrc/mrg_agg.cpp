@@ -339,7 +339,6 @@ AggLaunch agg_launch(mrg_ctx *c, const MapArgs &A, uint32_t nreg, uint32_t regca
     B.out = c->keys.ks;
     B.counters = c->d_cnt;
     B.hash_bits = hash_bits(c);
-    B.ablate = getenv("MRG_AGG_ABLATE") ? (uint32_t)atoi(getenv("MRG_AGG_ABLATE")) : 0u;
     B.nsub = nsub;
     B.kcap = c->keys.cap;
     B.n_reduce = c->R;

@@ -182,15 +182,6 @@ struct MapArgs {
     uint32_t kwords;             // list capacity per workgroup (tiles of its share + its steal budget); bounds the appends
     unsigned long long *counters;
     uint32_t hash_bits;          // 0 = full; else truncate internal hashes (collision test knob)
-    uint32_t ablate;             // perf diagnostics only (env MRG_ABLATE; results are WRONG when set):
-                                 // 1 = no tail-record stores, 2 = no LDS-table probe (all tokens
-                                 // become tail records), 4 = no per-token work after the queue,
-                                 // 8 = every block loads its document's first block (L2-resident),
-                                 // 16 = no LDS count add on table hits, 32 = classification
-                                 // only, 64 = no queue writes (and no tokens), 128 = every slow
-                                 // token through the codepoint walker (results exact: an A/B knob),
-                                 // 256 = no UTF-8 class fix of non-ASCII blocks, 512 = no slow
-                                 // tokens, 1024 = no squeeze of multi-byte gaps
     unsigned long long *prof;    // perf diagnostics (env MRG_PROF): per-phase wave clocks, [7]; else null
     // wide map (near-unique keys, wc): no LDS combine -- every short key goes
     // straight to its L1 bucket b = partition * wB1r + quantile (SipHash-1-3 % R, then the splitters of a
@@ -333,7 +324,6 @@ struct BucketArgs {
     KeySet out;
     unsigned long long *counters;
     uint32_t hash_bits;
-    uint32_t ablate;             // timing only (MRG_AGG_ABLATE): 1 = no table adds, 2 = no hash either, 4 = no tail stream at all
     uint32_t nsub;               // workgroups per bucket, each summing one hash sub-range (1 = whole bucket)
     uint64_t kcap;               // capacity of `out` (keys beyond it are counted, not written)
     uint32_t n_reduce;           // partition of every key written (SipHash-1-3 % n_reduce; 0 = leave to k_partition)

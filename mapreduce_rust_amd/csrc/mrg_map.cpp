@@ -649,7 +649,6 @@ void job_map(mrg_ctx *c) {
         A.fdoc = idx ? att.get<uint32_t>((uint64_t)grid * cap) : nullptr;
         A.foff = att.get<uint32_t>((uint64_t)grid * (MRG_NBUCKET + 1));
         const uint64_t lslots = map_args_shared(c, att, A, in, ms, lcap, launches == 0, launches);
-        A.ablate = getenv("MRG_ABLATE") ? (uint32_t)atoi(getenv("MRG_ABLATE")) : 0u;
         A.prof = nullptr;
         if (getenv("MRG_PROF")) {
             A.prof = att.get<unsigned long long>(8 + 8ull * grid);

@@ -280,7 +280,7 @@ def test_compacted_decode_edge(ctx, leads):
     per 2 KiB block, two per even lane (T = 64).  One lead fewer (T = 63); one more, in an odd segment (T =
     65: the per-lane loop takes over).  The document is first in its buffer, so block 0 is its first 2 KiB.
     Both paths must give the same output, so the test cannot tell which one ran: it pins the results on both
-    sides of the switch (and only of a build with MRG_MAP_CMPT, the default), not that the switch is at 64."""
+    sides of the switch, not that the switch is at 64."""
     import mapreduce_rust_amd as M
     import oracle_lib as O
     from gpu_util import run_wc
