@@ -146,11 +146,15 @@ int mrg_set_timing(mrg_ctx *ctx, int enable);
 /* Start a job.  n_reduce = nReduce (worker.rs:129).  Clears previous job state. */
 int mrg_job_begin(mrg_ctx *ctx, int app, uint32_t n_reduce, uint32_t flags);
 /* Document names, indexed by global document id (indexer output; ignored by wc).  Every rank of a
- * multi-GPU job passes the full table.  Names must not contain ' ', ',' or '\n'. */
+ * multi-GPU job passes the full table.  Names must not contain ' ', ',' or '\n'.
+ * Every document id the job's keys carry (from mrg_job_set_input, mrg_map or mrg_job_import) must be below
+ * n_names: mrg_job_reduce and mrg_job_final return MRG_EINVAL for an id that has no name. */
 int mrg_job_set_doc_names(mrg_ctx *ctx, const char *const *names, uint32_t n_names);
 /* Input: documents laid out back to back in ONE device buffer d_bytes (16-byte aligned);
  * document i is d_bytes[h_doc_off[i] .. h_doc_off[i+1]) with global id h_doc_ids[i] (NULL: i).
- * The buffer is borrowed until the next mrg_job_begin. */
+ * The buffer is borrowed until the next mrg_job_begin.
+ * Indexer: an id is not checked here (the names may be set later); an id at or above the n_names of
+ * mrg_job_set_doc_names makes mrg_job_reduce and mrg_job_final return MRG_EINVAL. */
 int mrg_job_set_input(mrg_ctx *ctx, const uint8_t *d_bytes, const uint64_t *h_doc_off, uint32_t n_docs,
                       const uint32_t *h_doc_ids);
 /* Map: tokenize (wc.rs:6-13) + combine + SipHash partition (worker.rs:111-115).  Validates UTF-8. */
@@ -542,7 +546,8 @@ int mrg_parts_get(const mrg_parts *parts, uint32_t r, const uint8_t **h_rec, uin
                   const uint8_t **h_heap, uint64_t *heap_bytes);
 void mrg_parts_free(mrg_parts *parts);
 /* One reduce task: partition r of k map outputs -> exact bytes of mr-{r}.txt (worker.rs:157-193).
- * For the indexer, doc_names[id] names global document id (n_docs entries). */
+ * For the indexer, doc_names[id] names global document id (n_docs entries); MRG_EINVAL when a record of
+ * the partition carries an id (mrg_map's doc_id) at or above n_docs. */
 int mrg_reduce(mrg_ctx *ctx, int app, uint32_t r, const mrg_parts *const *in, size_t k, uint32_t n_reduce,
                uint32_t flags, const char *const *doc_names, uint32_t n_docs, uint8_t **h_out, size_t *h_out_len);
 

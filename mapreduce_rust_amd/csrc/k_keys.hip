@@ -910,6 +910,17 @@ __global__ void k_make_sortrec(KeySet ks, uint64_t n, const uint32_t *doc_rank, 
     out[i] = r;
 }
 
+// the largest of doc[0..n): one LDS atomic per thread, one global atomic per workgroup (*out zeroed by the caller)
+__global__ void k_max_u32(const uint32_t *doc, uint64_t n, uint32_t *out) {
+    __shared__ uint32_t m;
+    if (threadIdx.x == 0) m = 0u;
+    __syncthreads();
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) atomicMax(&m, doc[i]);
+    __syncthreads();
+    if (threadIdx.x == 0 && m) atomicMax(out, m);
+}
+
 template <class T>
 __global__ void k_fill(T *p, T v, uint64_t n) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1002,6 +1013,10 @@ void mrg_launch_export_pack(KeySet ks, const uint8_t *heap, uint64_t n, uint32_t
 void mrg_launch_make_sortrec(KeySet ks, uint64_t n, const uint32_t *doc_rank, void *recs, hipStream_t s, bool carry) {
     if (!n) return;
     hipLaunchKernelGGL(k_make_sortrec, grid_for(n), dim3(256), 0, s, ks, n, doc_rank, (SortRec *)recs, carry ? 1 : 0);
+}
+void mrg_launch_max_doc(KeySet ks, uint64_t n, uint32_t *d_max, hipStream_t s) {
+    if (!n) return;
+    hipLaunchKernelGGL(k_max_u32, grid_for(n), dim3(256), 0, s, ks.doc, n, d_max);
 }
 void mrg_launch_wide_counts(const BucketArgs &a, uint64_t *cnt, uint64_t nseg, hipStream_t s) {
     hipLaunchKernelGGL(k_wide_counts, grid_for(nseg), dim3(256), 0, s, a, cnt);

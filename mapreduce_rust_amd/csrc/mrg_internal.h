@@ -368,6 +368,8 @@ void mrg_launch_export_pack(KeySet ks, const uint8_t *heap, uint64_t n, uint32_t
 // carry (wc, counts not changed after the sort): count and length in the record's doc / pad words
 void mrg_launch_make_sortrec(KeySet ks, uint64_t n, const uint32_t *doc_rank, void *recs, hipStream_t s,
                              bool carry = false);
+// *d_max (zeroed by the caller) = the largest document id of the n keys (indexer: checked against the names)
+void mrg_launch_max_doc(KeySet ks, uint64_t n, uint32_t *d_max, hipStream_t s);
 void mrg_launch_fill_u32(uint32_t *p, uint32_t v, uint64_t n, hipStream_t s);
 void mrg_launch_fill_u64(uint64_t *p, uint64_t v, uint64_t n, hipStream_t s);
 void mrg_launch_iota_u32(uint32_t *p, uint64_t n, hipStream_t s);

@@ -43,7 +43,17 @@ DocRank doc_ranks(mrg_ctx *c, Scratch &sc) {
     HIPCHK(hipMemcpyAsync(d.rank, rank.data(), 4ull * nn, hipMemcpyHostToDevice, s));
     if (!cat.empty()) HIPCHK(hipMemcpyAsync(d.names, cat.data(), cat.size(), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(d.name_off, noff.data(), 8ull * (nn + 1), hipMemcpyHostToDevice, s));
+    // every key's document id must have a name: rank[id] and name_off[rank + 1] are read without a bound.
+    // Covers ids from mrg_job_set_input, mrg_map, mrg_job_import and the accumulator; read back with the
+    // sync below.
+    uint32_t *d_max = sc.get<uint32_t>(1);
+    uint32_t max_id = 0;
+    HIPCHK(hipMemsetAsync(d_max, 0, 4, s));
+    mrg_launch_max_doc(c->keys.ks, c->keys.n, d_max, s);
+    HIPCHK(hipMemcpyAsync(&max_id, d_max, 4, hipMemcpyDeviceToHost, s));
     sync(c);  // host vectors go out of scope
+    if (c->keys.n && max_id >= nn)
+        raise(MRG_EINVAL, "indexer: document id %u has no name (%u names; mrg_job_set_doc_names)", max_id, nn);
     return d;
 }
 
