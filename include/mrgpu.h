@@ -125,7 +125,8 @@ typedef struct {
  * (6, additive): mrg_vocab_postings
  * (6, additive): mrg_vocab_search
  * (6, additive): mrg_vocab_stats_add, mrg_vocab_search_shard, mrg_search_merge, MRG_SEARCH_MAX_SHARDS
- * (6, additive): mrg_vocab_postings_merge */
+ * (6, additive): mrg_vocab_postings_merge
+ * (6, additive): mrg_vocab_search_bool, mrg_vocab_search_bool_shard, MRG_Q_SHOULD, MRG_Q_MUST, MRG_Q_MUST_NOT */
 #define MRG_ABI_VERSION 6
 
 const char *mrg_last_error(void);
@@ -461,6 +462,57 @@ int mrg_vocab_search_shard(mrg_ctx *ctx, const mrg_vocab *v, const uint64_t *d_p
 int mrg_search_merge(mrg_ctx *ctx, uint32_t n_shards, uint32_t n_queries, uint32_t k_in, const uint32_t *d_in_docs,
                      const float *d_in_scores, const uint32_t *h_in_top_n, uint32_t k_out, uint32_t *d_top_docs,
                      float *d_top_scores, uint32_t *h_top_n);
+
+/* ---- Boolean queries (6, additive) ----
+ * mrg_vocab_search_bool, mrg_vocab_search_bool_shard: mrg_vocab_search and mrg_vocab_search_shard with a role for
+ * every query position.  h_q_role (host memory) is indexed like d_q_ids: h_q_role[j] is the role of d_q_ids[j]
+ * for j in h_q_off[0] .. h_q_off[n_queries] - 1, the entries below h_q_off[0] are not read; NULL means every
+ * position is MRG_Q_SHOULD.  Everything not named here is as for the plain call -- layout, validation, chunking
+ * by MRG_SEARCH_ACC_BYTES, the "index N" and "posting N" errors, the d_df checks of the shard call (for positions
+ * of every role), the output rows, "the entries from h_top_n[q] on are not written", two calls giving identical
+ * bytes.
+ *   score(q,d) = the sum over the positions j of q whose role is SHOULD or MUST, in order, of w(q[j], d)
+ * -- the same float32 additions in the same order that mrg_vocab_search performs for q with its MUST_NOT
+ * positions deleted, so for a document that passes the filter the score is that call's score, bit for bit.
+ * A document stands in the postings of a word when the index passed holds a posting of it for that word,
+ * whatever the posting's tf: a tf of 0 satisfies MUST, triggers MUST_NOT, and adds 0 to the score.
+ * d is a hit of q when d stands in the postings of the word of every MUST position, in the postings of the word
+ * of no MUST_NOT position, and score(q,d) > 0.  Hence:
+ *   a word that stands m times as MUST is required once and scores m times;
+ *   a MUST position that is MRG_ID_UNK, or a word with no postings in this index, gives the query no hits (in
+ *     a shard call: no hits in this shard), and none of the query's postings are visited then;
+ *   a MUST_NOT position that is MRG_ID_UNK, or a word with no postings, excludes nothing;
+ *   the same word as MUST and MUST_NOT gives no hits; the same word as SHOULD and MUST_NOT excludes its
+ *     documents; where a MUST_NOT position stands in its query makes no difference;
+ *   a query of MUST_NOT positions only has no hits: its score is 0.
+ * h_top_n[q] = min(k, hits of q), and the selection at the k-th place is exact among the hits (score descending,
+ * then document ascending).  With h_q_role = NULL, or every role MRG_Q_SHOULD, both calls run the plain search
+ * and write byte for byte what mrg_vocab_search / mrg_vocab_search_shard write.
+ * Shards that partition the documents, searched with mrg_vocab_search_bool_shard with k = k_in >= k_out and merged
+ * with mrg_search_merge, give the rows of mrg_vocab_search_bool over the index in one piece with k = k_out, byte
+ * for byte: a document lives in one shard, which holds all its postings and filters it alone.
+ * Refused in addition, checked before any device work, MRG_EINVAL with every output untouched: a role above 2
+ * (mrg_last_error names the smallest index, "role at index N").  The postings of MUST_NOT words are visited and
+ * checked like the others ("posting N"), except their d_tf, which is not read.  The call never writes outside its
+ * rows.  After every error the context and the vocabulary stay usable, and all pool scratch is returned.
+ * Scratch: as for the plain call when every role is SHOULD.  Otherwise 4 more bytes per document and query of
+ * a chunk (the match state: the distinct MUST words that hold the document, the top bit once a MUST_NOT word
+ * does), so a chunk holds MRG_SEARCH_ACC_BYTES / (8 n_docs) queries, and 8 bytes per query that has a MUST or
+ * MUST_NOT position. */
+#define MRG_Q_SHOULD 0u    /* scores; not required (every position of mrg_vocab_search is this) */
+#define MRG_Q_MUST 1u      /* scores; a hit stands in this word's postings */
+#define MRG_Q_MUST_NOT 2u  /* scores nothing; a hit does not stand in this word's postings */
+int mrg_vocab_search_bool(mrg_ctx *ctx, const mrg_vocab *v, const uint64_t *d_post_off, const uint32_t *d_docs,
+                          const uint32_t *d_tf, uint64_t n_entries, const uint32_t *d_doc_len, uint32_t n_docs,
+                          uint32_t doc_base, const uint32_t *d_q_ids, const uint8_t *h_q_role, const uint64_t *h_q_off,
+                          uint32_t n_queries, float k1, float b, uint32_t k, uint32_t *d_top_docs, float *d_top_scores,
+                          uint32_t *h_top_n);
+int mrg_vocab_search_bool_shard(mrg_ctx *ctx, const mrg_vocab *v, const uint64_t *d_post_off, const uint32_t *d_docs,
+                                const uint32_t *d_tf, uint64_t n_entries, const uint32_t *d_doc_len, uint32_t n_docs,
+                                uint32_t doc_base, const uint64_t *d_df, uint64_t coll_docs, uint64_t coll_sum_len,
+                                const uint32_t *d_q_ids, const uint8_t *h_q_role, const uint64_t *h_q_off,
+                                uint32_t n_queries, float k1, float b, uint32_t k, uint32_t *d_top_docs,
+                                float *d_top_scores, uint32_t *h_top_n);
 
 /* (6, additive): mrg_vocab_postings_merge.  The indexes of the shards of one collection -> one index, on the
  * device; the merged index is searched with the plain mrg_vocab_search.  Shard s is what mrg_vocab_postings wrote

@@ -12,8 +12,8 @@ package is the host-side mirror of the reference's interfaces over that ABI:
 
 There is no CPU fallback: if the HIP library is missing or no GPU is present, calls raise.
 """
-from .native import (APP_INDEXER, APP_WC, FLAG_FINAL_TXT, FLAG_NO_COMPAT_DROP_LAST, ID_UNK, Comm, Context, MrgError,
-                     Vocab, comm_id, debug_hash_bits, lib_path, load)
+from .native import (APP_INDEXER, APP_WC, FLAG_FINAL_TXT, FLAG_NO_COMPAT_DROP_LAST, ID_UNK, Q_MUST, Q_MUST_NOT,
+                     Q_SHOULD, Comm, Context, MrgError, Vocab, clause_roles, comm_id, debug_hash_bits, lib_path, load)
 
 __all__ = ["APP_WC", "APP_INDEXER", "FLAG_NO_COMPAT_DROP_LAST", "FLAG_FINAL_TXT", "MrgError", "Context", "Comm",
-           "Vocab", "ID_UNK", "comm_id", "debug_hash_bits", "lib_path", "load"]
+           "Vocab", "ID_UNK", "Q_SHOULD", "Q_MUST", "Q_MUST_NOT", "clause_roles", "comm_id", "debug_hash_bits", "lib_path", "load"]

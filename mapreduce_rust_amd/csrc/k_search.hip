@@ -1,5 +1,5 @@
 // k_search.hip -- BM25 top-k over the inverted index of mrg_vocab_postings, for a batch of queries (gfx950;
-// DESIGN.md section 24).
+// DESIGN.md sections 24 and 34).
 //
 // mrg_vocab_search: plan -> accumulate -> select -> order, the queries in chunks of dense score rows.
 //   plan        k_srch_gather reads post_off[t], post_off[t + 1] of every query position, k_srch_sum adds the
@@ -19,6 +19,11 @@
 //               k_srch_scan (per row), k_srch_take (everything above, the first `need` ties by document).
 //   order       k_srch_order, one workgroup per query: the <= 1024 candidates ranked in LDS by (score
 //               descending, document ascending) and written to the output rows, top_n entries and no more.
+// mrg_vocab_search_bool: a call with a MUST or MUST_NOT position keeps a match state per
+// cell beside the score.  Its accumulate launches take k_srch_acc<true>, which also counts the distinct MUST words
+// that hold the document and marks the documents of MUST_NOT words; k_srch_filter then zeroes the cells of the
+// queries' rows whose state is not the query's number of distinct MUST words.  The select sees rows of hits only.
+// Every other call launches k_srch_acc<false>, the kernel without any of this.
 // No kernel waits for another workgroup.  The only atomics add integers or take a minimum: no result depends
 // on scheduling.
 #include <algorithm>
@@ -73,13 +78,23 @@ __global__ __launch_bounds__(SRCH_WG) void k_srch_sum(const uint32_t *doc_len, u
 // ---------------------------------------------------------------- accumulate
 
 // One posting, standing at position p of docs: checked, then added to its cell.  `prev` is the document of
-// position p - 1 when that belongs to the same segment (has_prev).
-__device__ __forceinline__ void srch_one(const SearchPlan &A, float *row, float idf, uint32_t doc, uint32_t tf,
-                                         uint32_t prev, bool has_prev, uint64_t p) {
+// position p - 1 when that belongs to the same segment (has_prev).  BOOL (a Boolean search, DESIGN.md section
+// 34): `mode` is the tile's SRCH_TILE_* bits, uniform in the workgroup; the match state of the cell is updated
+// like the score, with a plain read-modify-write or a plain store, and whatever the posting's tf.
+template <bool BOOL>
+__device__ __forceinline__ void srch_one(const SearchPlan &A, float *row, uint32_t *match, uint32_t mode, float idf,
+                                         uint32_t doc, uint32_t tf, uint32_t prev, bool has_prev, uint64_t p) {
     const uint32_t idx = doc - A.doc_base;
     if (idx >= A.n_docs || (has_prev && prev >= doc)) {
         atomicMin(A.err, (unsigned long long)p);
         return;
+    }
+    if (BOOL) {
+        if (mode & SRCH_TILE_EXCLUDE) {  // (a count that is lost under the store belonged to an excluded cell)
+            match[idx] = SRCH_EXCLUDED;
+            return;
+        }
+        if (mode & SRCH_TILE_COUNT) match[idx] += 1u;
     }
     if (!tf) return;  // w = 0
     const float tff = (float)tf, dl = (float)A.doc_len[idx];
@@ -87,9 +102,13 @@ __device__ __forceinline__ void srch_one(const SearchPlan &A, float *row, float 
     row[idx] += w;
 }
 
+template <bool BOOL>
 __global__ __launch_bounds__(SRCH_WG) void k_srch_acc(SearchPlan A, const SearchTile *tiles) {
     const SearchTile T = tiles[blockIdx.x];
-    float *row = A.acc + (uint64_t)T.row * A.stride;
+    const uint32_t trow = BOOL ? T.row & SRCH_TILE_ROW : T.row, mode = BOOL ? T.row & ~SRCH_TILE_ROW : 0u;
+    float *row = A.acc + (uint64_t)trow * A.stride;
+    uint32_t *match = BOOL ? A.match + (uint64_t)trow * A.stride : nullptr;
+    const bool want_tf = !(mode & SRCH_TILE_EXCLUDE);  // (a MUST_NOT tile reads the documents only)
     const int64_t lo = T.lo, hi = T.hi, seg = T.seg_lo;
     // the window of the tile starts at a 16-byte boundary of docs; it may start below the tile
     const int64_t wbase = (int64_t)(((uint64_t)T.lo + A.shift) / MRG_SEARCH_TILE * MRG_SEARCH_TILE) - (int64_t)A.shift;
@@ -98,23 +117,49 @@ __global__ __launch_bounds__(SRCH_WG) void k_srch_acc(SearchPlan A, const Search
         if (p0 + 4 <= lo || p0 >= hi) continue;
         if (p0 >= lo && p0 + 4 <= hi) {  // four postings of the tile, 16-byte aligned in docs
             const uint4 d = *reinterpret_cast<const uint4 *>(A.docs + p0);
-            uint4 f;
-            if (A.tf_vec) f = *reinterpret_cast<const uint4 *>(A.tf + p0);
-            else f = make_uint4(A.tf[p0], A.tf[p0 + 1], A.tf[p0 + 2], A.tf[p0 + 3]);
+            uint4 f = make_uint4(0u, 0u, 0u, 0u);
+            if (want_tf && A.tf_vec) f = *reinterpret_cast<const uint4 *>(A.tf + p0);
+            else if (want_tf) f = make_uint4(A.tf[p0], A.tf[p0 + 1], A.tf[p0 + 2], A.tf[p0 + 3]);
             const bool hp = p0 > seg;
             const uint32_t prev = hp ? A.docs[p0 - 1] : 0u;
-            srch_one(A, row, T.idf, d.x, f.x, prev, hp, (uint64_t)p0);
-            srch_one(A, row, T.idf, d.y, f.y, d.x, true, (uint64_t)p0 + 1u);
-            srch_one(A, row, T.idf, d.z, f.z, d.y, true, (uint64_t)p0 + 2u);
-            srch_one(A, row, T.idf, d.w, f.w, d.z, true, (uint64_t)p0 + 3u);
+            srch_one<BOOL>(A, row, match, mode, T.idf, d.x, f.x, prev, hp, (uint64_t)p0);
+            srch_one<BOOL>(A, row, match, mode, T.idf, d.y, f.y, d.x, true, (uint64_t)p0 + 1u);
+            srch_one<BOOL>(A, row, match, mode, T.idf, d.z, f.z, d.y, true, (uint64_t)p0 + 2u);
+            srch_one<BOOL>(A, row, match, mode, T.idf, d.w, f.w, d.z, true, (uint64_t)p0 + 3u);
         } else {  // the tile's first or last few postings, one by one
             for (int e = 0; e < 4; ++e) {
                 const int64_t p = p0 + e;
                 if (p < lo || p >= hi) continue;
                 const bool hp = p > seg;
-                srch_one(A, row, T.idf, A.docs[p], A.tf[p], hp ? A.docs[p - 1] : 0u, hp, (uint64_t)p);
+                srch_one<BOOL>(A, row, match, mode, T.idf, A.docs[p], want_tf ? A.tf[p] : 0u, hp ? A.docs[p - 1] : 0u, hp,
+                               (uint64_t)p);
             }
         }
+    }
+}
+
+// ---------------------------------------------------------------- filter
+
+// A Boolean search, before the select: a cell keeps its score when its match state equals the distinct MUST
+// words of its query, and becomes 0 -- no hit -- otherwise.  One row of `rows` per blockIdx.y; 16-byte loads
+// of the scores, and of the match states only where one of the four scores is set (most of a row is not).
+// The cells of the stride beyond n_docs are never written by the accumulate, and stay 0 here.
+__global__ __launch_bounds__(SRCH_WG) void k_srch_filter(SearchPlan A, const SearchFilterRow *rows) {
+    const SearchFilterRow R = rows[blockIdx.y];
+    uint4 *v = reinterpret_cast<uint4 *>(A.acc + (uint64_t)R.row * A.stride);
+    const uint4 *m = reinterpret_cast<const uint4 *>(A.match + (uint64_t)R.row * A.stride);
+    const uint64_t nvec = A.stride >> 2;
+    for (uint64_t i = (uint64_t)blockIdx.x * SRCH_WG + threadIdx.x; i < nvec; i += (uint64_t)gridDim.x * SRCH_WG) {
+        uint4 q = v[i];
+        if (!(q.x | q.y | q.z | q.w)) continue;
+        const uint4 c = m[i];
+        const bool drop = (q.x && c.x != R.need) || (q.y && c.y != R.need) || (q.z && c.z != R.need) || (q.w && c.w != R.need);
+        if (!drop) continue;
+        if (c.x != R.need) q.x = 0u;
+        if (c.y != R.need) q.y = 0u;
+        if (c.z != R.need) q.z = 0u;
+        if (c.w != R.need) q.w = 0u;
+        v[i] = q;
     }
 }
 
@@ -320,8 +365,21 @@ void mrg_search_launch_sum(const uint32_t *doc_len, uint32_t n_docs, unsigned lo
 void mrg_search_launch_acc(const SearchPlan &p, const SearchTile *tiles, uint64_t n, hipStream_t s) {
     for (uint64_t at = 0; at < n; at += 1u << 30) {  // (a grid has fewer than 2^31 workgroups)
         const unsigned g = (unsigned)std::min<uint64_t>(n - at, 1u << 30);
-        hipLaunchKernelGGL(k_srch_acc, dim3(g), dim3(SRCH_WG), 0, s, p, tiles + at);
+        hipLaunchKernelGGL(k_srch_acc<false>, dim3(g), dim3(SRCH_WG), 0, s, p, tiles + at);
     }
+}
+
+void mrg_search_launch_acc_bool(const SearchPlan &p, const SearchTile *tiles, uint64_t n, hipStream_t s) {
+    for (uint64_t at = 0; at < n; at += 1u << 30) {
+        const unsigned g = (unsigned)std::min<uint64_t>(n - at, 1u << 30);
+        hipLaunchKernelGGL(k_srch_acc<true>, dim3(g), dim3(SRCH_WG), 0, s, p, tiles + at);
+    }
+}
+
+void mrg_search_launch_filter(const SearchPlan &p, const SearchFilterRow *rows, uint32_t n, hipStream_t s) {
+    if (!n) return;  // (n <= the chunk's rows <= 65535: a grid coordinate)
+    const unsigned gx = (unsigned)std::min<uint64_t>(grid_for(p.stride >> 2), std::max(1u, (unsigned)srch_cus() * 8u / n));
+    hipLaunchKernelGGL(k_srch_filter, dim3(gx, n), dim3(SRCH_WG), 0, s, p, rows);
 }
 
 void mrg_search_launch_select(const SearchPlan &p, hipStream_t s) {

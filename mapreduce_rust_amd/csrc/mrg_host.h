@@ -268,7 +268,8 @@ struct Acc {
 //   mrg_vocab_encode        info and ms[0..2]; ms[3], the time of the last mrg_job_vocab, stays
 //   mrg_vocab_decode        info and ms[0..2]; ms[3], the time of the last mrg_vocab_from_text, stays
 //   mrg_vocab_term_counts, mrg_vocab_postings, mrg_vocab_search   everything (they write ms[0..3], ms[0..4], ms[0..3])
-//   mrg_vocab_search_shard  as mrg_vocab_search, in the same record; mrg_vocab_stats_add and mrg_search_merge keep none
+//   mrg_vocab_search_shard, mrg_vocab_search_bool, mrg_vocab_search_bool_shard  as mrg_vocab_search, in the same
+//   record; mrg_vocab_stats_add and mrg_search_merge keep none
 //   mrg_vocab_postings_merge  everything (it writes ms[0..2])
 struct VocDiag {
     uint64_t info[8] = {};

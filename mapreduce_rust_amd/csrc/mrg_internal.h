@@ -750,10 +750,23 @@ void mrg_post_launch_unpack(const PostRec *in, uint64_t n, uint32_t *docs, uint3
 // ---- k_search.hip: BM25 top-k over the inverted index
 // The part of one (query, position) segment of postings that falls into one window of MRG_SEARCH_TILE
 // postings: [lo, hi) of d_docs / d_tf, lo >= seg_lo = the segment's first posting; `row` is the query's
-// accumulator row in its chunk, idf the float idf of the position's word.
+// accumulator row in its chunk, idf the float idf of the position's word.  In a Boolean search (section 34) the
+// two top bits of `row` carry what the tile does besides or instead of scoring, SRCH_TILE_*; a plain search
+// leaves them 0 (a chunk holds at most 65535 rows).
 struct SearchTile {
     uint32_t lo, hi, seg_lo, row;
     float idf;
+};
+#define SRCH_TILE_ROW 0x3FFFFFFFu
+#define SRCH_TILE_COUNT 0x40000000u    // scores, and adds 1 to the cell's match state: the first MUST of a word
+#define SRCH_TILE_EXCLUDE 0x80000000u  // scores nothing, stores SRCH_EXCLUDED into the match state: MUST_NOT
+// The match state of a cell: the distinct MUST words that hold the document, or SRCH_EXCLUDED + as many once a
+// MUST_NOT word held it.  A query has at most 2^20 positions, so no count reaches the top bit: a cell passes
+// the filter when its state equals the query's number of distinct MUST words, and an excluded cell never does,
+// wherever the MUST_NOT stood in the query.
+#define SRCH_EXCLUDED 0x80000000u
+struct SearchFilterRow {
+    uint32_t row, need;  // the row in the chunk; its query's distinct MUST words
 };
 // One mrg_vocab_search call (the index, the scoring constants, the error cell) and its current chunk of
 // `rows` queries: everything below `rows` is chunk scratch, indexed by the row in the chunk.
@@ -769,6 +782,7 @@ struct SearchPlan {
     uint32_t want;               // min(k, n_docs): the rank the select looks for
     uint64_t stride;             // floats per accumulator row: n_docs rounded up to 4
     float *acc;                  // [rows * stride] zeroed: the scores
+    uint32_t *match;             // [rows * stride] zeroed: the match states of a Boolean search; null otherwise
     uint32_t *hist;              // [rows * 256] zeroed: the select's histogram of the current byte
     uint32_t *sel;               // [rows * 4]: prefix, rank still wanted, scores above the prefix, top_n
     uint32_t ntile;              // tiles of MRG_SEARCH_SEL_TILE documents per row
@@ -787,6 +801,10 @@ void mrg_search_launch_gather(const uint32_t *q_ids, uint64_t n_ids, const uint6
 void mrg_search_launch_sum(const uint32_t *doc_len, uint32_t n_docs, unsigned long long *sum, hipStream_t s);  // *sum zeroed
 // acc[row][doc - doc_base] += w for the n tiles at `tiles`, which belong to one position of the chunk's queries
 void mrg_search_launch_acc(const SearchPlan &p, const SearchTile *tiles, uint64_t n, hipStream_t s);
+// the same for tiles that carry SRCH_TILE_* (p.match is set): the second instantiation of the kernel
+void mrg_search_launch_acc_bool(const SearchPlan &p, const SearchTile *tiles, uint64_t n, hipStream_t s);
+// acc[row][i] = 0 where match[row][i] != need, for the n rows at `rows`: before the select
+void mrg_search_launch_filter(const SearchPlan &p, const SearchFilterRow *rows, uint32_t n, hipStream_t s);
 // the chunk's rows -> top_n[q0 ..] and the candidates (select, ordered compaction) -> the output rows q0 ..
 void mrg_search_launch_select(const SearchPlan &p, hipStream_t s);
 void mrg_search_launch_order(const SearchPlan &p, hipStream_t s);

@@ -638,6 +638,10 @@ void vocab_postings(mrg_ctx *c, const mrg_vocab *v, const uint32_t *d_terms, con
 // Then the queries go in chunks of dense score rows: one accumulate launch per query position, the radix select
 // with the ordered compaction, the ordering of the candidates.
 // cs (mrg_vocab_search_shard): the index is one shard of a collection; N, avgdl and every df are the collection's.
+// roles (mrg_vocab_search_bool, _bool_shard): h_q_role of the call, MRG_Q_* per query id,
+// indexed like h_q_off; `boolean` names the entry point.  With a role other than SHOULD in the call, every cell
+// has a match state beside its score, the accumulate launches take the role-aware kernel, and the rows of the
+// queries that have such a role are filtered before the select.  Without one the call is the plain search.
 struct CollStats {
     const uint64_t *d_df;
     uint64_t docs, sum_len;
@@ -645,8 +649,10 @@ struct CollStats {
 void vocab_search(mrg_ctx *c, const mrg_vocab *v, const uint64_t *d_post_off, const uint32_t *d_docs, const uint32_t *d_tf,
                   uint64_t n_entries, const uint32_t *d_doc_len, uint32_t n_docs, uint32_t doc_base, const uint32_t *d_q_ids,
                   const uint64_t *h_q_off, uint32_t n_queries, float k1, float b, uint32_t k, uint32_t *d_top_docs,
-                  float *d_top_scores, uint32_t *h_top_n, const CollStats *cs = nullptr) {
-    const char *fn = cs ? "mrg_vocab_search_shard" : "mrg_vocab_search";
+                  float *d_top_scores, uint32_t *h_top_n, const CollStats *cs = nullptr, const uint8_t *roles = nullptr,
+                  bool boolean = false) {
+    const char *fn = boolean ? (cs ? "mrg_vocab_search_bool_shard" : "mrg_vocab_search_bool")
+                             : (cs ? "mrg_vocab_search_shard" : "mrg_vocab_search");
     voc_args(c, v, n_queries);
     if (!d_post_off) raise(MRG_EINVAL, "null d_post_off (the vocabulary's words + 1 offsets of mrg_vocab_postings)");
     if (!h_q_off) raise(MRG_EINVAL, "null offsets (h_q_off needs n_queries + 1 entries)");
@@ -677,6 +683,13 @@ void vocab_search(mrg_ctx *c, const mrg_vocab *v, const uint64_t *d_post_off, co
     if (n_ids > (1ull << 20)) raise(MRG_EINVAL, "%s: %llu query ids in one call: at most 1048576", fn,
                                     (unsigned long long)n_ids);
     if (n_ids && !d_q_ids) raise(MRG_EINVAL, "null query ids");
+    bool filtered = false;  // a role other than SHOULD in the call
+    for (uint64_t i = qlo; roles && i < qlo + n_ids; ++i) {
+        if (roles[i] > MRG_Q_MUST_NOT)
+            raise(MRG_EINVAL, "%s: role at index %llu: %u is none of MRG_Q_SHOULD, MRG_Q_MUST, MRG_Q_MUST_NOT", fn,
+                  (unsigned long long)i, (unsigned)roles[i]);
+        filtered |= roles[i] != MRG_Q_SHOULD;
+    }
     c->srch.clear(4);
     c->srch.info[0] = n_queries;
     c->srch.info[1] = n_ids;
@@ -761,8 +774,9 @@ void vocab_search(mrg_ctx *c, const mrg_vocab *v, const uint64_t *d_post_off, co
     P.ntile = (uint32_t)((P.stride + MRG_SEARCH_SEL_TILE - 1u) / MRG_SEARCH_SEL_TILE);
     P.out_docs = d_top_docs;
     P.out_scores = d_top_scores;
+    const uint64_t cell_bytes = filtered ? 8u : 4u;  // the score, and the match state of a Boolean search
     const uint32_t rows_max = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(n_queries, 65535u),
-                                                           std::max<uint64_t>(1, acc_bytes / (4u * P.stride)));
+                                                           std::max<uint64_t>(1, acc_bytes / (cell_bytes * P.stride)));
     // the tiles, by (chunk, position, query): launch j of a chunk takes position j of its queries
     struct Launch {
         uint64_t first, n;  // tiles
@@ -770,8 +784,44 @@ void vocab_search(mrg_ctx *c, const mrg_vocab *v, const uint64_t *d_post_off, co
     std::vector<SearchTile> tiles;
     std::vector<Launch> launches;
     std::vector<uint32_t> chunk_launches;  // launches of every chunk
+    // a Boolean search: what every position does (SRCH_TILE_* or 0; QUERY_DEAD: a query that cannot have a hit),
+    // and by chunk the rows to filter
+    constexpr uint32_t QUERY_DEAD = 1u;
+    std::vector<uint32_t> mode(filtered ? n_ids : 0, 0u);
+    std::vector<SearchFilterRow> frows;
+    std::vector<uint32_t> chunk_frows;
+    std::vector<std::pair<uint32_t, uint64_t>> must;  // (word, position) of the MUST positions of one query
     for (uint64_t q0 = 0; q0 < n_queries; q0 += rows_max) {
         const uint32_t rows = (uint32_t)std::min<uint64_t>(rows_max, n_queries - q0);
+        uint32_t nf = 0;
+        for (uint32_t r = 0; filtered && r < rows; ++r) {
+            const uint64_t a = h_q_off[q0 + r] - qlo, e = h_q_off[q0 + r + 1] - qlo;
+            must.clear();
+            bool any = false, dead = false;
+            for (uint64_t i = a; i < e; ++i) {
+                const uint8_t role = roles[qlo + i];
+                any |= role != MRG_Q_SHOULD;
+                if (role == MRG_Q_MUST_NOT) mode[i] = SRCH_TILE_EXCLUDE;
+                if (role != MRG_Q_MUST) continue;
+                dead |= po[2 * i] == po[2 * i + 1];  // MRG_ID_UNK, or a word with no postings here
+                must.emplace_back(ids[i], i);
+            }
+            if (dead) {  // no tiles: the row stays zero
+                for (uint64_t i = a; i < e; ++i) mode[i] = QUERY_DEAD;
+                continue;
+            }
+            if (!any) continue;
+            std::sort(must.begin(), must.end());
+            uint32_t need = 0;
+            for (size_t m = 0; m < must.size(); ++m)
+                if (!m || must[m].first != must[m - 1].first) {  // the first MUST position of the word counts
+                    mode[must[m].second] = SRCH_TILE_COUNT;
+                    ++need;
+                }
+            frows.push_back(SearchFilterRow{r, need});
+            ++nf;
+        }
+        chunk_frows.push_back(nf);
         uint64_t longest = 0;
         for (uint32_t r = 0; r < rows; ++r) longest = std::max(longest, h_q_off[q0 + r + 1] - h_q_off[q0 + r]);
         uint32_t nl = 0;
@@ -782,6 +832,8 @@ void vocab_search(mrg_ctx *c, const mrg_vocab *v, const uint64_t *d_post_off, co
                 if (at >= h_q_off[q0 + r + 1]) continue;
                 const uint64_t a = po[2 * (at - qlo)], e = po[2 * (at - qlo) + 1], df = e - a;
                 if (!df) continue;  // MRG_ID_UNK, or a word with no postings
+                const uint32_t md = filtered ? mode[at - qlo] : 0u;
+                if (md == QUERY_DEAD) continue;
                 // (a df above N cannot ascend strictly inside the collection: the kernel reports it)
                 double x = df <= n_docs ? ((double)n_docs - (double)df + 0.5) / ((double)df + 0.5) : 0.0;
                 if (cs) {  // (checked above: the shard's df <= the collection's <= N)
@@ -791,7 +843,7 @@ void vocab_search(mrg_ctx *c, const mrg_vocab *v, const uint64_t *d_post_off, co
                 const float idf = (float)log(1.0 + x);
                 for (uint64_t lo = a; lo < e;) {
                     const uint64_t hi = std::min(e, ((lo + P.shift) / MRG_SEARCH_TILE + 1u) * MRG_SEARCH_TILE - P.shift);
-                    tiles.push_back(SearchTile{(uint32_t)lo, (uint32_t)hi, (uint32_t)a, r, idf});
+                    tiles.push_back(SearchTile{(uint32_t)lo, (uint32_t)hi, (uint32_t)a, r | md, idf});
                     lo = hi;
                 }
             }
@@ -802,12 +854,26 @@ void vocab_search(mrg_ctx *c, const mrg_vocab *v, const uint64_t *d_post_off, co
         }
         chunk_launches.push_back(nl);
     }
+    if (filtered) {  // (the tiles of a query with an unsatisfiable MUST were dropped)
+        visited = 0;
+        for (const SearchTile &t : tiles) visited += t.hi - t.lo;
+        c->srch.info[2] = visited;
+    }
     SearchTile *d_tiles = sc.get<SearchTile>(tiles.size());
     P.top_n = sc.get<uint32_t>(n_queries);
-    HIPCHK(hipMemcpyAsync(d_tiles, tiles.data(), sizeof(SearchTile) * tiles.size(), hipMemcpyHostToDevice, s));
+    if (!tiles.empty())  // (none: every query of a Boolean search has an unsatisfiable MUST)
+        HIPCHK(hipMemcpyAsync(d_tiles, tiles.data(), sizeof(SearchTile) * tiles.size(), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemsetAsync(P.top_n, 0, 4 * (uint64_t)n_queries, s));
     const uint64_t n_acc = (uint64_t)rows_max * P.stride, n_cnt = 2 * (uint64_t)rows_max * P.ntile;
     P.acc = sc.get<float>(n_acc);
+    SearchFilterRow *d_frows = nullptr;
+    if (filtered) {
+        P.match = sc.get<uint32_t>(n_acc);
+        if (!frows.empty()) {
+            d_frows = sc.get<SearchFilterRow>(frows.size());
+            HIPCHK(hipMemcpyAsync(d_frows, frows.data(), sizeof(SearchFilterRow) * frows.size(), hipMemcpyHostToDevice, s));
+        }
+    }
     P.hist = sc.get<uint32_t>(256 * (uint64_t)rows_max);
     P.sel = sc.get<uint32_t>(4 * (uint64_t)rows_max);
     P.cnt = sc.get<uint32_t>(n_cnt);
@@ -816,21 +882,27 @@ void vocab_search(mrg_ctx *c, const mrg_vocab *v, const uint64_t *d_post_off, co
     c->srch.info[3] = chunk_launches.size();
     c->srch.info[4] = launches.size();
     c->srch.info[5] = 16 * n_ids + 16 + sizeof(SearchTile) * tiles.size() + 4 * (uint64_t)n_queries + 4 * n_acc +
-                      (1024 + 16 + 8 * (uint64_t)k) * rows_max + 4 * n_cnt;
+                      (1024 + 16 + 8 * (uint64_t)k) * rows_max + 4 * n_cnt +
+                      (filtered ? 4 * n_acc + sizeof(SearchFilterRow) * frows.size() : 0);
     HIPCHK(hipMemsetAsync(P.hist, 0, 1024 * (uint64_t)rows_max, s));
     c->srch.rec(c, 5);
     if (c->timing) c->srch.ms[0] = c->srch.elapsed(c, 4, 5);
 
     // ---- the chunks
-    uint64_t li = 0;
+    uint64_t li = 0, fi = 0;
     for (uint64_t q0 = 0, ch = 0; q0 < n_queries; q0 += rows_max, ++ch) {
         P.rows = (uint32_t)std::min<uint64_t>(rows_max, n_queries - q0);
         P.q0 = (uint32_t)q0;
         c->srch.rec(c, 0);
         HIPCHK(hipMemsetAsync(P.acc, 0, 4 * (uint64_t)P.rows * P.stride, s));
+        if (filtered) HIPCHK(hipMemsetAsync(P.match, 0, 4 * (uint64_t)P.rows * P.stride, s));
         for (uint32_t j = 0; j < chunk_launches[ch]; ++j, ++li)
-            mrg_search_launch_acc(P, d_tiles + launches[li].first, launches[li].n, s);
+            (filtered ? mrg_search_launch_acc_bool : mrg_search_launch_acc)(P, d_tiles + launches[li].first, launches[li].n, s);
         c->srch.rec(c, 1);
+        if (filtered) {
+            mrg_search_launch_filter(P, d_frows + fi, chunk_frows[ch], s);
+            fi += chunk_frows[ch];
+        }
         mrg_search_launch_select(P, s);
         c->srch.rec(c, 2);
         mrg_search_launch_order(P, s);
@@ -1156,6 +1228,17 @@ int mrg_vocab_search(mrg_ctx *c, const mrg_vocab *v, const uint64_t *d_post_off,
     });
 }
 
+int mrg_vocab_search_bool(mrg_ctx *c, const mrg_vocab *v, const uint64_t *d_post_off, const uint32_t *d_docs,
+                          const uint32_t *d_tf, uint64_t n_entries, const uint32_t *d_doc_len, uint32_t n_docs,
+                          uint32_t doc_base, const uint32_t *d_q_ids, const uint8_t *h_q_role, const uint64_t *h_q_off,
+                          uint32_t n_queries, float k1, float b, uint32_t k, uint32_t *d_top_docs, float *d_top_scores,
+                          uint32_t *h_top_n) {
+    return guard([&] {
+        vocab_search(c, v, d_post_off, d_docs, d_tf, n_entries, d_doc_len, n_docs, doc_base, d_q_ids, h_q_off, n_queries, k1, b,
+                     k, d_top_docs, d_top_scores, h_top_n, nullptr, h_q_role, true);
+    });
+}
+
 int mrg_vocab_stats_add(mrg_ctx *c, const mrg_vocab *v, const uint64_t *d_post_off, const uint32_t *d_doc_len, uint32_t n_docs,
                         uint64_t *d_df, uint64_t *h_coll) {
     return guard([&] { vocab_stats_add(c, v, d_post_off, d_doc_len, n_docs, d_df, h_coll); });
@@ -1170,6 +1253,18 @@ int mrg_vocab_search_shard(mrg_ctx *c, const mrg_vocab *v, const uint64_t *d_pos
         const CollStats cs{d_df, coll_docs, coll_sum_len};
         vocab_search(c, v, d_post_off, d_docs, d_tf, n_entries, d_doc_len, n_docs, doc_base, d_q_ids, h_q_off, n_queries, k1, b,
                      k, d_top_docs, d_top_scores, h_top_n, &cs);
+    });
+}
+
+int mrg_vocab_search_bool_shard(mrg_ctx *c, const mrg_vocab *v, const uint64_t *d_post_off, const uint32_t *d_docs,
+                                const uint32_t *d_tf, uint64_t n_entries, const uint32_t *d_doc_len, uint32_t n_docs,
+                                uint32_t doc_base, const uint64_t *d_df, uint64_t coll_docs, uint64_t coll_sum_len,
+                                const uint32_t *d_q_ids, const uint8_t *h_q_role, const uint64_t *h_q_off, uint32_t n_queries,
+                                float k1, float b, uint32_t k, uint32_t *d_top_docs, float *d_top_scores, uint32_t *h_top_n) {
+    return guard([&] {
+        const CollStats cs{d_df, coll_docs, coll_sum_len};
+        vocab_search(c, v, d_post_off, d_docs, d_tf, n_entries, d_doc_len, n_docs, doc_base, d_q_ids, h_q_off, n_queries, k1, b,
+                     k, d_top_docs, d_top_scores, h_top_n, &cs, h_q_role, true);
     });
 }
 
@@ -1194,10 +1289,11 @@ int mrg_vocab_postings_merge(mrg_ctx *c, const mrg_vocab *v, uint32_t n_shards, 
 // with the scan, place (with the seams), copy (HIP events, with mrg_set_timing).
 int mrg_postings_merge_info(mrg_ctx *c, uint64_t *h_info, double *h_ms) { return voc_info(c, &mrg_ctx::pmrg, 3, h_info, h_ms); }
 
-// Diagnostics of the last mrg_vocab_search or mrg_vocab_search_shard (not in include/mrgpu.h; tools/time_search.py,
-// tools/time_search_shards.py): h_info[0..6) =
-// queries, query positions, postings visited, chunks, accumulate launches, scratch bytes; h_ms[0..4) = plan,
-// accumulate, select (with the compaction), order, summed over the chunks (HIP events, with mrg_set_timing).
+// Diagnostics of the last mrg_vocab_search, _search_shard, _search_bool or _search_bool_shard (not in include/mrgpu.h;
+// tools/time_search.py, tools/time_search_shards.py, tools/time_search_bool.py): h_info[0..6) =
+// queries, query positions, postings visited, chunks, accumulate launches, scratch bytes (with the match states of
+// a Boolean search); h_ms[0..4) = plan, accumulate, select (with the filter and the compaction), order, summed over
+// the chunks (HIP events, with mrg_set_timing).
 int mrg_search_info(mrg_ctx *c, uint64_t *h_info, double *h_ms) { return voc_info(c, &mrg_ctx::srch, 4, h_info, h_ms); }
 
 // Diagnostics of the last mrg_vocab_decode (not in include/mrgpu.h; tools/time_decode.py): h_info[0..4) =

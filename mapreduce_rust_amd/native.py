@@ -36,6 +36,8 @@ SEARCH_MAX_K = 1024
 # search_merge: at most SEARCH_MAX_SHARDS rows per query; they are staged in LDS when n_shards * k_in is at most
 # MERGE_LDS_KEYS, and read from global memory otherwise (MRG_SEARCH_MAX_SHARDS, MRG_MERGE_LDS_KEYS of csrc/mrg_device.h)
 SEARCH_MAX_SHARDS = 64
+# search_bool: the role of a query position (MRG_Q_SHOULD, MRG_Q_MUST, MRG_Q_MUST_NOT of include/mrgpu.h)
+Q_SHOULD, Q_MUST, Q_MUST_NOT = 0, 1, 2
 MERGE_LDS_KEYS = 8192
 # postings_merge: one workgroup copies PMERGE_TILE consecutive entries of one shard (MRG_PMERGE_TILE of
 # csrc/mrg_device.h)
@@ -143,6 +145,11 @@ _SIGS = {
     "mrg_vocab_stats_add": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _u64p]),
     "mrg_vocab_search_shard": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint64, _vp, C.c_uint32, C.c_uint32, _vp, C.c_uint64,
                                          C.c_uint64, _vp, _u64p, C.c_uint32, C.c_float, C.c_float, C.c_uint32, _vp, _vp, _u32p]),
+    "mrg_vocab_search_bool": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint64, _vp, C.c_uint32, C.c_uint32, _vp, C.c_char_p, _u64p,
+                                        C.c_uint32, C.c_float, C.c_float, C.c_uint32, _vp, _vp, _u32p]),
+    "mrg_vocab_search_bool_shard": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint64, _vp, C.c_uint32, C.c_uint32, _vp, C.c_uint64,
+                                              C.c_uint64, _vp, C.c_char_p, _u64p, C.c_uint32, C.c_float, C.c_float, C.c_uint32,
+                                              _vp, _vp, _u32p]),
     "mrg_search_merge": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _u32p, C.c_uint32, _vp, _vp, _u32p]),
     "mrg_vocab_postings_merge": (C.c_int, [_vp, _vp, C.c_uint32, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _u64p, _vp, _vp,
                                            _vp, C.c_uint64, _u64p]),
@@ -207,6 +214,34 @@ def _check(rc):
 
 def _u64arr(xs):
     return (C.c_uint64 * max(len(xs), 1))(*xs)
+
+
+def _roles_arg(q_roles, q_off):
+    """h_q_role of the Boolean searches: None, or one byte per query id up to q_off[-1]"""
+    if q_roles is None:
+        return None
+    q_roles = bytes(q_roles)
+    if len(q_roles) < q_off[-1]:
+        raise ValueError(f"q_roles needs q_off[-1] = {q_off[-1]} entries (indexed like the query ids), has {len(q_roles)}")
+    return q_roles
+
+
+def clause_roles(tok_off):
+    """The roles and query offsets of Boolean queries that were encoded as three consecutive "documents" each --
+    the must, should and must-not texts of a query, any of them empty -- in one encode() call: tok_off is the
+    3 * n_queries + 1 token offsets encode() returned.  Returns (roles, q_off): query q is the ids
+    tok_off[3 q] .. tok_off[3 q + 3] with the roles by clause, as search_bool() takes them beside the ids
+    encode() wrote.  No id is copied; the entries of roles below tok_off[0] are not read by the search."""
+    tok_off = [int(x) for x in tok_off]
+    if len(tok_off) < 1 or (len(tok_off) - 1) % 3:
+        raise ValueError("tok_off needs 3 * n_queries + 1 entries: the must, should and must-not text of every query")
+    roles = bytearray(tok_off[-1])
+    for i in range(len(tok_off) - 1):
+        if tok_off[i + 1] < tok_off[i]:
+            raise ValueError(f"tok_off must be non-decreasing (entry {i})")
+        role = (Q_MUST, Q_SHOULD, Q_MUST_NOT)[i % 3]
+        roles[tok_off[i]:tok_off[i + 1]] = bytes([role]) * (tok_off[i + 1] - tok_off[i])
+    return bytes(roles), tok_off[::3]
 
 
 def _voc_info(name, ctx, info_keys, ms_keys):
@@ -595,6 +630,36 @@ class Context:
                                              k, top_docs_ptr, top_scores_ptr, top))
         return list(top)[:n]
 
+    def search_bool(self, vocab, post_off_ptr, docs_ptr, tf_ptr, n_entries, doc_len_ptr, n_docs, q_ids_ptr, q_roles, q_off, k,
+                    top_docs_ptr, top_scores_ptr, k1=1.2, b=0.75, doc_base=0):
+        """mrg_vocab_search_bool: search() with a role for every query position.  q_roles (bytes or a sequence of
+        ints, indexed like the query ids: q_roles[j] belongs to q_ids[j]; None: all Q_SHOULD) holds Q_SHOULD,
+        Q_MUST or Q_MUST_NOT.  A hit stands in the postings of every MUST word and of no MUST_NOT word; SHOULD and
+        MUST positions score, MUST_NOT positions do not.  clause_roles() makes q_roles and q_off from encode()'s
+        offsets."""
+        if len(q_off) < 1:
+            raise ValueError("q_off needs n_queries + 1 entries (at least [0])")
+        n = len(q_off) - 1
+        top = (C.c_uint32 * max(n, 1))()
+        _check(load().mrg_vocab_search_bool(self.h, vocab.h, post_off_ptr, docs_ptr, tf_ptr, n_entries, doc_len_ptr, n_docs,
+                                            doc_base, q_ids_ptr, _roles_arg(q_roles, q_off), _u64arr(q_off), n, k1, b, k,
+                                            top_docs_ptr, top_scores_ptr, top))
+        return list(top)[:n]
+
+    def search_bool_shard(self, vocab, post_off_ptr, docs_ptr, tf_ptr, n_entries, doc_len_ptr, n_docs, q_ids_ptr, q_roles,
+                          q_off, k, top_docs_ptr, top_scores_ptr, df_ptr, coll, k1=1.2, b=0.75, doc_base=0):
+        """mrg_vocab_search_bool_shard: search_bool() over one shard of a collection, scored with the collection's
+        statistics as search_shard() is.  A shard filters its own documents; the rows go through search_merge()."""
+        if len(q_off) < 1:
+            raise ValueError("q_off needs n_queries + 1 entries (at least [0])")
+        n = len(q_off) - 1
+        top = (C.c_uint32 * max(n, 1))()
+        _check(load().mrg_vocab_search_bool_shard(self.h, vocab.h, post_off_ptr, docs_ptr, tf_ptr, n_entries, doc_len_ptr,
+                                                  n_docs, doc_base, df_ptr, int(coll[0]), int(coll[1]), q_ids_ptr,
+                                                  _roles_arg(q_roles, q_off), _u64arr(q_off), n, k1, b, k, top_docs_ptr,
+                                                  top_scores_ptr, top))
+        return list(top)[:n]
+
     def search_merge(self, n_shards, n_queries, k_in, in_docs_ptr, in_scores_ptr, in_top_n, k_out, top_docs_ptr,
                      top_scores_ptr):
         """mrg_search_merge: the rows of n_shards searches over the same queries -> the collection's rows.  Row
@@ -633,8 +698,9 @@ class Context:
                          ("ms_sum", "ms_place", "ms_copy"))
 
     def search_info(self):
-        """Diagnostics of the last search(): queries, query positions, postings visited, chunks, accumulate
-        launches, scratch bytes; HIP-event ms per phase, summed over the chunks (with set_timing)."""
+        """Diagnostics of the last search(), search_shard(), search_bool() or search_bool_shard(): queries, query
+        positions, postings visited, chunks, accumulate launches, scratch bytes (with the match states of a Boolean
+        search); HIP-event ms per phase, summed over the chunks (with set_timing)."""
         return _voc_info("mrg_search_info", self, ("queries", "positions", "postings", "chunks", "acc_launches",
                                                    "scratch_bytes"),
                          ("ms_plan", "ms_accumulate", "ms_select", "ms_order"))

@@ -37,6 +37,10 @@ pub const MRG_ID_UNK: u32 = 0xFFFF_FFFF;
 pub const MRG_SEARCH_MAX_K: u32 = 1024;
 /// `mrg_search_merge`: the most shards one call merges.
 pub const MRG_SEARCH_MAX_SHARDS: u32 = 64;
+/// `mrg_vocab_search_bool`: the role of a query position.
+pub const MRG_Q_SHOULD: u8 = 0;
+pub const MRG_Q_MUST: u8 = 1;
+pub const MRG_Q_MUST_NOT: u8 = 2;
 pub const MRG_XREC_BYTES: usize = 24;
 pub const MRG_ABI_VERSION: u32 = 6;
 pub const MRG_COMM_ID_BYTES: usize = 128;
@@ -144,6 +148,10 @@ extern "C" {
     pub fn mrg_vocab_search(ctx: *mut mrg_ctx, v: *const mrg_vocab, d_post_off: *const u64, d_docs: *const u32, d_tf: *const u32, n_entries: u64, d_doc_len: *const u32, n_docs: u32, doc_base: u32, d_q_ids: *const u32, h_q_off: *const u64, n_queries: u32, k1: f32, b: f32, k: u32, d_top_docs: *mut u32, d_top_scores: *mut f32, h_top_n: *mut u32) -> c_int;
     pub fn mrg_vocab_stats_add(ctx: *mut mrg_ctx, v: *const mrg_vocab, d_post_off: *const u64, d_doc_len: *const u32, n_docs: u32, d_df: *mut u64, h_coll: *mut u64) -> c_int;
     pub fn mrg_vocab_search_shard(ctx: *mut mrg_ctx, v: *const mrg_vocab, d_post_off: *const u64, d_docs: *const u32, d_tf: *const u32, n_entries: u64, d_doc_len: *const u32, n_docs: u32, doc_base: u32, d_df: *const u64, coll_docs: u64, coll_sum_len: u64, d_q_ids: *const u32, h_q_off: *const u64, n_queries: u32, k1: f32, b: f32, k: u32, d_top_docs: *mut u32, d_top_scores: *mut f32, h_top_n: *mut u32) -> c_int;
+    /// `mrg_vocab_search` with a role (`MRG_Q_*`) for every query position; `h_q_role` may be null (all SHOULD).
+    pub fn mrg_vocab_search_bool(ctx: *mut mrg_ctx, v: *const mrg_vocab, d_post_off: *const u64, d_docs: *const u32, d_tf: *const u32, n_entries: u64, d_doc_len: *const u32, n_docs: u32, doc_base: u32, d_q_ids: *const u32, h_q_role: *const u8, h_q_off: *const u64, n_queries: u32, k1: f32, b: f32, k: u32, d_top_docs: *mut u32, d_top_scores: *mut f32, h_top_n: *mut u32) -> c_int;
+    /// `mrg_vocab_search_shard` with a role for every query position.
+    pub fn mrg_vocab_search_bool_shard(ctx: *mut mrg_ctx, v: *const mrg_vocab, d_post_off: *const u64, d_docs: *const u32, d_tf: *const u32, n_entries: u64, d_doc_len: *const u32, n_docs: u32, doc_base: u32, d_df: *const u64, coll_docs: u64, coll_sum_len: u64, d_q_ids: *const u32, h_q_role: *const u8, h_q_off: *const u64, n_queries: u32, k1: f32, b: f32, k: u32, d_top_docs: *mut u32, d_top_scores: *mut f32, h_top_n: *mut u32) -> c_int;
     pub fn mrg_search_merge(ctx: *mut mrg_ctx, n_shards: u32, n_queries: u32, k_in: u32, d_in_docs: *const u32, d_in_scores: *const f32, h_in_top_n: *const u32, k_out: u32, d_top_docs: *mut u32, d_top_scores: *mut f32, h_top_n: *mut u32) -> c_int;
     pub fn mrg_vocab_postings_merge(ctx: *mut mrg_ctx, v: *const mrg_vocab, n_shards: u32, h_post_off: *const *const u64, h_docs: *const *const u32, h_tf: *const *const u32, h_entries: *const u64, d_post_off: *mut u64, d_docs: *mut u32, d_tf: *mut u32, cap: u64, h_total: *mut u64) -> c_int;
 
