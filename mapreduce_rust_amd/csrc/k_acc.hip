@@ -122,27 +122,6 @@ __global__ __launch_bounds__(ACC_WG) void k_acc_rehash(AccTable O, AccTable T, b
     (void)acc_add(T, a != MRG_EMPTY_K0, a, b, d, c, p, idx);
 }
 
-// Slot of this thread's item in an append by the whole workgroup: one device atomic per workgroup
-// (k_keys.hip wg_append).  Every thread calls it.
-__device__ __forceinline__ uint64_t acc_wg_append(unsigned long long *counter, bool pred, uint32_t *s_w,
-                                                  unsigned long long *s_base) {
-    const uint64_t m = __ballot(pred);
-    const uint32_t wv = threadIdx.x >> 6, lane = __lane_id();
-    if (lane == 0) s_w[wv] = (uint32_t)__popcll(m);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t run = 0;
-        for (int w = 0; w < ACC_NW; ++w) {
-            const uint32_t c = s_w[w];
-            s_w[w] = run;
-            run += c;
-        }
-        *s_base = run ? atomicAdd(counter, (unsigned long long)run) : 0ull;
-    }
-    __syncthreads();
-    return *s_base + s_w[wv] + (uint64_t)__popcll(m & mrg_lanemask_lt());
-}
-
 __global__ __launch_bounds__(ACC_WG) void k_acc_emit(AccTable T, bool idx, KeySet out, uint64_t out_cap,
                                                     unsigned long long *counter) {
     __shared__ uint32_t s_w[ACC_NW];
@@ -152,7 +131,7 @@ __global__ __launch_bounds__(ACC_WG) void k_acc_emit(AccTable T, bool idx, KeySe
     uint64_t a = MRG_EMPTY_K0;
     if (i < T.cap) a = T.k0[i];
     const bool full = a != MRG_EMPTY_K0;
-    const uint64_t j = acc_wg_append(counter, full, s_w, &s_base);
+    const uint64_t j = mrg_wg_append<ACC_WG>(counter, full, s_w, &s_base);
     if (full && j < out_cap) {
         const uint64_t b = T.k1[i];
         out.k0[j] = a;

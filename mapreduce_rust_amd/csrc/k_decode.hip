@@ -47,14 +47,6 @@ unsigned dec_grid(uint64_t nchunks) {
     return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(need, (uint64_t)cu * 8u));
 }
 
-inline unsigned grid_for(uint64_t n, int b = DEC_WG) { return (unsigned)std::max<uint64_t>(1, (n + b - 1) / b); }
-
-__device__ __forceinline__ void wave_sync_lds() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 struct DecArgs {
     DecPlan P;
     const uint32_t *wlen;      // [n]
@@ -63,11 +55,6 @@ struct DecArgs {
     const uint64_t *line_off;  // [n + 1]
     uint64_t n;
 };
-
-__device__ __forceinline__ uint64_t wave_sum64(uint64_t v) {
-    for (int o = 32; o > 0; o >>= 1) v += (uint64_t)__shfl_xor((unsigned long long)v, o);
-    return v;
-}
 
 // The lane's four ids of a chunk: id[j] at position p0 + j.  present bit j: the position lies in
 // [lo, hi) and the id is in the vocabulary (or is UNK with unk bytes to write); len[j] = the bytes of its
@@ -136,7 +123,7 @@ __global__ __launch_bounds__(DEC_WG) void k_dec_count(DecArgs A) {
             for (int j = 0; j < 4; ++j)
                 if (((present >> j) & 1u) && p0 + (uint32_t)j < limit) sum += (uint64_t)len[j] + 1u;
         }
-        sum = wave_sum64(sum);
+        sum = mrg_wave_sum(sum);
         if (lane == 0) {
             if (MODE == DEC_COUNT) P.cnt[chunk] = sum;
             else P.out_off[item] = P.cnt[min(chunk, P.nchunks)] + sum;
@@ -178,11 +165,7 @@ __global__ __launch_bounds__(DEC_WG) void k_dec_emit(DecArgs A) {
             }
         }
         // ---- where this lane's bytes go (every lane of the wave is here)
-        uint64_t x = mine;
-        for (uint32_t o = 1; o < 64u; o <<= 1) {
-            const uint64_t y = (uint64_t)__shfl_up((unsigned long long)x, o);
-            if (lane >= o) x += y;
-        }
+        const uint64_t x = mrg_wave_scan_incl(mine);
         const uint64_t total = (uint64_t)__shfl((unsigned long long)x, 63);
         const uint64_t gs = out_lo + P.cnt[chunk], ge = min(gs + total, out_hi);  // the chunk's bytes
         uint64_t at[4];  // first byte of id j
@@ -225,7 +208,7 @@ __global__ __launch_bounds__(DEC_WG) void k_dec_emit(DecArgs A) {
                     for (uint64_t a = b0 + lane; a < b1; a += 64u) so[a - w] = from[a - a0];
                 }
             }
-            wave_sync_lds();
+            mrg_wave_sync_lds();
             // ---- flush: whole 16-byte granules inside the chunk's bytes as one store, the others bytewise
 #pragma unroll
             for (uint32_t r = 0; r < DEC_WIN / 1024u; ++r) {
@@ -239,7 +222,7 @@ __global__ __launch_bounds__(DEC_WG) void k_dec_emit(DecArgs A) {
                         if (g + b >= gs && g + b < ge) *reinterpret_cast<uint8_t *>((uintptr_t)(g + b)) = so[q + b];
                 }
             }
-            wave_sync_lds();  // the next window reuses this wave's LDS
+            mrg_wave_sync_lds();  // the next window reuses this wave's LDS
         }
     }
 }
@@ -269,7 +252,7 @@ DecArgs dec_args(const DecPlan &P, const VocTable &t, const VocWords &w) {
 uint64_t mrg_dec_bitmap_words(uint64_t nchunks) { return nchunks * (MRG_DEC_CHUNK / 32u) + 8u; }
 
 void mrg_dec_launch_bounds(const DecPlan &P, hipStream_t s) {
-    hipLaunchKernelGGL(k_dec_bounds, dim3(grid_for(P.n_docs)), dim3(DEC_WG), 0, s, P.tok_off, P.n_docs, P.bnd);
+    hipLaunchKernelGGL(k_dec_bounds, dim3(grid_for(P.n_docs, DEC_WG)), dim3(DEC_WG), 0, s, P.tok_off, P.n_docs, P.bnd);
 }
 void mrg_dec_launch_count(const DecPlan &P, const VocTable &t, const VocWords &w, hipStream_t s) {
     hipLaunchKernelGGL(k_dec_count<DEC_COUNT>, dim3(dec_grid(P.nchunks)), dim3(DEC_WG), 0, s, dec_args(P, t, w));

@@ -65,14 +65,6 @@ unsigned chunk_grid(uint64_t ntiles) {
     return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(need, (uint64_t)cu * 8u));
 }
 
-inline unsigned grid_for(uint64_t n, int b = ENC_WG) { return (unsigned)std::max<uint64_t>(1, (n + b - 1) / b); }
-
-__device__ __forceinline__ void wave_sync_lds() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // ---------------------------------------------------------------- keys
 __device__ __forceinline__ uint64_t voc_fold(uint64_t h, uint64_t w) {
     return mrg_fmix64(h ^ w) + 0x9E3779B97F4A7C15ull;
@@ -366,11 +358,6 @@ __device__ __forceinline__ void classes16(const uint32_t (&w)[4], uint32_t &W16,
     }
 }
 
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-    for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
-    return v;
-}
-
 // any bit of the per-lane 16-bit masks m[0..64) set at chunk positions [q, e)
 __device__ __forceinline__ bool any_bit(const uint16_t *m, uint32_t q, uint32_t e) {
     bool any = false;
@@ -485,7 +472,7 @@ __global__ __launch_bounds__(ENC_WG) void k_enc(EncArgs A, VocTable T) {
         s_w[wv][lane] = (uint16_t)W16;
         s_h[wv][lane] = (uint16_t)H16;
         const uint64_t LB = __ballot(brk != 0u);
-        wave_sync_lds();
+        mrg_wave_sync_lds();
         while (T16) {  // (per lane; reconverges before the scan below)
             const uint32_t j = (uint32_t)__builtin_ctz(T16);
             T16 &= T16 - 1u;
@@ -562,11 +549,7 @@ __global__ __launch_bounds__(ENC_WG) void k_enc(EncArgs A, VocTable T) {
         }
     }
     // ---- rank of this lane's tokens inside the chunk (every lane of the wave is here)
-    uint32_t x = nv;
-    for (uint32_t o = 1; o < 64u; o <<= 1) {
-        const uint32_t y = (uint32_t)__shfl_up((int)x, o);
-        if (lane >= o) x += y;
-    }
+    const uint32_t x = mrg_wave_scan_incl(nv);
     const uint32_t excl = x - nv, total = (uint32_t)__shfl((int)x, 63);
     if (MODE == ENC_COUNT) {
         if (lane == 0) A.cnt[tile] = total;
@@ -579,12 +562,12 @@ __global__ __launch_bounds__(ENC_WG) void k_enc(EncArgs A, VocTable T) {
             if (base + i < A.out_n) A.out[base + i] = s_ids[wv][i * 64u + lane];
         n_tok += total;
     }
-    wave_sync_lds();  // the next chunk reuses this wave's LDS
+    mrg_wave_sync_lds();  // the next chunk reuses this wave's LDS
     }
     if (MODE == ENC_COUNT) {
         if (lane == 0 && n_na) atomicAdd(&A.info[3], (unsigned long long)n_na);
     } else if (MODE == ENC_EMIT) {
-        const uint32_t unk = wave_sum(st.unk), lng = wave_sum(st.lng), pr = wave_sum(st.probes);
+        const uint32_t unk = mrg_wave_sum(st.unk), lng = mrg_wave_sum(st.lng), pr = mrg_wave_sum(st.probes);
         if (lane == 0) {
             if (n_tok) atomicAdd(&A.info[0], (unsigned long long)n_tok);
             if (unk) atomicAdd(&A.info[1], (unsigned long long)unk);
@@ -671,21 +654,21 @@ __global__ __launch_bounds__(ENC_WG) void k_enc_bounds(const uint64_t *doc_off, 
 
 void mrg_voc_launch_lines(const SortRec *top, uint64_t m, KeySet ks, uint64_t min_count, uint64_t *len64,
                           uint32_t *wlen, unsigned long long *nkeep, hipStream_t s) {
-    hipLaunchKernelGGL(k_voc_lines, dim3(grid_for(m + 1)), dim3(ENC_WG), 0, s, top, m, ks, min_count, len64, wlen, nkeep);
+    hipLaunchKernelGGL(k_voc_lines, dim3(grid_for(m + 1, ENC_WG)), dim3(ENC_WG), 0, s, top, m, ks, min_count, len64, wlen, nkeep);
 }
 void mrg_voc_launch_build(const VocTable &t, const uint32_t *wlen, unsigned long long *fail, hipStream_t s) {
-    hipLaunchKernelGGL(k_voc_clear, dim3(grid_for(t.cap)), dim3(ENC_WG), 0, s, t);
-    if (t.n) hipLaunchKernelGGL(k_voc_insert, dim3(grid_for(t.n)), dim3(ENC_WG), 0, s, t, wlen, fail);
+    hipLaunchKernelGGL(k_voc_clear, dim3(grid_for(t.cap, ENC_WG)), dim3(ENC_WG), 0, s, t);
+    if (t.n) hipLaunchKernelGGL(k_voc_insert, dim3(grid_for(t.n, ENC_WG)), dim3(ENC_WG), 0, s, t, wlen, fail);
 }
 
 void mrg_voc_launch_words(const VocTable &t, const VocWords &w, hipStream_t s) {
-    if (t.n) hipLaunchKernelGGL(k_voc_words, dim3(grid_for(t.n)), dim3(ENC_WG), 0, s, t, w);
+    if (t.n) hipLaunchKernelGGL(k_voc_words, dim3(grid_for(t.n, ENC_WG)), dim3(ENC_WG), 0, s, t, w);
 }
 void mrg_voc_launch_check(const VocTable &t, uint32_t *wlen, unsigned long long *err, hipStream_t s) {
-    if (t.n) hipLaunchKernelGGL(k_voc_check, dim3(grid_for(t.n)), dim3(ENC_WG), 0, s, t, wlen, err);
+    if (t.n) hipLaunchKernelGGL(k_voc_check, dim3(grid_for(t.n, ENC_WG)), dim3(ENC_WG), 0, s, t, wlen, err);
 }
 void mrg_voc_launch_verify(const VocTable &t, const uint32_t *wlen, unsigned long long *dup, hipStream_t s) {
-    if (t.n) hipLaunchKernelGGL(k_voc_verify, dim3(grid_for(t.n)), dim3(ENC_WG), 0, s, t, wlen, dup);
+    if (t.n) hipLaunchKernelGGL(k_voc_verify, dim3(grid_for(t.n, ENC_WG)), dim3(ENC_WG), 0, s, t, wlen, dup);
 }
 
 uint64_t mrg_enc_bitmap_words(uint64_t ntiles) { return ntiles * 32u + 8u; }
@@ -708,7 +691,7 @@ static EncArgs enc_args(const EncPlan &P) {
     return A;
 }
 void mrg_enc_launch_bounds(const EncPlan &P, hipStream_t s) {
-    hipLaunchKernelGGL(k_enc_bounds, dim3(grid_for((uint64_t)P.n_docs + 1)), dim3(ENC_WG), 0, s, P.doc_off, P.n_docs,
+    hipLaunchKernelGGL(k_enc_bounds, dim3(grid_for((uint64_t)P.n_docs + 1, ENC_WG)), dim3(ENC_WG), 0, s, P.doc_off, P.n_docs,
                        P.bnd);
 }
 void mrg_enc_launch_count(const EncPlan &P, const VocTable &t, hipStream_t s) {

@@ -15,8 +15,6 @@
 
 namespace {
 
-inline dim3 grid_for(uint64_t n, int b = 256) { return dim3((unsigned)((n + b - 1) / b)); }
-
 __device__ __forceinline__ uint32_t key_byte_at(const KeySet &ks, const uint8_t *heap, uint32_t e, uint32_t i,
                                                 uint64_t k0, uint64_t k1) {
     return ks.len[e] > 16u ? heap[ks.hoff[e] + i] : mrg_key_byte(k0, k1, i);
@@ -228,12 +226,12 @@ __global__ void k_gather_first(const SortRec *r, const uint64_t *H, uint64_t G, 
 }  // namespace
 
 void mrg_launch_fix_runs(SortRec *r, uint64_t n, KeySet ks, const uint8_t *heap, hipStream_t s) {
-    if (n) hipLaunchKernelGGL(k_fix_runs, grid_for(n), dim3(256), 0, s, r, n, ks, heap);
+    if (n) hipLaunchKernelGGL(k_fix_runs, grid_for(n, 256), dim3(256), 0, s, r, n, ks, heap);
 }
 
 void mrg_launch_final_part(const SortRec *r, uint64_t n, KeySet ks, const uint8_t *heap, int drop_last,
                            uint32_t *part2, hipStream_t s) {
-    if (n) hipLaunchKernelGGL(k_final_part, grid_for(n), dim3(256), 0, s, r, n, ks, heap, drop_last, part2);
+    if (n) hipLaunchKernelGGL(k_final_part, grid_for(n, 256), dim3(256), 0, s, r, n, ks, heap, drop_last, part2);
 }
 
 uint64_t mrg_format(const FormatArgs &f, DevPool &pool, uint8_t **out_buf, uint64_t *out_cap,
@@ -256,14 +254,14 @@ uint64_t mrg_format(const FormatArgs &f, DevPool &pool, uint8_t **out_buf, uint6
     uint64_t *total_d = sc.get<uint64_t>(2);
     // (no memset: k_part_off writes every entry 0..R, also for n == 0)
     uint64_t *scantmp = sc.get<uint64_t>(mrg_scan_tmp_elems(n + 1));
-    if (n && f.any_long) hipLaunchKernelGGL(k_fix_runs, grid_for(n), dim3(256), 0, s, recs, n, f.ks, f.heap);
+    if (n && f.any_long) hipLaunchKernelGGL(k_fix_runs, grid_for(n, 256), dim3(256), 0, s, recs, n, f.ks, f.heap);
 
     uint64_t total = 0;
     if (!f.indexer) {
         uint64_t *L = sc.get<uint64_t>(n + 1);
         uint64_t *O = sc.get<uint64_t>(n + 1);
         if (n) {
-            hipLaunchKernelGGL(k_wc_len, grid_for(n), dim3(256), 0, s, recs, n, f.ks, f.drop_last, f.carried, L);
+            hipLaunchKernelGGL(k_wc_len, grid_for(n, 256), dim3(256), 0, s, recs, n, f.ks, f.drop_last, f.carried, L);
             mrg_scan_u64(L, O, n, scantmp, s);
         }
         hipLaunchKernelGGL(k_total, dim3(1), dim3(1), 0, s, L, O, n, total_d);
@@ -271,8 +269,8 @@ uint64_t mrg_format(const FormatArgs &f, DevPool &pool, uint8_t **out_buf, uint6
         // 16 short-key bytes or the long key's heap bytes, and 20 digits), the count read with part_off
         grow_out(n * (16u + 2u + 20u) + f.heap_bytes + 16u);
         if (n)
-            hipLaunchKernelGGL(k_wc_write, grid_for(n), dim3(256), 0, s, recs, n, f.ks, f.heap, L, O, f.carried, *out_buf);
-        hipLaunchKernelGGL(k_part_off, grid_for(n + 1), dim3(256), 0, s, recs, O, n, R, (const uint64_t *)nullptr,
+            hipLaunchKernelGGL(k_wc_write, grid_for(n, 256), dim3(256), 0, s, recs, n, f.ks, f.heap, L, O, f.carried, *out_buf);
+        hipLaunchKernelGGL(k_part_off, grid_for(n + 1, 256), dim3(256), 0, s, recs, O, n, R, (const uint64_t *)nullptr,
                            (const uint64_t *)total_d, part_off);
         HIPCHK(hipMemcpyAsync(&total, total_d, sizeof total, hipMemcpyDeviceToHost, s));
         sc.put(L);
@@ -284,7 +282,7 @@ uint64_t mrg_format(const FormatArgs &f, DevPool &pool, uint8_t **out_buf, uint6
         uint64_t *P = sc.get<uint64_t>(n + 1);
         uint64_t G = 0, Ptot = 0;
         if (n) {
-            hipLaunchKernelGGL(k_idx_heads, grid_for(n), dim3(256), 0, s, recs, n, f.ks, f.heap, f.name_off, head, nl);
+            hipLaunchKernelGGL(k_idx_heads, grid_for(n, 256), dim3(256), 0, s, recs, n, f.ks, f.heap, f.name_off, head, nl);
             mrg_scan_u64(head, E, n, scantmp, s);
             mrg_scan_u64(nl, P, n, scantmp, s);
             hipLaunchKernelGGL(k_total, dim3(1), dim3(1), 0, s, head, E, n, total_d);
@@ -301,8 +299,8 @@ uint64_t mrg_format(const FormatArgs &f, DevPool &pool, uint8_t **out_buf, uint6
         uint64_t *GO = sc.get<uint64_t>(G + 1);
         SortRec *first = sc.get<SortRec>(G + 1);
         if (G) {
-            hipLaunchKernelGGL(k_idx_groups, grid_for(n), dim3(256), 0, s, head, E, n, H);
-            hipLaunchKernelGGL(k_idx_glen, grid_for(G), dim3(256), 0, s, recs, n, G, f.ks, H, P, Ptot, f.drop_last, GL);
+            hipLaunchKernelGGL(k_idx_groups, grid_for(n, 256), dim3(256), 0, s, head, E, n, H);
+            hipLaunchKernelGGL(k_idx_glen, grid_for(G, 256), dim3(256), 0, s, recs, n, G, f.ks, H, P, Ptot, f.drop_last, GL);
             mrg_scan_u64(GL, GO, G, scantmp, s);
         }
         hipLaunchKernelGGL(k_total, dim3(1), dim3(1), 0, s, GL, GO, G, total_d);
@@ -311,10 +309,10 @@ uint64_t mrg_format(const FormatArgs &f, DevPool &pool, uint8_t **out_buf, uint6
         HIPCHK(hipStreamSynchronize(s));
         grow_out(total + 16);
         if (n)
-            hipLaunchKernelGGL(k_idx_write, grid_for(n), dim3(256), 0, s, recs, n, G, f.ks, f.heap, head, E, H, P, GL,
+            hipLaunchKernelGGL(k_idx_write, grid_for(n, 256), dim3(256), 0, s, recs, n, G, f.ks, f.heap, head, E, H, P, GL,
                                GO, f.names, f.name_off, *out_buf);
-        if (G) hipLaunchKernelGGL(k_gather_first, grid_for(G), dim3(256), 0, s, recs, H, G, first);
-        hipLaunchKernelGGL(k_part_off, grid_for(G + 1), dim3(256), 0, s, first, GO, G, R, (const uint64_t *)nullptr,
+        if (G) hipLaunchKernelGGL(k_gather_first, grid_for(G, 256), dim3(256), 0, s, recs, H, G, first);
+        hipLaunchKernelGGL(k_part_off, grid_for(G + 1, 256), dim3(256), 0, s, first, GO, G, R, (const uint64_t *)nullptr,
                            (const uint64_t *)total_d, part_off);
         sc.put(head); sc.put(E); sc.put(nl); sc.put(P);
         sc.put(H); sc.put(GL); sc.put(GO); sc.put(first);

@@ -15,31 +15,6 @@
 
 namespace {
 
-inline dim3 grid_for(uint64_t n, int b = 256) { return dim3((unsigned)((n + b - 1) / b)); }
-
-// Slot of this thread's item in an append to *counter by the whole workgroup (every thread calls it):
-// one device atomic per workgroup instead of one per wave (a table of 2 M slots compacted with a wave
-// atomic each spent 0.4 ms on one contended counter).
-template <int WG>
-__device__ __forceinline__ uint64_t wg_append(unsigned long long *counter, bool pred, uint32_t *s_w,
-                                              unsigned long long *s_base) {
-    const uint64_t m = __ballot(pred);
-    const uint32_t wv = threadIdx.x >> 6, lane = __lane_id();
-    if (lane == 0) s_w[wv] = (uint32_t)__popcll(m);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t run = 0;
-        for (int w = 0; w < WG / 64; ++w) {
-            const uint32_t c = s_w[w];
-            s_w[w] = run;
-            run += c;
-        }
-        *s_base = run ? atomicAdd(counter, (unsigned long long)run) : 0ull;
-    }
-    __syncthreads();
-    return *s_base + s_w[wv] + (uint64_t)__popcll(m & mrg_lanemask_lt());
-}
-
 // ---------------------------------------------------------------- per-bucket LDS aggregation
 // One workgroup per hash bucket sums every record of its bucket -- the map workgroups' tail regions
 // (count 1 each), the bucket's slice of every map workgroup's flushed LDS table and the bucket's
@@ -184,6 +159,7 @@ __global__ __launch_bounds__(BA_WG, 1) void k_bucket_agg(BucketArgs A) {
             const uint32_t r = r0 + (uint32_t)lane;
             const uint32_t c = r < nreg ? (s_rn[r] + CH - 1u) / CH : 0u;
             uint32_t incl = c;
+            // not mrg_wave_scan_incl: its unsigned lane compare changes k_bucket_agg's code
             for (int o = 1; o < 64; o <<= 1) {
                 const uint32_t v = __shfl_up(incl, o);
                 if (lane >= o) incl += v;
@@ -342,6 +318,7 @@ __global__ __launch_bounds__(BA_WG, 1) void k_bucket_agg(BucketArgs A) {
                 cnt = fo[b + 1] - lo;
             }
             uint32_t incl = cnt;
+            // not mrg_wave_scan_incl: its unsigned lane compare changes k_bucket_agg's code
             for (int o = 1; o < 64; o <<= 1) {
                 const uint32_t v = __shfl_up(incl, o);
                 if (lane >= o) incl += v;
@@ -442,6 +419,7 @@ __global__ __launch_bounds__(BA_WG, 1) void k_bucket_agg(BucketArgs A) {
         const int e0 = 2 * lane, e1 = e0 + 1;
         const uint32_t c0 = e0 < NPW ? s_po[e0] : 0u, c1 = e1 < NPW ? s_po[e1] : 0u;
         uint32_t incl = c0 + c1;
+        // not mrg_wave_scan_incl: its unsigned lane compare changes k_bucket_agg's code
         for (int o = 1; o < 64; o <<= 1) {
             const uint32_t v = __shfl_up(incl, o);
             if (lane >= o) incl += v;
@@ -564,7 +542,7 @@ __global__ __launch_bounds__(TC_WG) void k_table_compact(TableArgs T, bool idx, 
     __shared__ unsigned long long s_base;
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const bool full = i < T.cap && T.tk0[i] != MRG_EMPTY_K0;
-    const uint64_t j = wg_append<TC_WG>(counter, full, s_w, &s_base);
+    const uint64_t j = mrg_wg_append<TC_WG>(counter, full, s_w, &s_base);
     if (!full) return;
     const uint64_t a = T.tk0[i], b = T.tk1[i];
     out.k0[j] = a;
@@ -945,20 +923,20 @@ void mrg_launch_bucket_agg(const BucketArgs &a, bool indexer, bool count32, hipS
 }
 
 void mrg_launch_table_clear(const TableArgs &t, bool indexer, hipStream_t s) {
-    hipLaunchKernelGGL(k_table_clear, grid_for(t.cap), dim3(256), 0, s, t, indexer);
+    hipLaunchKernelGGL(k_table_clear, grid_for(t.cap, 256), dim3(256), 0, s, t, indexer);
 }
 void mrg_launch_table_insert(const TableArgs &t, const uint64_t *k0, const uint64_t *k1, const uint32_t *cnt32,
                              const uint32_t *doc, uint64_t n, bool indexer, hipStream_t s) {
     if (!n) return;
-    hipLaunchKernelGGL(k_table_insert, grid_for(n), dim3(256), 0, s, t, k0, k1, cnt32, doc, n, indexer);
+    hipLaunchKernelGGL(k_table_insert, grid_for(n, 256), dim3(256), 0, s, t, k0, k1, cnt32, doc, n, indexer);
 }
 void mrg_launch_table_insert_x(const TableArgs &t, const XRec *x, uint64_t n, bool indexer, hipStream_t s) {
     if (!n) return;
-    hipLaunchKernelGGL(k_table_insert_x, grid_for(n), dim3(256), 0, s, t, x, n, indexer);
+    hipLaunchKernelGGL(k_table_insert_x, grid_for(n, 256), dim3(256), 0, s, t, x, n, indexer);
 }
 void mrg_launch_table_insert_l(const TableArgs &t, const LRec *x, uint64_t n, bool indexer, hipStream_t s) {
     if (!n) return;
-    hipLaunchKernelGGL(k_table_insert_l, grid_for(n), dim3(256), 0, s, t, x, n, indexer);
+    hipLaunchKernelGGL(k_table_insert_l, grid_for(n, 256), dim3(256), 0, s, t, x, n, indexer);
 }
 void mrg_launch_table_compact(const TableArgs &t, bool indexer, KeySet out, unsigned long long *counter,
                               hipStream_t s) {
@@ -966,13 +944,13 @@ void mrg_launch_table_compact(const TableArgs &t, bool indexer, KeySet out, unsi
 }
 void mrg_launch_partition(KeySet ks, const uint8_t *heap, uint64_t n, uint32_t n_reduce, hipStream_t s) {
     if (!n) return;
-    hipLaunchKernelGGL(k_partition, grid_for(n), dim3(256), 0, s, ks, heap, n, n_reduce);
+    hipLaunchKernelGGL(k_partition, grid_for(n, 256), dim3(256), 0, s, ks, heap, n, n_reduce);
 }
 void mrg_launch_long_group(const uint64_t *fp_sorted, const uint32_t *idx_sorted, const uint32_t *doc,
                            const uint8_t *heap, const uint64_t *hoff, const uint32_t *flen, uint64_t n,
                            uint32_t *rep, hipStream_t s) {
     if (!n) return;
-    hipLaunchKernelGGL(k_long_group, grid_for(n), dim3(256), 0, s, fp_sorted, idx_sorted, doc, heap, hoff, flen, n,
+    hipLaunchKernelGGL(k_long_group, grid_for(n, 256), dim3(256), 0, s, fp_sorted, idx_sorted, doc, heap, hoff, flen, n,
                        rep);
 }
 void mrg_launch_long_emit(const uint32_t *rep, const uint64_t *cnt_in, const uint64_t *k0, const uint64_t *k1,
@@ -980,20 +958,20 @@ void mrg_launch_long_emit(const uint32_t *rep, const uint64_t *cnt_in, const uin
                           unsigned long long *acc, KeySet out, unsigned long long *counter, bool indexer,
                           hipStream_t s) {
     if (!n) return;
-    hipLaunchKernelGGL(k_long_count, grid_for(n), dim3(256), 0, s, rep, cnt_in, n, acc);
-    hipLaunchKernelGGL(k_long_emit, grid_for(n), dim3(256), 0, s, rep, k0, k1, flen, hoff, doc, n,
+    hipLaunchKernelGGL(k_long_count, grid_for(n, 256), dim3(256), 0, s, rep, cnt_in, n, acc);
+    hipLaunchKernelGGL(k_long_emit, grid_for(n, 256), dim3(256), 0, s, rep, k0, k1, flen, hoff, doc, n,
                        (const unsigned long long *)acc, out, counter, indexer);
 }
 void mrg_launch_x_split_long(const XRec *x, uint64_t n, const uint64_t *seg_rec_end, const uint64_t *seg_heap_base,
                              uint32_t n_segs, LongItems li, unsigned long long *counter, bool indexer, hipStream_t s) {
     if (!n) return;
-    hipLaunchKernelGGL(k_x_split_long, grid_for(n), dim3(256), 0, s, x, n, seg_rec_end, seg_heap_base, n_segs, li,
+    hipLaunchKernelGGL(k_x_split_long, grid_for(n, 256), dim3(256), 0, s, x, n, seg_rec_end, seg_heap_base, n_segs, li,
                        counter, indexer);
 }
 void mrg_launch_l_split_long(const LRec *x, uint64_t n, const uint64_t *seg_rec_end, const uint64_t *seg_heap_base,
                              uint32_t n_segs, LongItems li, unsigned long long *counter, hipStream_t s) {
     if (!n) return;
-    hipLaunchKernelGGL(k_l_split_long, grid_for(n), dim3(256), 0, s, x, n, seg_rec_end, seg_heap_base, n_segs, li,
+    hipLaunchKernelGGL(k_l_split_long, grid_for(n, 256), dim3(256), 0, s, x, n, seg_rec_end, seg_heap_base, n_segs, li,
                        counter);
 }
 void mrg_launch_export_count(KeySet ks, uint64_t n, uint32_t n_owners, unsigned long long *rec_cnt,
@@ -1012,39 +990,39 @@ void mrg_launch_export_pack(KeySet ks, const uint8_t *heap, uint64_t n, uint32_t
 }
 void mrg_launch_make_sortrec(KeySet ks, uint64_t n, const uint32_t *doc_rank, void *recs, hipStream_t s, bool carry) {
     if (!n) return;
-    hipLaunchKernelGGL(k_make_sortrec, grid_for(n), dim3(256), 0, s, ks, n, doc_rank, (SortRec *)recs, carry ? 1 : 0);
+    hipLaunchKernelGGL(k_make_sortrec, grid_for(n, 256), dim3(256), 0, s, ks, n, doc_rank, (SortRec *)recs, carry ? 1 : 0);
 }
 void mrg_launch_max_doc(KeySet ks, uint64_t n, uint32_t *d_max, hipStream_t s) {
     if (!n) return;
-    hipLaunchKernelGGL(k_max_u32, grid_for(n), dim3(256), 0, s, ks.doc, n, d_max);
+    hipLaunchKernelGGL(k_max_u32, grid_for(n, 256), dim3(256), 0, s, ks.doc, n, d_max);
 }
 void mrg_launch_wide_counts(const BucketArgs &a, uint64_t *cnt, uint64_t nseg, hipStream_t s) {
-    hipLaunchKernelGGL(k_wide_counts, grid_for(nseg), dim3(256), 0, s, a, cnt);
+    hipLaunchKernelGGL(k_wide_counts, grid_for(nseg, 256), dim3(256), 0, s, a, cnt);
 }
 void mrg_launch_wide_gather(const BucketArgs &a, const uint64_t *off, uint64_t nseg, uint32_t n_reduce, SortRec *out,
                             hipStream_t s) {
     hipLaunchKernelGGL(k_wide_gather, dim3((unsigned)nseg), dim3(256), 0, s, a, off, n_reduce, out);
 }
 void mrg_launch_wide_heads(const SortRec *r, uint64_t n, uint64_t *head, uint64_t *cv, hipStream_t s) {
-    if (n) hipLaunchKernelGGL(k_wide_heads, grid_for(n), dim3(256), 0, s, r, n, head, cv);
+    if (n) hipLaunchKernelGGL(k_wide_heads, grid_for(n, 256), dim3(256), 0, s, r, n, head, cv);
 }
 void mrg_launch_wide_keys(const SortRec *r, uint64_t n, const uint64_t *head, const uint64_t *E, KeySet ks,
                           uint64_t *F, hipStream_t s) {
-    if (n) hipLaunchKernelGGL(k_wide_keys, grid_for(n), dim3(256), 0, s, r, n, head, E, ks, F);
+    if (n) hipLaunchKernelGGL(k_wide_keys, grid_for(n, 256), dim3(256), 0, s, r, n, head, E, ks, F);
 }
 void mrg_launch_wide_cnt(const uint64_t *F, uint64_t runs, uint64_t n, const uint64_t *C, uint64_t ctot, KeySet ks,
                          hipStream_t s) {
-    if (runs) hipLaunchKernelGGL(k_wide_cnt, grid_for(runs), dim3(256), 0, s, F, runs, n, C, ctot, ks);
+    if (runs) hipLaunchKernelGGL(k_wide_cnt, grid_for(runs, 256), dim3(256), 0, s, F, runs, n, C, ctot, ks);
 }
 void mrg_launch_fill_u32(uint32_t *p, uint32_t v, uint64_t n, hipStream_t s) {
     if (!n) return;
-    hipLaunchKernelGGL(k_fill<uint32_t>, grid_for(n), dim3(256), 0, s, p, v, n);
+    hipLaunchKernelGGL(k_fill<uint32_t>, grid_for(n, 256), dim3(256), 0, s, p, v, n);
 }
 void mrg_launch_fill_u64(uint64_t *p, uint64_t v, uint64_t n, hipStream_t s) {
     if (!n) return;
-    hipLaunchKernelGGL(k_fill<uint64_t>, grid_for(n), dim3(256), 0, s, p, v, n);
+    hipLaunchKernelGGL(k_fill<uint64_t>, grid_for(n, 256), dim3(256), 0, s, p, v, n);
 }
 void mrg_launch_iota_u32(uint32_t *p, uint64_t n, hipStream_t s) {
     if (!n) return;
-    hipLaunchKernelGGL(k_iota, grid_for(n), dim3(256), 0, s, p, n);
+    hipLaunchKernelGGL(k_iota, grid_for(n, 256), dim3(256), 0, s, p, n);
 }

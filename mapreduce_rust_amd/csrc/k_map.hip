@@ -122,17 +122,6 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
 // must be wave-uniform, as every ballot is.
 __device__ __forceinline__ uint64_t wave_mask(bool b) { return __builtin_amdgcn_ballot_w64(b); }
 __device__ __forceinline__ bool lane_of(uint64_t m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
-// a workgroup barrier for LDS only: the wave's outstanding global stores are not waited for (a
-// __syncthreads() waits for them too -- at the end of the map that is every workgroup's last tail
-// stores at once)
-__device__ __forceinline__ void lds_only_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-__device__ __forceinline__ void wave_sync_lds() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // Global memory through address-space-1 pointers.  The kernel reads its pointers from a MapArgs in
 // device memory, so without the cast every access would be a FLAT instruction -- and a pending FLAT
@@ -219,6 +208,7 @@ __device__ __forceinline__ BlkInfo locate_blk(const MapArgs &A, uint64_t c, uint
 }
 
 // Document of block c: the d with chunk_base[d] <= c < chunk_base[d + 1] (binary search; scalar).
+// not mrg_last_le: its midpoint a + (b - a) / 2 changes the map kernels' code (more spilled SGPRs)
 __device__ __forceinline__ uint32_t find_doc(const MapArgs &A, uint64_t c) {
     const CAS uint64_t *cb = cp(A.chunk_base);
     uint32_t lo = 0, hi = A.n_docs;  // cb[lo] <= c < cb[hi]
@@ -1385,7 +1375,7 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
                     const uint32_t T = lane_u32(incl, 63);
                     if (T <= 64u) {
                         LDS uint64_t *slot = (LDS uint64_t *)queue;
-                        wave_sync_lds();
+                        mrg_wave_sync_lds();
                         uint32_t pos = incl - c;
                         for (uint32_t m = mAB0; m;) {
                             const uint32_t q = (uint32_t)__builtin_ctz(m);
@@ -1399,7 +1389,7 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
                             const int so = (sb ? 1024 : 0) + (int)l16 + (int)p;
                             slot[pos++] = (uint64_t)__builtin_amdgcn_alignbyte(b, a, p & 3u) | ((uint64_t)(uint32_t)min(hi - so, 4) << 32);
                         }
-                        wave_sync_lds();
+                        mrg_wave_sync_lds();
                         if ((uint32_t)lane < T) {
                             // (the slot's address is formed here: hoisted out of the main loop it held a
                             // VGPR the kernel does not have, and was spilled to scratch)
@@ -1414,7 +1404,7 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
                             ((LDS uint32_t *)slot)[2 * ln] =
                                 n | (cl == MRG_CLS_W ? 8u : 0u) | (cl == MRG_CLS_S ? 16u : 0u);
                         }
-                        wave_sync_lds();
+                        mrg_wave_sync_lds();
                         pos = incl - c;
                         for (uint32_t m = mAB0; m;) {
                             const uint32_t q = (uint32_t)__builtin_ctz(m);
@@ -1575,7 +1565,7 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
         auto slow_tokens = [&](uint32_t nslow, uint64_t At, uint64_t whi, uint32_t nseg) {
             if (!nslow) return;
             const uint64_t wbase = At - (uint64_t)BEHIND;
-            wave_sync_lds();
+            mrg_wave_sync_lds();
             auto rd = [&](uint64_t a) -> uint32_t {
                 if (a >= At && a < whi) return (uint32_t)win[a - wbase];
                 return (uint32_t)gp(A.in)[a];
@@ -1613,7 +1603,7 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
             // ---- block queue: the whole block staged, scanned and queued once
             const uint64_t whi = Ab + (uint64_t)clip_u32(doc_hi - Ab, (uint32_t)(BLK + HALO));
             // stage the block and its 64-byte halo (the previous block's readers are done: program order)
-            wave_sync_lds();
+            mrg_wave_sync_lds();
             reinterpret_cast<uint4 *>(win)[1 + lane] = X.v0;
             reinterpret_cast<uint4 *>(win)[65 + lane] = X.v1;
             if (ln - 1u < 4u) reinterpret_cast<uint4 *>(win)[128 + lane] = X.e;
@@ -1670,7 +1660,7 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
                 }
                 MRG_PT(2);
                 const bool may_claim = table_open();
-                wave_sync_lds();
+                mrg_wave_sync_lds();
                 const uint32_t nslow = rounds(total, may_claim);
                 MRG_PT(3);
                 slow_tokens(nslow, Ab, whi, (uint32_t)(BLK / SEG));
@@ -1679,7 +1669,7 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
                 seg_hi = min(seg_lo + (uint32_t)QRANGE, (uint32_t)(BLK / SEG));
                 in_range(seg_lo, seg_hi, a0, a1);
                 total = scan2(a0, a1);
-                wave_sync_lds();  // the queue's readers are done before it is filled again
+                mrg_wave_sync_lds();  // the queue's readers are done before it is filled again
             }
         } else {
 #pragma unroll
@@ -1692,7 +1682,7 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
             const uint64_t t1 = umin64(At + (uint64_t)TILE, doc_hi);
             const uint64_t whi = umin64(t1 + (uint64_t)HALO, doc_hi);
             // stage the tile and its 64-byte halo (the previous tile's readers are done: program order)
-            wave_sync_lds();
+            mrg_wave_sync_lds();
             reinterpret_cast<uint4 *>(win)[1 + lane] = j == 0 ? X.v0 : X.v1;
             if (j == 0 ? lane < 4 : (lane >= 1 && lane < 5))
                 reinterpret_cast<uint4 *>(win)[65 + (j == 0 ? lane : lane - 1)] = j == 0 ? X.v1 : X.e;
@@ -1721,7 +1711,7 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
             const uint32_t total = lane_u32(incl, 63);
             MRG_PT(2);
             const bool may_claim = table_open();
-            wave_sync_lds();
+            mrg_wave_sync_lds();
             const uint32_t nslow = rounds(total, may_claim);
             MRG_PT(3);
             slow_tokens(nslow, At, whi, 64u);
@@ -1755,7 +1745,7 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
             return (uint32_t)c0;
         }
         const uint64_t ns2 = A.n_static, np = A.n_chunks - ns2;   // (re-read: not held in registers)
-        wave_sync_lds();
+        mrg_wave_sync_lds();
         uint32_t pt = first_u32(s_pool[wv]);
         while ((pt >> 8) < 8u) {
             const uint32_t part = pt & 7u;
@@ -1837,7 +1827,7 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
             I.Ab += (uint64_t)BLK;
             I.lo = -(int32_t)BEHIND;
         } else if (cn != NONE) {
-            wave_sync_lds();  // lane 0's writes above, read by every lane
+            mrg_wave_sync_lds();  // lane 0's writes above, read by every lane
             const uint4 r0 = *reinterpret_cast<const uint4 *>(nxt), r1 = *reinterpret_cast<const uint4 *>(nxt + 4);
             I.Ab = (uint64_t)first_u32(r0.x) | ((uint64_t)first_u32(r0.y) << 32);
             I.doc_hi = (uint64_t)first_u32(r0.z) | ((uint64_t)first_u32(r0.w) << 32);
@@ -1863,11 +1853,11 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
 #ifdef MRG_MAP_PROF
     __shared__ unsigned long long s_loop_end;
     if (tid == 0) s_loop_end = 0;
-    lds_only_barrier();
+    mrg_lds_barrier();
     if (P && lane == 0) atomicMax(&s_loop_end, (unsigned long long)wall_clock64());
 #endif
     // ---- non-ASCII tiles recorded by the main loop
-    lds_only_barrier();   // s_ngen final
+    mrg_lds_barrier();   // s_ngen final
     if (s_ngen) __syncthreads();  // (uniform) the list is complete: its global writes, then the barrier
     {
         const uint32_t ng = min(s_ngen, A.kwords);
@@ -1881,10 +1871,10 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
                 const TileInfo T = sub_tile(b, kk % NSUB);
                 uint4 x0, x1;
                 load(T, x0, x1);
-                wave_sync_lds();
+                mrg_wave_sync_lds();
                 if (j0 >= T.v0 && j0 < T.v1) reinterpret_cast<uint4 *>(win)[j0] = x0;
                 if (has1 && j1 >= T.v0 && j1 < T.v1) reinterpret_cast<uint4 *>(win)[j1] = x1;
-                wave_sync_lds();
+                mrg_wave_sync_lds();
                 my_tokens += generic_tile<CAP, IDX, WIDE, T64>(A, table, tails, win, T.At, T.t0, T.t1,
                                                     T.doc_lo, T.doc_hi, T.wlo, T.whi, T.docid);
             }
@@ -1894,7 +1884,7 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
     MRG_PT(5);
     // ---- flush the LDS table into this workgroup's region, sorted by bucket (LDS-only barriers from
     // here on: the tail stores drain meanwhile; the kernel's end waits for them)
-    lds_only_barrier();
+    mrg_lds_barrier();
     uint32_t my_tail = 0, my_tail16 = 0;
     if constexpr (WIDE) {  // the wide map: records per L1 bucket; a region past its capacity -> rerun
         uint32_t over = 0;
@@ -1923,7 +1913,7 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
         }
     }
     for (int b = tid; b <= MRG_NBUCKET; b += WG) s_hist[b] = 0;
-    lds_only_barrier();
+    mrg_lds_barrier();
     MRG_FT(0);
     for (int i = tid; i < CAP; i += WG) {
         const KeyPair k = s_key[i];
@@ -1931,7 +1921,7 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
         const uint32_t b = bucket_of(key_hash(k.a, k.b, IDX ? s_doc[i] : MRG_EMPTY_DOC, hbits));
         s_rank[i] = (uint16_t)atomicAdd(&s_hist[b], 1u);
     }
-    lds_only_barrier();
+    mrg_lds_barrier();
     MRG_FT(1);
     if (tid < 64) {  // exclusive scan of the bucket histogram by one wave
         uint32_t run = 0;
@@ -1943,7 +1933,7 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
         }
         if (lane == 0) s_hist[MRG_NBUCKET] = run;
     }
-    lds_only_barrier();
+    mrg_lds_barrier();
     MRG_FT(2);
     GAS uint32_t *foff = gp(A.foff) + (uint64_t)blockIdx.x * (MRG_NBUCKET + 1);
     for (int b = tid; b <= MRG_NBUCKET; b += WG) foff[b] = s_hist[b];
@@ -1963,6 +1953,7 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
     MRG_FT(3);
     // token and tail totals: waves -> LDS -> one device atomic per workgroup and counter (a wave
     // atomic each put 8 K atomics on two counters at the very end of the launch)
+    // not mrg_wave_sum_lane0: three calls one after the other change the map kernels' code
     uint32_t t = my_tokens, ttl = my_tail, t16 = my_tail16;
     for (int off = 32; off > 0; off >>= 1) {
         t += __shfl_down(t, off);
@@ -1974,7 +1965,7 @@ __global__ __launch_bounds__(WG, 1) void k_map(const MapArgs *__restrict__ Ap) {
         atomicAdd(&s_tot[1], ttl);
         if (t16) atomicAdd(&s_tot[2], t16);
     }
-    lds_only_barrier();
+    mrg_lds_barrier();
     if (tid == 0) {
         g_add(&A.counters[CNT_TOKENS], (unsigned long long)s_tot[0]);
         g_add(&A.counters[CNT_REC], (unsigned long long)s_tot[1]);

@@ -40,13 +40,6 @@ int pst_cus() {
     return cu;
 }
 
-inline unsigned grid_for(uint64_t n, uint64_t b = PST_WG) { return (unsigned)std::max<uint64_t>(1, (n + b - 1) / b); }
-
-__device__ __forceinline__ uint32_t pst_wave_sum(uint32_t v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-    return v;  // (lane 0)
-}
-
 // one term, standing at index `at` of the terms
 __device__ __forceinline__ void pst_count_one(const PostPlan &A, uint32_t t, uint64_t at, uint32_t *s_h, uint32_t &n_lds,
                                               uint32_t &n_glb) {
@@ -92,8 +85,8 @@ __global__ __launch_bounds__(PST_WG) void k_post_count(PostPlan A) {
         const uint32_t x = s_h[i];
         if (x) atomicAdd(&A.df[i], (unsigned long long)x);
     }
-    n_lds = pst_wave_sum(n_lds);
-    n_glb = pst_wave_sum(n_glb);
+    n_lds = mrg_wave_sum_lane0(n_lds);
+    n_glb = mrg_wave_sum_lane0(n_glb);
     if (__lane_id() == 0) {
         if (n_lds) atomicAdd(&A.stat[1], (unsigned long long)n_lds);
         if (n_glb) atomicAdd(&A.stat[2], (unsigned long long)n_glb);
@@ -106,19 +99,9 @@ __global__ __launch_bounds__(PST_WG) void k_post_max(const unsigned long long *d
     unsigned long long m = 0;
     for (uint64_t i = (uint64_t)blockIdx.x * PST_WG + threadIdx.x; i < n_words; i += (uint64_t)gridDim.x * PST_WG)
         m = max(m, df[i]);
+    // not mrg_wave_max: only lane 0 needs it, and the shifts down take 8 instructions fewer than the butterfly
     for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned long long)__shfl_down(m, o));
     if (__lane_id() == 0 && m) atomicMax(&stat[3], m);
-}
-
-// the row that holds index `pos` of the terms: the last r of [a, b) with off[r] <= pos, given
-// off[a] <= pos < off[b] (empty rows before it share its offset, so the last one is the holder)
-__device__ __forceinline__ uint32_t pst_row(const uint64_t *off, uint32_t a, uint32_t b, uint64_t pos) {
-    while (b - a > 1u) {
-        const uint32_t m = a + ((b - a) >> 1);
-        if (off[m] <= pos) a = m;
-        else b = m;
-    }
-    return a;
 }
 
 __global__ __launch_bounds__(PST_WG) void k_post_pack(PostPlan A, PostRec *out) {
@@ -126,7 +109,7 @@ __global__ __launch_bounds__(PST_WG) void k_post_pack(PostPlan A, PostRec *out) 
     const uint32_t tid = threadIdx.x;
     const uint64_t n = A.hi - A.lo;
     const uint64_t t0 = (uint64_t)blockIdx.x * MRG_POST_TILE, t1 = min(t0 + MRG_POST_TILE, n);  // (t0 < n by the grid)
-    if (tid < 2u) s_r[tid] = pst_row(A.row_off, 0u, A.n_docs, A.lo + (tid ? t1 - 1u : t0));
+    if (tid < 2u) s_r[tid] = mrg_last_le(A.row_off, 0u, A.n_docs, A.lo + (tid ? t1 - 1u : t0));
     __syncthreads();
     const uint32_t r1 = s_r[1];
     uint32_t r = s_r[0];  // rows ascend with the entries of a thread
@@ -134,7 +117,7 @@ __global__ __launch_bounds__(PST_WG) void k_post_pack(PostPlan A, PostRec *out) 
         const uint64_t i = t0 + (uint64_t)k * PST_WG + tid;
         if (i >= t1) break;
         const uint64_t pos = A.lo + i;
-        r = pst_row(A.row_off, r, r1 + 1u, pos);  // off[r1 + 1] > lo + t1 - 1 >= pos
+        r = mrg_last_le(A.row_off, r, r1 + 1u, pos);  // off[r1 + 1] > lo + t1 - 1 >= pos
         out[i] = PostRec{A.terms[pos], A.doc_base + r, A.counts ? A.counts[pos] : 0u};
     }
 }
@@ -152,12 +135,12 @@ __global__ __launch_bounds__(PST_WG) void k_post_unpack(const PostRec *in, uint6
 void mrg_post_launch_count(const PostPlan &p, hipStream_t s) {
     // all workgroups resident (4 per CU), striding over the 16-byte vectors
     const uint64_t nvec = (p.hi - p.lo) / 4u;
-    const unsigned g = (unsigned)std::min<uint64_t>(grid_for(nvec), (uint64_t)pst_cus() * 4u);
+    const unsigned g = (unsigned)std::min<uint64_t>(grid_for(nvec, PST_WG), (uint64_t)pst_cus() * 4u);
     hipLaunchKernelGGL(k_post_count, dim3(g), dim3(PST_WG), 0, s, p);
 }
 
 void mrg_post_launch_max(const PostPlan &p, hipStream_t s) {
-    const unsigned g = (unsigned)std::min<uint64_t>(grid_for(p.n_words), (uint64_t)pst_cus() * 4u);
+    const unsigned g = (unsigned)std::min<uint64_t>(grid_for(p.n_words, PST_WG), (uint64_t)pst_cus() * 4u);
     hipLaunchKernelGGL(k_post_max, dim3(g), dim3(PST_WG), 0, s, (const unsigned long long *)p.df, p.n_words, p.stat);
 }
 
@@ -168,5 +151,5 @@ void mrg_post_launch_pack(const PostPlan &p, PostRec *out, hipStream_t s) {
 
 void mrg_post_launch_unpack(const PostRec *in, uint64_t n, uint32_t *docs, uint32_t *tf, hipStream_t s) {
     if (!n) return;
-    hipLaunchKernelGGL(k_post_unpack, dim3(grid_for(n)), dim3(PST_WG), 0, s, in, n, docs, tf);
+    hipLaunchKernelGGL(k_post_unpack, dim3(grid_for(n, PST_WG)), dim3(PST_WG), 0, s, in, n, docs, tf);
 }

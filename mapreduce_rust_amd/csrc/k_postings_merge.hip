@@ -37,8 +37,6 @@ static_assert(MRG_SEARCH_MAX_SHARDS <= 64u, "the error cell holds word * 64 + sh
 constexpr uint32_t PMG_LDS_WORDS = MRG_PMERGE_TILE;
 static_assert(8u * (2u * PMG_LDS_WORDS + 3u) * 4u <= 160u * 1024u, "8 workgroups per CU");
 
-inline unsigned grid_for(uint64_t n, uint64_t b = PMG_WG) { return (unsigned)std::max<uint64_t>(1, (n + b - 1) / b); }
-
 __global__ __launch_bounds__(PMG_WG) void k_pmerge_sum(PMergePlan A) {
     const uint64_t w = (uint64_t)blockIdx.x * PMG_WG + threadIdx.x;
     if (w > A.n_words) return;
@@ -86,19 +84,8 @@ __global__ __launch_bounds__(PMG_WG) void k_pmerge_place(PMergePlan A) {
             pos += b - a;
         }
     }
-    for (int o = 32; o > 0; o >>= 1) single += __shfl_down(single, o);
+    single = mrg_wave_sum_lane0(single);
     if (__lane_id() == 0 && single) atomicAdd(A.stat + 1, (unsigned long long)single);
-}
-
-// the word that holds position `pos` of a shard: the last w of [a, b) with off[w] <= pos, given
-// off[a] <= pos < off[b] (empty words before it share its offset, so the last one is the holder)
-__device__ __forceinline__ uint32_t pmg_word(const uint64_t *off, uint32_t a, uint32_t b, uint64_t pos) {
-    while (b - a > 1u) {
-        const uint32_t m = a + ((b - a) >> 1);
-        if (off[m] <= pos) a = m;
-        else b = m;
-    }
-    return a;
 }
 
 // out[0, len) = src[0, len), src = base + at of an array of n entries; the workgroup's threads together.
@@ -145,7 +132,7 @@ __global__ __launch_bounds__(PMG_WG) void k_pmerge_copy(PMergePlan A) {
     if (t0 >= S.n) return;  // (not with the host's tile0; keeps the reads inside the shard whatever was copied)
     const uint64_t t1 = min(t0 + MRG_PMERGE_TILE, S.n);
     const uint32_t nw = (uint32_t)A.n_words;
-    if (tid < 2u) s_w[tid] = pmg_word(S.off, 0u, nw, tid ? t1 - 1u : t0);
+    if (tid < 2u) s_w[tid] = mrg_last_le(S.off, 0u, nw, tid ? t1 - 1u : t0);
     __syncthreads();
     const uint32_t w0 = s_w[0], w1 = s_w[1];
     const uint32_t *dst = A.dst + (uint64_t)s * A.n_words;
@@ -188,7 +175,7 @@ __global__ __launch_bounds__(PMG_WG) void k_pmerge_copy(PMergePlan A) {
             }
             d = (uint64_t)s_dst[i] + (p - s_rel[i]);
         } else {
-            const uint32_t w = pmg_word(S.off, w0 + i, w1 + 1u, pos);
+            const uint32_t w = mrg_last_le(S.off, w0 + i, w1 + 1u, pos);
             i = w - w0;
             d = (uint64_t)dst[w] + (pos - S.off[w]);
         }
@@ -200,12 +187,12 @@ __global__ __launch_bounds__(PMG_WG) void k_pmerge_copy(PMergePlan A) {
 }  // namespace
 
 void mrg_pmerge_launch_sum(const PMergePlan &p, hipStream_t s) {
-    hipLaunchKernelGGL(k_pmerge_sum, dim3(grid_for(p.n_words + 1)), dim3(PMG_WG), 0, s, p);
+    hipLaunchKernelGGL(k_pmerge_sum, dim3(grid_for(p.n_words + 1, PMG_WG)), dim3(PMG_WG), 0, s, p);
 }
 
 void mrg_pmerge_launch_place(const PMergePlan &p, hipStream_t s) {
     if (!p.n_words) return;
-    hipLaunchKernelGGL(k_pmerge_place, dim3(grid_for(p.n_words)), dim3(PMG_WG), 0, s, p);
+    hipLaunchKernelGGL(k_pmerge_place, dim3(grid_for(p.n_words, PMG_WG)), dim3(PMG_WG), 0, s, p);
 }
 
 void mrg_pmerge_launch_copy(const PMergePlan &p, hipStream_t s) {

@@ -52,8 +52,6 @@ int srch_cus() {
     return cu;
 }
 
-inline unsigned grid_for(uint64_t n, uint64_t b = SRCH_WG) { return (unsigned)std::max<uint64_t>(1, (n + b - 1) / b); }
-
 // ---------------------------------------------------------------- plan
 
 __global__ __launch_bounds__(SRCH_WG) void k_srch_gather(const uint32_t *q_ids, uint64_t n_ids, const uint64_t *post_off,
@@ -71,7 +69,7 @@ __global__ __launch_bounds__(SRCH_WG) void k_srch_sum(const uint32_t *doc_len, u
     unsigned long long a = 0;
     for (uint64_t i = (uint64_t)blockIdx.x * SRCH_WG + threadIdx.x; i < n_docs; i += (uint64_t)gridDim.x * SRCH_WG)
         a += doc_len[i];
-    for (int o = 32; o > 0; o >>= 1) a += (unsigned long long)__shfl_down(a, o);
+    a = mrg_wave_sum_lane0(a);
     if (__lane_id() == 0 && a) atomicAdd(sum, a);
 }
 
@@ -188,7 +186,7 @@ __global__ __launch_bounds__(SRCH_WG) void k_srch_hist(SearchPlan A, uint32_t d)
             else if (((x[j] ^ prefix) & mask) == 0u) atomicAdd(&h[(x[j] >> sh) & 0xFFu], 1u);
         }
     }
-    for (int o = 32; o > 0; o >>= 1) nz += __shfl_down(nz, o);
+    nz = mrg_wave_sum_lane0(nz);
     if (__lane_id() == 0 && nz) atomicAdd(&h[0], nz);
     __syncthreads();
     const uint32_t c = h[tid];
@@ -227,26 +225,6 @@ __global__ __launch_bounds__(256) void k_srch_pick(SearchPlan A, uint32_t d) {
     }
 }
 
-// exclusive scan of v over the workgroup's 256 threads, in thread order; *total = the sum
-__device__ __forceinline__ uint32_t srch_wg_scan(uint32_t v, uint32_t *s_w, uint32_t *total) {
-    const uint32_t lane = __lane_id(), wave = threadIdx.x >> 6;
-    uint32_t x = v;
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t y = __shfl_up(x, o);
-        if ((int)lane >= o) x += y;
-    }
-    if (lane == 63u) s_w[wave] = x;
-    __syncthreads();
-    uint32_t base = 0, tot = 0;
-    for (uint32_t w = 0; w < SRCH_WG / 64; ++w) {
-        const uint32_t c = s_w[w];
-        if (w < wave) base += c;
-        tot += c;
-    }
-    *total = tot;
-    return base + x - v;
-}
-
 // the four scores of the thread in tile `tile` of the row: bits, 0 beyond the row
 __device__ __forceinline__ uint4 srch_load4(const SearchPlan &A, uint32_t row, uint32_t tile, uint64_t *first) {
     const uint64_t i = (uint64_t)tile * SRCH_WG + threadIdx.x;
@@ -272,7 +250,7 @@ __global__ __launch_bounds__(SRCH_WG) void k_srch_count(SearchPlan A) {
     uint64_t first;
     const uint4 q = srch_load4(A, row, tile, &first);
     uint32_t total;
-    (void)srch_wg_scan(srch_flags(q, A.sel[4u * row]), s_w, &total);
+    (void)mrg_wg_scan_excl<SRCH_WG / 64, false, false>(srch_flags(q, A.sel[4u * row]), s_w, &total);
     if (threadIdx.x == 0) {
         uint32_t *c = A.cnt + 2u * ((uint64_t)row * A.ntile + tile);
         c[0] = total & 0xFFFFu;
@@ -290,7 +268,7 @@ __global__ __launch_bounds__(SRCH_WG) void k_srch_scan(SearchPlan A) {
         for (int k = 0; k < 2; ++k) {
             const uint32_t v = i < A.ntile ? c[2u * i + k] : 0u;
             uint32_t total;
-            const uint32_t ex = srch_wg_scan(v, s_w, &total);
+            const uint32_t ex = mrg_wg_scan_excl<SRCH_WG / 64, false, false>(v, s_w, &total);
             if (i < A.ntile) c[2u * i + k] = carry[k] + ex;
             carry[k] += total;
             __syncthreads();  // s_w is written again
@@ -307,7 +285,7 @@ __global__ __launch_bounds__(SRCH_WG) void k_srch_take(SearchPlan A) {
     const uint4 q = srch_load4(A, row, tile, &first);
     const uint32_t mine = srch_flags(q, thr);
     uint32_t total;
-    const uint32_t ex = srch_wg_scan(mine, s_w, &total);
+    const uint32_t ex = mrg_wg_scan_excl<SRCH_WG / 64, false, false>(mine, s_w, &total);
     if (!mine) return;
     const uint32_t *c = A.cnt + 2u * ((uint64_t)row * A.ntile + tile);
     uint32_t g = c[0] + (ex & 0xFFFFu), e = c[1] + (ex >> 16);
@@ -352,13 +330,13 @@ __global__ __launch_bounds__(SRCH_WG) void k_srch_order(SearchPlan A) {
 void mrg_search_launch_gather(const uint32_t *q_ids, uint64_t n_ids, const uint64_t *post_off, uint64_t n_words,
                               uint64_t *po, hipStream_t s, const uint64_t *df, uint64_t *dfo) {
     if (n_ids)
-        hipLaunchKernelGGL(k_srch_gather, dim3(grid_for(n_ids)), dim3(SRCH_WG), 0, s, q_ids, n_ids, post_off, n_words, po, df,
+        hipLaunchKernelGGL(k_srch_gather, dim3(grid_for(n_ids, SRCH_WG)), dim3(SRCH_WG), 0, s, q_ids, n_ids, post_off, n_words, po, df,
                            dfo);
 }
 
 void mrg_search_launch_sum(const uint32_t *doc_len, uint32_t n_docs, unsigned long long *sum, hipStream_t s) {
     if (!n_docs) return;
-    const unsigned g = (unsigned)std::min<uint64_t>(grid_for(n_docs), (uint64_t)srch_cus() * 4u);
+    const unsigned g = (unsigned)std::min<uint64_t>(grid_for(n_docs, SRCH_WG), (uint64_t)srch_cus() * 4u);
     hipLaunchKernelGGL(k_srch_sum, dim3(g), dim3(SRCH_WG), 0, s, doc_len, n_docs, sum);
 }
 
@@ -378,13 +356,13 @@ void mrg_search_launch_acc_bool(const SearchPlan &p, const SearchTile *tiles, ui
 
 void mrg_search_launch_filter(const SearchPlan &p, const SearchFilterRow *rows, uint32_t n, hipStream_t s) {
     if (!n) return;  // (n <= the chunk's rows <= 65535: a grid coordinate)
-    const unsigned gx = (unsigned)std::min<uint64_t>(grid_for(p.stride >> 2), std::max(1u, (unsigned)srch_cus() * 8u / n));
+    const unsigned gx = (unsigned)std::min<uint64_t>(grid_for(p.stride >> 2, SRCH_WG), std::max(1u, (unsigned)srch_cus() * 8u / n));
     hipLaunchKernelGGL(k_srch_filter, dim3(gx, n), dim3(SRCH_WG), 0, s, p, rows);
 }
 
 void mrg_search_launch_select(const SearchPlan &p, hipStream_t s) {
     // the rows of a chunk are independent: grid.y = the row (chunks hold at most 65535 rows)
-    const unsigned gx = (unsigned)std::min<uint64_t>(grid_for(p.stride >> 2), std::max(1u, (unsigned)srch_cus() * 8u / p.rows));
+    const unsigned gx = (unsigned)std::min<uint64_t>(grid_for(p.stride >> 2, SRCH_WG), std::max(1u, (unsigned)srch_cus() * 8u / p.rows));
     for (uint32_t d = 0; d < 4u; ++d) {
         hipLaunchKernelGGL(k_srch_hist, dim3(gx, p.rows), dim3(SRCH_WG), 0, s, p, d);
         hipLaunchKernelGGL(k_srch_pick, dim3(p.rows), dim3(256), 0, s, p, d);

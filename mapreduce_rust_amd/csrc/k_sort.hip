@@ -20,6 +20,7 @@ constexpr int IPT = 8;                  // items per thread
 constexpr int TILE = BS * IPT;          // 2048 items per tile
 
 // ------------------------------------------------------------------ block scan helpers
+// not mrg_wave_scan_incl / mrg_wg_scan_excl: their unsigned lane compare changes the scan kernels' code
 template <class T>
 __device__ __forceinline__ T wave_incl_scan(T v) {
     const int lane = __lane_id();

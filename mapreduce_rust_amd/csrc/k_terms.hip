@@ -39,45 +39,14 @@ int trm_cus() {
     return cu;
 }
 
-inline unsigned grid_for(uint64_t n, int b = TRM_WG) { return (unsigned)std::max<uint64_t>(1, (n + b - 1) / b); }
-
 // NT = 64: the caller is one wave with LDS of its own; NT = 256: the whole workgroup
 template <int NT>
 __device__ __forceinline__ void trm_sync() {
     if (NT == 64) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        mrg_wave_sync_lds();
     } else {
         __syncthreads();
     }
-}
-
-// exclusive scan of one value per thread over the NT threads; *total = the sum
-template <int NT>
-__device__ __forceinline__ uint32_t trm_scan(uint32_t v, uint32_t *s_red, uint32_t *total) {
-    const uint32_t lane = __lane_id();
-    uint32_t inc = v;
-    for (uint32_t o = 1; o < 64u; o <<= 1) {
-        const uint32_t u = __shfl_up(inc, o);
-        if (lane >= o) inc += u;
-    }
-    if (NT == 64) {
-        *total = __shfl(inc, 63);
-        return inc - v;
-    }
-    const uint32_t w = threadIdx.x >> 6;
-    if (lane == 63u) s_red[w] = inc;
-    __syncthreads();
-    uint32_t base = 0, tot = 0;
-    for (uint32_t i = 0; i < (uint32_t)(NT / 64); ++i) {
-        const uint32_t x = s_red[i];
-        if (i < w) base += x;
-        tot += x;
-    }
-    __syncthreads();  // s_red is reused by the next document
-    *total = tot;
-    return base + inc - v;
 }
 
 // One document by NT threads (tid = 0 .. NT - 1): s holds the padded length (a power of two >= NT), pos
@@ -122,7 +91,7 @@ __device__ __forceinline__ void trm_doc(const TermsPlan &A, uint32_t doc, uint32
         prev = v;
     }
     uint32_t tot;
-    const uint32_t pre = trm_scan<NT>(h | (u << 16), s_red, &tot);
+    const uint32_t pre = mrg_wg_scan_excl<NT / 64>(h | (u << 16), s_red, &tot);
     const uint32_t nd = tot & 0xFFFFu, nu = tot >> 16;  // (nu <= P <= 4096, nd likewise)
     if (!EMIT) {
         if (tid == 0) {
@@ -168,21 +137,10 @@ __global__ __launch_bounds__(TRM_WG) void k_terms_wg(TermsPlan A, const uint32_t
 }
 
 // ---- the large path
-// the slice document that holds position i: the last j with soff[j] <= i
-__device__ __forceinline__ uint32_t trm_find(const uint64_t *soff, uint32_t nd, uint64_t i) {
-    uint32_t a = 0, b = nd;  // soff[a] <= i < soff[b]
-    while (b - a > 1u) {
-        const uint32_t m = a + ((b - a) >> 1);
-        if (soff[m] <= i) a = m;
-        else b = m;
-    }
-    return a;
-}
-
 __global__ __launch_bounds__(TRM_WG) void k_terms_keys(TermsPlan A, TermsSlice S, uint64_t *keys) {
     const uint64_t i = (uint64_t)blockIdx.x * TRM_WG + threadIdx.x;
     if (i >= S.m) return;
-    const uint32_t j = trm_find(S.soff, S.nd, i);
+    const uint32_t j = mrg_last_le(S.soff, 0u, S.nd, i);  // the slice document that holds position i
     const uint64_t at = A.tok_off[S.ldoc[j]] + (i - S.soff[j]);
     const uint32_t v = A.in[at];
     if (v != TRM_UNK && (uint64_t)v >= A.n_words) atomicMin(A.err, (unsigned long long)at);
@@ -264,17 +222,17 @@ void mrg_terms_launch_lds(const TermsPlan &p, const uint32_t *list, uint32_t n, 
 }
 
 void mrg_terms_launch_keys(const TermsPlan &p, const TermsSlice &sl, uint64_t *keys, hipStream_t s) {
-    hipLaunchKernelGGL(k_terms_keys, dim3(grid_for(sl.m)), dim3(TRM_WG), 0, s, p, sl, keys);
+    hipLaunchKernelGGL(k_terms_keys, dim3(grid_for(sl.m, TRM_WG)), dim3(TRM_WG), 0, s, p, sl, keys);
 }
 void mrg_terms_launch_flags(const uint64_t *keys, uint64_t m, uint64_t n_words, uint32_t *flag, hipStream_t s) {
-    hipLaunchKernelGGL(k_terms_flags, dim3(grid_for(m + 1)), dim3(TRM_WG), 0, s, keys, m, n_words, flag);
+    hipLaunchKernelGGL(k_terms_flags, dim3(grid_for(m + 1, TRM_WG)), dim3(TRM_WG), 0, s, keys, m, n_words, flag);
 }
 void mrg_terms_launch_rows(const TermsPlan &p, const TermsSlice &sl, const uint64_t *keys, const uint32_t *E,
                            hipStream_t s) {
-    hipLaunchKernelGGL(k_terms_rows, dim3(grid_for(sl.nd)), dim3(TRM_WG), 0, s, p, sl, keys, E);
+    hipLaunchKernelGGL(k_terms_rows, dim3(grid_for(sl.nd, TRM_WG)), dim3(TRM_WG), 0, s, p, sl, keys, E);
 }
 void mrg_terms_launch_write(const TermsPlan &p, const TermsSlice &sl, const uint64_t *keys, const uint32_t *E,
                             uint32_t *pos, hipStream_t s) {
-    hipLaunchKernelGGL(k_terms_pos, dim3(grid_for(sl.m)), dim3(TRM_WG), 0, s, keys, sl.m, p.n_words, E, pos);
-    hipLaunchKernelGGL(k_terms_write, dim3(grid_for(sl.m)), dim3(TRM_WG), 0, s, p, sl, keys, E, (const uint32_t *)pos);
+    hipLaunchKernelGGL(k_terms_pos, dim3(grid_for(sl.m, TRM_WG)), dim3(TRM_WG), 0, s, keys, sl.m, p.n_words, E, pos);
+    hipLaunchKernelGGL(k_terms_write, dim3(grid_for(sl.m, TRM_WG)), dim3(TRM_WG), 0, s, p, sl, keys, E, (const uint32_t *)pos);
 }

@@ -20,8 +20,6 @@ namespace {
 
 constexpr uint64_t SEGB = 64;  // bytes per thread
 
-inline dim3 grid_for(uint64_t n, int b = 256) { return dim3((unsigned)((n + b - 1) / b)); }
-
 __device__ __forceinline__ void report(unsigned long long *err, uint64_t pos) {
     atomicMin(err, (unsigned long long)pos);
 }
@@ -243,7 +241,7 @@ __global__ void k_text_lines(const uint8_t *in, const uint64_t *fo, const uint64
     if (seg >= nseg) return;
     const uint64_t s0 = seg * SEGB;
     uint32_t lo = 0, hi = nf;  // file of this segment: the last f with fo[f] <= s0
-    while (hi - lo > 1) {
+    while (hi - lo > 1) {  // not mrg_last_le: its midpoint (no overflow at 2^31 files) costs this kernel an instruction
         const uint32_t mid = (lo + hi) >> 1;
         if (fo[mid] <= s0) lo = mid;
         else hi = mid;
@@ -305,31 +303,31 @@ __global__ void k_add_first(const SortRec *r, KeySet ks, uint64_t v) { ks.cnt[r[
 void mrg_launch_text_tok(const uint8_t *in, uint64_t n, uint32_t n_reduce, const uint64_t *base, uint64_t *cnt,
                          TextTok *out, unsigned long long *err, hipStream_t s) {
     const uint64_t nseg = (n + SEGB - 1) / SEGB;
-    if (nseg) hipLaunchKernelGGL(k_text_tok, grid_for(nseg), dim3(256), 0, s, in, n, n_reduce, base, cnt, out, err);
+    if (nseg) hipLaunchKernelGGL(k_text_tok, grid_for(nseg, 256), dim3(256), 0, s, in, n, n_reduce, base, cnt, out, err);
 }
 uint64_t mrg_text_segments(uint64_t n) { return (n + SEGB - 1) / SEGB; }
 void mrg_launch_text_keys(const TextTok *t, uint64_t n, uint64_t *part, uint32_t *idx, hipStream_t s) {
-    if (n) hipLaunchKernelGGL(k_text_keys, grid_for(n), dim3(256), 0, s, t, n, part, idx);
+    if (n) hipLaunchKernelGGL(k_text_keys, grid_for(n, 256), dim3(256), 0, s, t, n, part, idx);
 }
 void mrg_launch_text_len(const TextTok *t, const uint32_t *idx, uint64_t n, uint64_t *L, hipStream_t s) {
-    if (n) hipLaunchKernelGGL(k_text_len, grid_for(n), dim3(256), 0, s, t, idx, n, L);
+    if (n) hipLaunchKernelGGL(k_text_len, grid_for(n, 256), dim3(256), 0, s, t, idx, n, L);
 }
 void mrg_launch_text_part_off(const uint64_t *part, const uint64_t *O, uint64_t n, uint32_t R, uint64_t total,
                               uint64_t *part_off, hipStream_t s) {
-    hipLaunchKernelGGL(k_text_part_off, grid_for(n + 1), dim3(256), 0, s, part, O, n, R, total, part_off);
+    hipLaunchKernelGGL(k_text_part_off, grid_for(n + 1, 256), dim3(256), 0, s, part, O, n, R, total, part_off);
 }
 void mrg_launch_text_write(const uint8_t *in, const TextTok *t, const uint32_t *idx, uint64_t n, const uint64_t *O,
                            uint8_t *out, hipStream_t s) {
-    if (n) hipLaunchKernelGGL(k_text_write, grid_for(n), dim3(256), 0, s, in, t, idx, n, O, out);
+    if (n) hipLaunchKernelGGL(k_text_write, grid_for(n, 256), dim3(256), 0, s, in, t, idx, n, O, out);
 }
 void mrg_launch_utf8_check(const uint8_t *in, uint64_t n, unsigned long long *err, hipStream_t s) {
-    if (n) hipLaunchKernelGGL(k_utf8_check, grid_for(n), dim3(256), 0, s, in, n, err);
+    if (n) hipLaunchKernelGGL(k_utf8_check, grid_for(n, 256), dim3(256), 0, s, in, n, err);
 }
 void mrg_launch_text_lines(const uint8_t *in, const uint64_t *fo, const uint64_t *fe, uint32_t nf, uint64_t nseg,
                            const uint64_t *base, uint64_t *cnt, LRec *out, unsigned long long *err,
                            unsigned long long *nempty, hipStream_t s) {
     if (nseg)
-        hipLaunchKernelGGL(k_text_lines, grid_for(nseg), dim3(256), 0, s, in, fo, fe, nf, nseg, base, cnt, out, err,
+        hipLaunchKernelGGL(k_text_lines, grid_for(nseg, 256), dim3(256), 0, s, in, fo, fe, nf, nseg, base, cnt, out, err,
                            nempty);
 }
 void mrg_launch_add_first(const SortRec *r, KeySet ks, uint64_t v, hipStream_t s) {

@@ -274,8 +274,6 @@ __global__ void k_topk_gather(const SortRec *r, const uint32_t *vals, uint64_t m
     if (j < m) out[j] = r[vals[j]];
 }
 
-inline dim3 grid_for(uint64_t n, int b = 256) { return dim3((unsigned)((n + b - 1) / b)); }
-
 }  // namespace
 
 void mrg_topk_select(KeySet ks, uint64_t n, uint64_t want, TopkState *st, hipStream_t s) {
@@ -297,7 +295,7 @@ void mrg_topk_compact(KeySet ks, uint64_t n, TopkState *st, SortRec *out, uint64
 }
 
 void mrg_topk_cand_last(const SortRec *r, uint64_t m, KeySet ks, uint32_t R, uint32_t *cand_last, hipStream_t s) {
-    if (m) hipLaunchKernelGGL(k_topk_cand_last, grid_for(m), dim3(256), 0, s, r, m, ks, R, cand_last);
+    if (m) hipLaunchKernelGGL(k_topk_cand_last, grid_for(m, 256), dim3(256), 0, s, r, m, ks, R, cand_last);
 }
 
 void mrg_topk_exceed(KeySet ks, const uint8_t *heap, uint64_t n, const SortRec *r, uint32_t R,
@@ -309,9 +307,9 @@ void mrg_topk_exceed(KeySet ks, const uint8_t *heap, uint64_t n, const SortRec *
 
 void mrg_topk_count_keys(const SortRec *r, uint64_t m, KeySet ks, uint32_t R, const uint32_t *cand_last,
                          const uint32_t *exceeded, uint64_t *keys, uint32_t *vals, TopkState *st, hipStream_t s) {
-    if (m) hipLaunchKernelGGL(k_topk_count_keys, grid_for(m), dim3(256), 0, s, r, m, ks, R, cand_last, exceeded, keys, vals, st);
+    if (m) hipLaunchKernelGGL(k_topk_count_keys, grid_for(m, 256), dim3(256), 0, s, r, m, ks, R, cand_last, exceeded, keys, vals, st);
 }
 
 void mrg_topk_gather(const SortRec *r, const uint32_t *vals, uint64_t m, SortRec *out, hipStream_t s) {
-    if (m) hipLaunchKernelGGL(k_topk_gather, grid_for(m), dim3(256), 0, s, r, vals, m, out);
+    if (m) hipLaunchKernelGGL(k_topk_gather, grid_for(m, 256), dim3(256), 0, s, r, vals, m, out);
 }

@@ -51,14 +51,6 @@ constexpr uint32_t W_MAXD = 768;      // distinct keys a leaf may hold (75 % loa
 constexpr uint32_t W_SEGLDS = 2048;   // segment offsets cached in LDS per L1 tile
 constexpr uint32_t W_MAXSEG = 512;    // segmented L2: map workgroups (segments per bucket) at most
 
-// Workgroup barrier for LDS hand-offs only.  __syncthreads() also makes every wave wait for its
-// outstanding global stores (vmcnt(0)) -- a store's full round trip at each of the many barriers of a
-// leaf -- though no kernel here exchanges global data between its waves: only LDS needs ordering.
-__device__ __forceinline__ void lds_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-
-
 // ---------------------------------------------------------------- the map's records (count 1)
 // main segments: the tail regions of 12-byte records (bucket-major, map workgroup minor), the
 // per-bucket overflow lists, then the 16-byte tail regions (keys of 13..16 bytes) -- the order of
@@ -99,6 +91,7 @@ __device__ __forceinline__ void seg_rec(uint64_t segptr, uint64_t i, uint64_t &k
 }
 
 // s in [lo, hi) with off[s] <= i < off[s + 1]  (off non-decreasing; empty segments are skipped)
+// not mrg_last_le, here and in the three loops like it below: its midpoint a + (b - a) / 2 changes these kernels' code
 template <class OFF>
 __device__ __forceinline__ uint64_t seg_find(const OFF &off, uint64_t lo, uint64_t hi, uint64_t i) {
     while (hi - lo > 1) {
@@ -338,7 +331,7 @@ __global__ __launch_bounds__(W_WG, 1) void k_wl1(L1Args L) {
         s_lo = seg_find(off, 0, L.nseg, t0);
         s_hi = seg_find(off, 0, L.nseg, t1 - 1u) + 1u;
     }
-    lds_barrier();
+    mrg_lds_barrier();
     const uint64_t slo = s_lo, shi = s_hi;
     const bool cached = shi - slo + 1u <= W_SEGLDS;
     if (cached)
@@ -346,7 +339,7 @@ __global__ __launch_bounds__(W_WG, 1) void k_wl1(L1Args L) {
             s_off[x - slo] = L.off[x];
             if (x < shi) s_ptr[x - slo] = L.segptr[x];
         }
-    lds_barrier();
+    mrg_lds_barrier();
     // U records per thread per round: their loads are all in flight before the first is used.
     // A thread visits its records in increasing order, so it keeps its segment (first record, end,
     // base address) in registers and only steps to the next segment when a record crosses its end:
@@ -407,7 +400,7 @@ __global__ __launch_bounds__(W_WG, 1) void k_wl1(L1Args L) {
         }
     }
     if (!SCATTER) {
-        lds_barrier();
+        mrg_lds_barrier();
         for (uint32_t b = tid; b < L.B1; b += W_WG) L.cnt[(uint64_t)b * L.ntiles + t] = s_h[b];
     }
 }
@@ -417,33 +410,6 @@ __global__ void k_wbstart(const uint32_t *cnt, uint32_t B1, uint32_t ntiles, uin
     const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b < B1) bstart[b] = cnt[(uint64_t)b * ntiles];
     else if (b == B1) bstart[b] = n;
-}
-
-// ---------------------------------------------------------------- block helpers (1024 threads)
-__device__ __forceinline__ uint32_t wave_scan_incl(uint32_t v) {
-    const uint32_t lane = __lane_id();
-    for (uint32_t o = 1; o < 64; o <<= 1) {
-        const uint32_t u = __shfl_up(v, o);
-        if (lane >= o) v += u;
-    }
-    return v;
-}
-// exclusive block scan of one value per thread; s_ws holds NW words; *total = sum
-template <int NW = W_NW>
-__device__ __forceinline__ uint32_t block_scan_excl(uint32_t v, uint32_t *s_ws, uint32_t *total) {
-    const uint32_t lane = __lane_id(), w = threadIdx.x >> 6;
-    const uint32_t inc = wave_scan_incl(v);
-    if (lane == 63) s_ws[w] = inc;
-    lds_barrier();
-    uint32_t base = 0, tot = 0;
-    for (uint32_t i = 0; i < (uint32_t)NW; ++i) {
-        const uint32_t x = s_ws[i];
-        base += i < w ? x : 0u;
-        tot += x;
-    }
-    lds_barrier();
-    *total = tot;
-    return base + inc - v;
 }
 
 // wide map regions of bucket b (one wave): segment starts soff[b][w] (bucket-relative; a region holds
@@ -458,7 +424,7 @@ __global__ __launch_bounds__(64) void k_wmap_seg(const uint32_t *wcnt, uint32_t 
     for (uint32_t w0 = 0; w0 < grid; w0 += 64) {
         const uint32_t w = w0 + lane;
         const uint32_t v = w < grid ? min(c[w], wcap) : 0u;
-        const uint32_t inc = wave_scan_incl(v);
+        const uint32_t inc = mrg_wave_scan_incl(v);
         if (w < grid) so[w] = run + inc - v;
         run += (uint32_t)__shfl(inc, 63);
     }
@@ -559,7 +525,7 @@ __global__ __launch_bounds__(W_WG, 1) void k_wl2(L2Args L) {
 #endif
     if (SEG) {
         for (uint32_t w = tid; w <= L.grid + 1u; w += W_WG) s_cseg[w] = L.soff[(uint64_t)b * (L.grid + 2u) + w];
-        lds_barrier();
+        mrg_lds_barrier();
     }
     L2P(0);
     const uint64_t base = L.bstart[b], nb = L.bstart[b + 1] - base;
@@ -596,7 +562,7 @@ __global__ __launch_bounds__(W_WG, 1) void k_wl2(L2Args L) {
             s_smp[2 * k] = a;
             s_smp[2 * k + 1] = c;
         }
-        lds_barrier();
+        mrg_lds_barrier();
         {
             const uint64_t f0 = s_smp[0], f1 = s_smp[1];
             uint64_t o0 = 0, o1 = 0;
@@ -604,6 +570,7 @@ __global__ __launch_bounds__(W_WG, 1) void k_wl2(L2Args L) {
                 o0 |= s_smp[2 * k] ^ f0;
                 o1 |= s_smp[2 * k + 1] ^ f1;
             }
+            // not mrg_wave_or: the two words' butterflies interleaved; one after the other changes this kernel's code
             for (int o = 32; o > 0; o >>= 1) {
                 o0 |= __shfl_xor(o0, o);
                 o1 |= __shfl_xor(o1, o);
@@ -613,7 +580,7 @@ __global__ __launch_bounds__(W_WG, 1) void k_wl2(L2Args L) {
                 if (o1) { atomicOr(&s_dor[2], (uint32_t)o1); atomicOr(&s_dor[3], (uint32_t)(o1 >> 32)); }
             }
         }
-        lds_barrier();
+        mrg_lds_barrier();
         {
             // P: the first byte the sample differs on, but no later than the first byte the bucket's
             // bounds differ on -- keys outside the sample may differ earlier than it, never earlier
@@ -633,14 +600,14 @@ __global__ __launch_bounds__(W_WG, 1) void k_wl2(L2Args L) {
 #pragma unroll
             for (uint32_t t = 0; t < 3; ++t) dcode[256u * t + key_byte(a, c, dP + t)] = 1;
         }
-        lds_barrier();
+        mrg_lds_barrier();
         if (tid < 3u * 64u) {   // presence -> 2 x (present values below v) + (v present)
             const uint32_t t = tid >> 6, lane = tid & 63u;
             uint32_t *cw = reinterpret_cast<uint32_t *>(dcode + 256u * t);
             const uint32_t w0 = cw[2 * lane], w1 = cw[2 * lane + 1];   // values 4 lane .. 4 lane + 3
             const uint32_t pr[4] = {w0 & 1u, w0 >> 16, w1 & 1u, w1 >> 16};
             const uint32_t cnt = pr[0] + pr[1] + pr[2] + pr[3];
-            const uint32_t inc = wave_scan_incl(cnt);
+            const uint32_t inc = mrg_wave_scan_incl(cnt);
             uint32_t run = inc - cnt, e[4];
 #pragma unroll
             for (uint32_t x = 0; x < 4; ++x) {
@@ -651,7 +618,7 @@ __global__ __launch_bounds__(W_WG, 1) void k_wl2(L2Args L) {
             cw[2 * lane + 1] = e[2] | (e[3] << 16);
             if (lane == 63) s_dnv[t] = inc;
         }
-        lds_barrier();
+        mrg_lds_barrier();
         // radices n + 1: a value the sample lacks takes the code of the next present value (or n)
         // and zeroes the less significant codes, so the digit never decreases along the key order
         // (a lacking value collapsed onto a present one, with its lower bytes kept, would reorder)
@@ -677,7 +644,7 @@ __global__ __launch_bounds__(W_WG, 1) void k_wl2(L2Args L) {
             s_smp[2 * k] = a;
             s_smp[2 * k + 1] = c;
         }
-        lds_barrier();
+        mrg_lds_barrier();
         L2P(1);
         for (uint32_t size = 2; size <= P; size <<= 1) {
             for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
@@ -691,7 +658,7 @@ __global__ __launch_bounds__(W_WG, 1) void k_wl2(L2Args L) {
                         s_smp[2 * j] = a0; s_smp[2 * j + 1] = a1;
                     }
                 }
-                lds_barrier();
+                mrg_lds_barrier();
             }
         }
         L2P(2);
@@ -700,7 +667,7 @@ __global__ __launch_bounds__(W_WG, 1) void k_wl2(L2Args L) {
             s_spl[2 * q] = s_smp[2 * k];
             s_spl[2 * q + 1] = s_smp[2 * k + 1];
         }
-        lds_barrier();
+        mrg_lds_barrier();
         // the sample is dead now: its LDS holds the splitter index
         LeafIndex::build(s_spl, B2 - 1u, reinterpret_cast<uint16_t *>(s_smp), tid, W_WG);
     }
@@ -722,7 +689,7 @@ __global__ __launch_bounds__(W_WG, 1) void k_wl2(L2Args L) {
         s_cnt[j] = 0;
         s_cur[j] = 0;
     }
-    lds_barrier();
+    mrg_lds_barrier();
     // ---- histogram (U records per thread in flight)
     constexpr int U = MRG_WIDE_L2U;
     typedef uint64_t v2 __attribute__((ext_vector_type(2)));
@@ -763,7 +730,7 @@ __global__ __launch_bounds__(W_WG, 1) void k_wl2(L2Args L) {
                 }
         }
     }
-    lds_barrier();
+    mrg_lds_barrier();
     if (SEG && B2 > 1) {   // digit d -> leaf floor(records before d / target); the leaves' counts
         constexpr uint32_t PT = W_L2D / W_WG;
         uint32_t v[PT], sum = 0;
@@ -773,7 +740,7 @@ __global__ __launch_bounds__(W_WG, 1) void k_wl2(L2Args L) {
             sum += v[x];
         }
         uint32_t tot;
-        uint32_t run = block_scan_excl(sum, s_ws, &tot);
+        uint32_t run = mrg_wg_scan_excl<W_NW, true>(sum, s_ws, &tot);
 #pragma unroll
         for (uint32_t x = 0; x < PT; ++x) {
             const uint32_t leaf = min((uint32_t)(run / dtgt), B2 - 1u);
@@ -781,13 +748,13 @@ __global__ __launch_bounds__(W_WG, 1) void k_wl2(L2Args L) {
             if (v[x]) atomicAdd(&s_cnt[leaf], v[x]);
             run += v[x];
         }
-        lds_barrier();
+        mrg_lds_barrier();
     }
     L2P(4);
     {  // exclusive scan of the B2 <= 1024 counts, one per thread
         const uint32_t v = tid < B2 ? s_cnt[tid] : 0u;
         uint32_t tot;
-        const uint32_t ex = block_scan_excl(v, s_ws, &tot);
+        const uint32_t ex = mrg_wg_scan_excl<W_NW, true>(v, s_ws, &tot);
         if (tid < B2) s_cur[tid] = ex;
         const uint64_t lid = (uint64_t)b * MRG_WIDE_MAXB2 + tid;
         if (tid < B2) {
@@ -812,7 +779,7 @@ __global__ __launch_bounds__(W_WG, 1) void k_wl2(L2Args L) {
         }
         if (tid == 0) L.nleaf[b] = B2;
     }
-    lds_barrier();
+    mrg_lds_barrier();
     L2P(5);
     // ---- scatter, staged through LDS: a chunk of W_SC records is counting-sorted by leaf in LDS,
     // then stored so that consecutive threads write consecutive records of one leaf (a run of ~8
@@ -859,17 +826,17 @@ __global__ __launch_bounds__(W_WG, 1) void k_wl2(L2Args L) {
             else j[u] = gw(L.sub)[base + i];
         }
         if (tid < B2) s_cnt[tid] = 0;
-        lds_barrier();
+        mrg_lds_barrier();
 #pragma unroll
         for (uint32_t u = 0; u < SU; ++u)
             if (tid + u * W_WG < nc) r[u] = atomicAdd(&s_cnt[j[u]], 1u);
-        lds_barrier();
+        mrg_lds_barrier();
         {
             uint32_t tot;
-            const uint32_t ex = block_scan_excl(tid < B2 ? s_cnt[tid] : 0u, s_ws, &tot);
+            const uint32_t ex = mrg_wg_scan_excl<W_NW, true>(tid < B2 ? s_cnt[tid] : 0u, s_ws, &tot);
             if (tid < B2) s_bst[tid] = ex;
         }
-        lds_barrier();
+        mrg_lds_barrier();
 #pragma unroll
         for (uint32_t u = 0; u < SU; ++u)
             if (tid + u * W_WG < nc) {
@@ -877,7 +844,7 @@ __global__ __launch_bounds__(W_WG, 1) void k_wl2(L2Args L) {
                 stg[p] = x[u];
                 stl[p] = (uint16_t)j[u];
             }
-        lds_barrier();
+        mrg_lds_barrier();
 #pragma unroll
         for (uint32_t u = 0; u < SU; ++u) {
             const uint32_t p = tid + u * W_WG;
@@ -887,10 +854,10 @@ __global__ __launch_bounds__(W_WG, 1) void k_wl2(L2Args L) {
                 outv[d] = stg[p];   // (exact counts: a record lands inside its leaf)
             }
         }
-        lds_barrier();
+        mrg_lds_barrier();
         if (tid < B2) s_cur[tid] += s_cnt[tid];   // the thread that zeroes s_cnt[tid] next chunk
     }
-    lds_barrier();
+    mrg_lds_barrier();
     if (tid < B2) L.leaf_hi[(uint64_t)b * MRG_WIDE_MAXB2 + tid] = base + s_cur[tid];   // where each leaf ends in `out`
     L2P(6);
 #ifdef MRG_WIDE_PROF
@@ -1047,7 +1014,7 @@ __global__ __launch_bounds__(W_LWG, 3) void k_wleaf(LeafArgs L) {
         s_bytes = 0;
     }
     for (uint32_t i = tid; i < W_NDIG; i += W_LWG) s_dcnt[i] = 0;
-    lds_barrier();
+    mrg_lds_barrier();
     for (uint32_t i = blockIdx.x; i < nlist; i += gridDim.x) {
         uint64_t lid, mlo, mhi;
         leaf_at(i, lid, mlo, mhi);
@@ -1089,6 +1056,7 @@ __global__ __launch_bounds__(W_LWG, 3) void k_wleaf(LeafArgs L) {
                 o0 |= key[k].x ^ f.x;
                 o1 |= key[k].y ^ f.y;
             }
+            // not mrg_wave_or: the two words' butterflies interleaved; one after the other changes this kernel's code
             for (int o = 32; o > 0; o >>= 1) {
                 o0 |= __shfl_xor(o0, o);
                 o1 |= __shfl_xor(o1, o);
@@ -1097,7 +1065,7 @@ __global__ __launch_bounds__(W_LWG, 3) void k_wleaf(LeafArgs L) {
                 atomicOr((unsigned long long *)&s_or0, (unsigned long long)o0);
                 atomicOr((unsigned long long *)&s_or1, (unsigned long long)o1);
             }
-            lds_barrier();
+            mrg_lds_barrier();
             WP(0);
             const uint64_t r0 = s_or0, r1 = s_or1;
             uint32_t hb = r0 ? (uint32_t)__builtin_clzll(r0) : (r1 ? 64u + (uint32_t)__builtin_clzll(r1) : 0u);
@@ -1112,7 +1080,7 @@ __global__ __launch_bounds__(W_LWG, 3) void k_wleaf(LeafArgs L) {
                     within[k] = atomicAdd(&s_dcnt[dg[k]], 1u);
                 }
             }
-            lds_barrier();
+            mrg_lds_barrier();
             {
                 constexpr uint32_t PT = W_NDIG / W_LWG;
                 uint32_t v[PT], sum = 0, mx = 0;
@@ -1124,21 +1092,21 @@ __global__ __launch_bounds__(W_LWG, 3) void k_wleaf(LeafArgs L) {
                 }
                 if (mx > W_MAXBKT) atomicMax(&s_maxb, mx);
                 uint32_t tot;
-                uint32_t run = block_scan_excl<W_LNW>(sum, s_ws, &tot);
+                uint32_t run = mrg_wg_scan_excl<W_LNW, true>(sum, s_ws, &tot);
 #pragma unroll
                 for (uint32_t x = 0; x < PT; ++x) {
                     s_doff[tid * PT + x] = (uint16_t)run;
                     run += v[x];
                 }
             }
-            lds_barrier();
+            mrg_lds_barrier();
             WP(1);
             const bool small = s_maxb == 0;
             if (small) {
 #pragma unroll
                 for (uint32_t k = 0; k < W_LR; ++k)
                     if (dg[k] != 0xFFFFFFFFu) s_kb[s_doff[dg[k]] + within[k]] = key[k];
-                lds_barrier();
+                mrg_lds_barrier();
 #pragma unroll
                 for (uint32_t k = 0; k < W_LR; ++k) {
                     if (dg[k] == 0xFFFFFFFFu) continue;
@@ -1152,7 +1120,7 @@ __global__ __launch_bounds__(W_LWG, 3) void k_wleaf(LeafArgs L) {
                     s_kc[bs + rank] = key[k];
                     s_cc[bs + rank] = cnt[k];
                 }
-                lds_barrier();
+                mrg_lds_barrier();
                 WP(2);
                 for (uint32_t i = tid; i < W_NDIG; i += W_LWG) s_dcnt[i] = 0;   // for the next leaf
                 // runs of equal keys: thread t owns sorted items [W_LR t, W_LR t + W_LR)
@@ -1173,7 +1141,7 @@ __global__ __launch_bounds__(W_LWG, 3) void k_wleaf(LeafArgs L) {
                     nh += head[k] ? 1u : 0u;
                 }
                 uint32_t D;
-                uint32_t dpos = block_scan_excl<W_LNW>(nh, s_ws, &D);
+                uint32_t dpos = mrg_wg_scan_excl<W_LNW, true>(nh, s_ws, &D);
                 WP(3);
                 uint64_t bytes = 0;
 #pragma unroll
@@ -1194,9 +1162,10 @@ __global__ __launch_bounds__(W_LWG, 3) void k_wleaf(LeafArgs L) {
                     if (dpos == D - 1) L.leaf_last[lid] = ll;
                     ++dpos;
                 }
+                // not mrg_wave_sum: the call changes this kernel's code (the operand order of its 64-bit adds)
                 for (int o = 32; o > 0; o >>= 1) bytes += __shfl_xor(bytes, o);
                 if (lane == 0 && bytes) atomicAdd((unsigned long long *)&s_bytes, (unsigned long long)bytes);
-                lds_barrier();
+                mrg_lds_barrier();
                 if (tid == 0) {
                     L.leaf_out[lid] = out0;
                     L.leaf_nd[lid] = D;
@@ -1207,13 +1176,13 @@ __global__ __launch_bounds__(W_LWG, 3) void k_wleaf(LeafArgs L) {
                     s_or1 = 0;
                     s_bytes = 0;
                 }
-                lds_barrier();
+                mrg_lds_barrier();
                 WP(4);
                 continue;
             }
             // a bucket too large to rank by comparisons (many equal keys): the hash path below, once
             // every wave has read s_maxb
-            lds_barrier();
+            mrg_lds_barrier();
         }
         // table size: a power of two >= 2 x records (a leaf of duplicates still fits: distinct counts)
         uint32_t S = 64;
@@ -1230,7 +1199,7 @@ __global__ __launch_bounds__(W_LWG, 3) void k_wleaf(LeafArgs L) {
             s_or1 = 0;
             s_bytes = 0;
         }
-        lds_barrier();
+        mrg_lds_barrier();
         WP(0);
         // ---- sum the records per key (exact: full keys compared; slots fill monotonically)
         auto add = [&](uint64_t a, uint64_t c, uint64_t n) {
@@ -1270,7 +1239,7 @@ __global__ __launch_bounds__(W_LWG, 3) void k_wleaf(LeafArgs L) {
             if (s_ovf) break;
             add(L.wk0[wlo + i], L.wk1[wlo + i], L.wcnt[wlo + i]);
         }
-        lds_barrier();
+        mrg_lds_barrier();
         WP(1);
         if (s_ovf) {  // finished by the global fallback (mrg_agg.cpp wide_finish)
             if (tid == 0) {
@@ -1286,15 +1255,15 @@ __global__ __launch_bounds__(W_LWG, 3) void k_wleaf(LeafArgs L) {
                 s_bytes = 0;
             }
             for (uint32_t i = tid; i < W_NDIG; i += W_LWG) s_dcnt[i] = 0;
-            lds_barrier();
+            mrg_lds_barrier();
             continue;
         }
         // ---- compact the distinct keys (s_kc, s_cc); clear the digit counts
         const uint32_t D = s_nd;
-        lds_barrier();
+        mrg_lds_barrier();
         if (tid == 0) s_nd = 0;
         for (uint32_t i = tid; i < W_NDIG; i += W_LWG) s_dcnt[i] = 0;
-        lds_barrier();
+        mrg_lds_barrier();
         for (uint32_t i0 = 0; i0 < S; i0 += W_LWG) {
             const uint32_t i = i0 + tid;
             v2 k = v2{0, 0};
@@ -1314,7 +1283,7 @@ __global__ __launch_bounds__(W_LWG, 3) void k_wleaf(LeafArgs L) {
                 s_cc[pos] = n;
             }
         }
-        lds_barrier();
+        mrg_lds_barrier();
         // ---- my items (compacted index p = k * W_LWG + tid) in registers; the bits keys differ on
         const uint32_t NR = (D + W_LWG - 1) / W_LWG;   // items per thread (<= W_LR)
         v2 key[W_LR];
@@ -1332,6 +1301,7 @@ __global__ __launch_bounds__(W_LWG, 3) void k_wleaf(LeafArgs L) {
                     o1 |= key[k].y ^ f.y;
                 }
             }
+            // not mrg_wave_or: the two words' butterflies interleaved; one after the other changes this kernel's code
             for (int o = 32; o > 0; o >>= 1) {
                 o0 |= __shfl_xor(o0, o);
                 o1 |= __shfl_xor(o1, o);
@@ -1341,7 +1311,7 @@ __global__ __launch_bounds__(W_LWG, 3) void k_wleaf(LeafArgs L) {
                 atomicOr((unsigned long long *)&s_or1, (unsigned long long)o1);
             }
         }
-        lds_barrier();
+        mrg_lds_barrier();
         WP(2);
         const uint64_t o0 = s_or0, o1 = s_or1;
         // first differing bit (0 = most significant bit of k0); the digit = the W_DBITS bits from there
@@ -1358,7 +1328,7 @@ __global__ __launch_bounds__(W_LWG, 3) void k_wleaf(LeafArgs L) {
                 within[k] = atomicAdd(&s_dcnt[dg[k]], 1u);  // slot inside the bucket (any order)
             }
         }
-        lds_barrier();
+        mrg_lds_barrier();
         {  // exclusive scan of the digit counts, W_NDIG / W_LWG per thread; note the largest bucket
             constexpr uint32_t PT = W_NDIG / W_LWG;
             uint32_t v[PT], sum = 0, mx = 0;
@@ -1369,13 +1339,13 @@ __global__ __launch_bounds__(W_LWG, 3) void k_wleaf(LeafArgs L) {
             }
             if (mx > W_MAXBKT) atomicMax(&s_maxb, mx);
             uint32_t tot;
-            uint32_t run = block_scan_excl<W_LNW>(sum, s_ws, &tot);
+            uint32_t run = mrg_wg_scan_excl<W_LNW, true>(sum, s_ws, &tot);
             for (uint32_t x = 0; x < PT; ++x) {
                 s_doff[tid * PT + x] = (uint16_t)run;
                 run += v[x];
             }
         }
-        lds_barrier();
+        mrg_lds_barrier();
         WP(3);
         uint64_t bytes = 0;
         if (s_maxb == 0) {
@@ -1383,7 +1353,7 @@ __global__ __launch_bounds__(W_LWG, 3) void k_wleaf(LeafArgs L) {
 #pragma unroll
             for (uint32_t k = 0; k < W_LR; ++k)
                 if (dg[k] != 0xFFFFFFFFu) s_kb[s_doff[dg[k]] + within[k]] = key[k];
-            lds_barrier();
+            mrg_lds_barrier();
 #pragma unroll
             for (uint32_t k = 0; k < W_LR; ++k) {
                 if (dg[k] == 0xFFFFFFFFu) continue;
@@ -1409,14 +1379,14 @@ __global__ __launch_bounds__(W_LWG, 3) void k_wleaf(LeafArgs L) {
         } else {
             // ---- LSD radix sort of the index list by the varying key bytes (stable, per-wave ranks)
             for (uint32_t p = tid; p < D; p += W_LWG) s_ia[p] = (uint16_t)p;
-            lds_barrier();
+            mrg_lds_barrier();
             const int qlo = (int)(hb >> 3);
             const int qhi = o1 ? 15 - (int)(__builtin_ctzll(o1) >> 3) : 7 - (int)(__builtin_ctzll(o0) >> 3);
             uint16_t *src = s_ia, *dst = s_ib;
             uint16_t *s_wc = s_x;
             for (int q = qhi; q >= qlo; --q) {
                 for (uint32_t i = tid; i < NR * W_LNW * 256; i += W_LWG) s_wc[i] = 0;
-                lds_barrier();
+                mrg_lds_barrier();
                 uint32_t rk[W_LR];
 #pragma unroll
                 for (uint32_t k = 0; k < W_LR; ++k) {
@@ -1438,7 +1408,7 @@ __global__ __launch_bounds__(W_LWG, 3) void k_wleaf(LeafArgs L) {
                     dg[k] = d;
                     rk[k] = valid ? rank : 0xFFFFFFFFu;
                 }
-                lds_barrier();
+                mrg_lds_barrier();
                 {  // exclusive scan over the cells in (digit, round, wave) order: stable positions
                     const uint32_t C = 256u * NR * W_LNW, per = C / W_LWG;
                     uint32_t v[4 * W_LR];
@@ -1449,21 +1419,21 @@ __global__ __launch_bounds__(W_LWG, 3) void k_wleaf(LeafArgs L) {
                         sum += v[x];
                     }
                     uint32_t tot;
-                    uint32_t run = block_scan_excl<W_LNW>(sum, s_ws, &tot);
+                    uint32_t run = mrg_wg_scan_excl<W_LNW, true>(sum, s_ws, &tot);
 #pragma unroll
                     for (uint32_t x = 0; x < 4 * W_LR; ++x) {
                         if (x < per) s_wc[tid * per + x] = (uint16_t)run;
                         run += v[x];
                     }
                 }
-                lds_barrier();
+                mrg_lds_barrier();
 #pragma unroll
                 for (uint32_t k = 0; k < W_LR; ++k) {
                     if (k >= NR) break;
                     const uint32_t p = k * W_LWG + tid;
                     if (rk[k] != 0xFFFFFFFFu) dst[s_wc[(dg[k] * NR + k) * W_LNW + wv] + rk[k]] = src[p];
                 }
-                lds_barrier();
+                mrg_lds_barrier();
                 uint16_t *tmp = src;
                 src = dst;
                 dst = tmp;
@@ -1480,9 +1450,10 @@ __global__ __launch_bounds__(W_LWG, 3) void k_wleaf(LeafArgs L) {
             }
         }
         WP(4);
+        // not mrg_wave_sum: the call changes this kernel's code (the operand order of its 64-bit adds)
         for (int o = 32; o > 0; o >>= 1) bytes += __shfl_xor(bytes, o);
         if (lane == 0 && bytes) atomicAdd((unsigned long long *)&s_bytes, (unsigned long long)bytes);
-        lds_barrier();
+        mrg_lds_barrier();
         if (tid == 0) {
             L.leaf_out[lid] = out0;
             L.leaf_nd[lid] = D;
@@ -1495,7 +1466,7 @@ __global__ __launch_bounds__(W_LWG, 3) void k_wleaf(LeafArgs L) {
             s_bytes = 0;
         }
         for (uint32_t i = tid; i < W_NDIG; i += W_LWG) s_dcnt[i] = 0;
-        lds_barrier();
+        mrg_lds_barrier();
         WP(5);
     }
 #ifdef MRG_WIDE_PROF
@@ -1544,6 +1515,7 @@ static_assert(W_VC <= 0x8000u, "s_ix holds sorted positions below the 0x8000 pad
 static_assert(W_VQ * W_VPASS == MRG_WIDE_MAXB2, "the waves of an L1 bucket pass on at most MAXB2 leaves together");
 static_assert(W_VRG >= 1 && W_VRG <= W_VIPL, "rank-loop row groups within the lane's rows");
 
+// not mrg_wave_sync_lds: the fences change k_wleafw's code
 __device__ __forceinline__ void wave_lds_sync() {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 }
@@ -1552,10 +1524,6 @@ __device__ __forceinline__ uint32_t first_bit(uint64_t o0, uint64_t o1) {   // 1
 }
 __device__ __forceinline__ uint32_t key_bit(uint64_t k0, uint64_t k1, uint32_t hb) {
     return hb < 64 ? (uint32_t)(k0 >> (63u - hb)) & 1u : (uint32_t)(k1 >> (127u - hb)) & 1u;
-}
-__device__ __forceinline__ uint64_t wave_or(uint64_t v) {
-    for (int o = 32; o > 0; o >>= 1) v |= __shfl_xor(v, o);
-    return v;
 }
 
 #ifndef MRG_WIDE_VWPE
@@ -1627,6 +1595,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MRG_WIDE_VWP
         uint64_t csum = 0;
 #pragma unroll
         for (uint32_t k = 0; k < W_VIPL; ++k) csum += cnt[k];
+        // not mrg_wave_sum: the call changes this kernel's code (the operand order of its 64-bit adds)
         for (int o = 32; o > 0; o >>= 1) csum += __shfl_xor(csum, o);
         bool big = csum > 0xFFFFFFFFull;
         VP(0);
@@ -1652,8 +1621,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MRG_WIDE_VWP
             o0 |= key[k].x ^ f.x;
             o1 |= key[k].y ^ f.y;
         }
-        o0 = wave_or(o0);
-        o1 = wave_or(o1);
+        o0 = mrg_wave_or(o0);
+        o1 = mrg_wave_or(o1);
         const uint32_t hb = first_bit(o0, o1);
         uint32_t D = 0, my_last = 0xFFFFFFFFu, my_ll = 0;
         uint64_t bytes = 0;
@@ -1661,6 +1630,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MRG_WIDE_VWP
             uint64_t n = 0;
 #pragma unroll
             for (uint32_t k = 0; k < W_VIPL; ++k) n += cnt[k];
+            // not mrg_wave_sum: the call changes this kernel's code (the operand order of its 64-bit adds)
             for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o);
             if (NT) {
                 D = 1;
@@ -1706,7 +1676,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MRG_WIDE_VWP
                 uint32_t *cw = reinterpret_cast<uint32_t *>(code + 256u * t);
                 const uint32_t w = cw[lane];
                 const uint32_t c = (w & 1u) + ((w >> 8) & 1u) + ((w >> 16) & 1u) + (w >> 24);
-                const uint32_t inc = wave_scan_incl(c);
+                const uint32_t inc = mrg_wave_scan_incl(c);
                 uint32_t r = inc - c, o = 0;
 #pragma unroll
                 for (uint32_t bb = 0; bb < 4; ++bb) {
@@ -1751,19 +1721,19 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MRG_WIDE_VWP
                     sum += v[x];
                     mx = max(mx, v[x]);
                 }
-                uint32_t run = wave_scan_incl(sum) - sum;
+                uint32_t run = mrg_wave_scan_incl(sum) - sum;
 #pragma unroll
                 for (uint32_t x = 0; x < PT; ++x) {
                     s_ds[lane * PT + x] = run;   // (in place: this lane read its counts above)
                     run += v[x];
                 }
                 if (lane == 63) s_ds[W_VND] = run;
-                for (int o = 32; o > 0; o >>= 1) mx = max(mx, (uint32_t)__shfl_xor(mx, o));
+                mx = mrg_wave_max(mx);
 #ifdef MRG_WIDE_PROF
                 uint32_t nz = 0;
 #pragma unroll
                 for (uint32_t x = 0; x < PT; ++x) nz += v[x] != 0u ? 1u : 0u;
-                for (int o = 32; o > 0; o >>= 1) nz += (uint32_t)__shfl_xor(nz, o);
+                nz = mrg_wave_sum(nz);
                 if (lane == 0) {
                     atomicAdd(&L.prof[14], (unsigned long long)nz);
                     atomicAdd(&L.prof[15], (unsigned long long)mx);
@@ -1874,6 +1844,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MRG_WIDE_VWP
         }
         VP(4);
         if (D && my_last == D - 1) L.leaf_last[lid] = my_ll;
+        // not mrg_wave_sum: the call changes this kernel's code (the operand order of its 64-bit adds)
         for (int o = 32; o > 0; o >>= 1) bytes += __shfl_xor(bytes, o);
         if (lane == 0) {
             L.leaf_out[lid] = out0;
@@ -1969,6 +1940,7 @@ __device__ __forceinline__ uint32_t line_words(uint64_t k0, uint64_t k1, uint64_
 constexpr uint32_t WW_WG = 256, WW_NW = WW_WG / 64;
 constexpr uint32_t WW_PER = 16;                          // workgroups per L1 bucket (64 waves stride its leaves)
 constexpr uint32_t WW_STGW = (16 + 64 * 38 + 64) / 4;   // stage dwords per wave: carried vector + 64 lines + slack
+// not mrg_wave_sync_lds: the fences change k_wwritew's code
 __device__ __forceinline__ void ww_sync() {   // the wave's LDS ops so far have completed (atomics included)
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_wave_barrier();
@@ -2009,7 +1981,7 @@ __global__ __launch_bounds__(WW_WG) void k_wwritew(const uint64_t *keys, const u
             uint64_t w[5] = {0, 0, 0, 0, 0};
             const uint32_t lw = line_words(kk.x, c, nw, w);
             const uint32_t ll = act ? lw : 0u;
-            const uint32_t incl = wave_scan_incl(ll), tot = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+            const uint32_t incl = mrg_wave_scan_incl(ll), tot = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
             if (ll) {
                 const uint32_t o = sh + incl - ll, base = o >> 2, bs = 8u * (o & 3u);
                 const uint32_t ndw = ((o & 3u) + ll + 3u) >> 2;
@@ -2172,9 +2144,9 @@ __global__ void k_wfb_stats(const uint32_t *list, uint32_t nlist, const uint64_t
         bytes += line_len(keys[2 * (o0 + p)], keys[2 * (o0 + p) + 1], ocnt[o0 + p]);
     __shared__ unsigned long long s_b;
     if (threadIdx.x == 0) s_b = 0;
-    lds_barrier();
+    mrg_lds_barrier();
     atomicAdd(&s_b, (unsigned long long)bytes);
-    lds_barrier();
+    mrg_lds_barrier();
     if (threadIdx.x == 0) {
         leaf_nd[lid] = (uint32_t)D;
         leaf_bytes[lid] = s_b;

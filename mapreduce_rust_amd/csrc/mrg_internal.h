@@ -138,6 +138,9 @@ struct Scratch {
 
 }  // namespace mrg_host
 
+// Workgroups of `block` threads that give each of n items a thread; at least one.
+inline unsigned grid_for(uint64_t n, uint64_t block) { return (unsigned)std::max<uint64_t>(1, (n + block - 1) / block); }
+
 struct MapArgs {
     const uint8_t *in;
     const uint64_t *doc_off;     // [n_docs + 1] byte offsets into `in`
